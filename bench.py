@@ -21,6 +21,11 @@ A run never reports fewer GPUs than it was asked for: `--gpus N` with fewer than
 WORLD_SIZE that is not N, exits non-zero before anything is timed (the reference takes --num-gpu the same way:
 /root/reference/src/main.cpp:147-148 -> iyokan_cufhe.cpp:530-536).
 
+A plain run sets up, warms up, times the --steps steps and prints the line (metric, value, unit, ms_per_step, dtype, config).
+`--full` adds everything else: the decrypt and word checks of the timed step, the weak-scaling leg, the `roofline` object and the
+CPU baseline.  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs) for comparing two builds; the inputs
+depend on the arguments only (seeded keys, bits and encryptions).
+
 Prints ONE JSON line on rank 0 (see README of the contract in DESIGN.md §Measurement).
 """
 import argparse
@@ -49,7 +54,12 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--gates", type=int, default=65536, help="gates per step, whole job (sharded over the GPUs)")
-    ap.add_argument("--no-weak", action="store_true", help="skip the extra weak-scaling measurement at N > 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: decrypt and word checks of the timed step, the weak-scaling "
+                         "leg at N > 1, the roofline object and the CPU baseline (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-weak", action="store_true", help="skip the extra weak-scaling measurement at N > 1 (--full)")
     ap.add_argument("--params", default="128bit", choices=["128bit", "80bit"])
     ap.add_argument("--decomp", default=None, choices=["split", "direct"],
                     help="80-bit set: gadget decomposition on the FP64 path (IYK_HIP_DECOMP; default split = exact "
@@ -57,7 +67,7 @@ def parse_args():
     ap.add_argument("--op", default="NAND", choices=["AND", "NAND", "ANDNOT", "OR", "NOR", "ORNOT", "XOR", "XNOR"],
                     help="binary gate of the flat batch (BASELINE config #2 is NAND)")
     ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="gates timed on the CPU oracle for cpu_baseline (-1: sized for ~15 s, 0: skip)")
+                    help="gates timed on the CPU oracle for cpu_baseline (--full; -1: sized for ~15 s, 0: skip)")
     ap.add_argument("--spawn", action="store_true",
                     help="re-execute under torch.distributed.run even for --gpus 1 (exercises the RCCL path on one GPU)")
     ap.add_argument("--traffic-bytes", type=float, default=None,
@@ -295,6 +305,30 @@ def word_check(params_name, op, first_gate, rows):
     return bool(np.array_equal(got, want[first_gate: first_gate + len(rows)]))
 
 
+DUMP_SEED = 20261016
+DUMP_ROWS = 8192   # whole output ciphertexts kept by --dump-outputs: 8 192 x 637 words x 8 bytes = 42 MB at the 128-bit set
+
+
+def dump_outputs(dirname, out_t, first_gate, total, rank, world):
+    """--dump-outputs: what the last timed step left in this rank's output block `out_t` (device int32, one TLWE row per gate,
+    first_gate = the block's first gate of the whole batch), as float64 files (every u32 torus word exactly):
+      out_body.npy        the body word b of EVERY output ciphertext of the block
+      out_ciphertexts.npy whole ciphertexts (a_0 .. a_{n-1}, b) of a fixed seeded sample of DUMP_ROWS gates of the batch
+      out_gate_index.npy  the gate index of each sampled row
+    At N > 1 every rank writes its own block's files with the suffix _rank<r>; the sample is drawn over the whole batch."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=min(total, DUMP_ROWS), replace=False))
+    pick = pick[(pick >= first_gate) & (pick < first_gate + out_t.shape[0])]
+    rows = out_t[torch.from_numpy(pick - first_gate).to(out_t.device)]
+    words = {"out_body": out_t[:, -1], "out_ciphertexts": rows}
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, t in words.items():
+        np.save(os.path.join(dirname, name + suffix + ".npy"), t.contiguous().cpu().numpy().view(np.uint32).astype(np.float64))
+    np.save(os.path.join(dirname, "out_gate_index" + suffix + ".npy"), pick.astype(np.float64))
+
+
 EXIT_BAD_WORLD = 3   # --gpus does not match the ranks that exist / the devices that are visible
 
 
@@ -370,7 +404,8 @@ def main():
     op_code = OPS[args.op]
     G_total = args.gates
     _, G_mine = shard(G_total, world, rank)      # strong scaling: this rank's block of the one batch
-    G_alloc = G_total if (world > 1 and not args.no_weak) else G_mine   # the weak leg runs G_total gates per rank
+    # the weak leg (--full) runs G_total gates per rank; a plain run allocates the same, so its inputs do not depend on --full
+    G_alloc = G_total if (world > 1 and not args.no_weak) else G_mine
 
     # ---- keys: rank 0 generates, RCCL broadcast (north_star: "bootstrapping key broadcast once") ----
     keys = client.keygen(params, seed=1) if rank == 0 else empty_keys(params)
@@ -429,17 +464,22 @@ def main():
         return elapsed, nb, br_ms, ks_ms, per_rank
 
     elapsed, nb, br_ms, ks_ms, per_rank = timed(G_mine, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, arena_t[2 * G_alloc: 2 * G_alloc + G_mine], shard(G_total, world, rank)[0], G_total,
+                     rank, world)
 
-    # ---- correctness of what was just timed: decrypt every output of the last step ----
-    got = arena_t[2 * G_alloc: 2 * G_alloc + G_mine].cpu().numpy().view(np.uint32)
-    want = np.array([PLAIN[args.op](int(a), int(b)) for a, b in zip(bits[:G_mine], bits[G_alloc: G_alloc + G_mine])],
-                    dtype=np.uint8)
-    decrypt_ok = bool(np.array_equal(client.decrypt_bits(keys, got), want))
-    # ... and, on rank 0 (whose inputs are the committed workload's), the WORDS of the timed step against the oracle's digests
-    words_ok = word_check(args.params, args.op, 0, got) if (rank == 0 and G_alloc == 65536 and G_total == 65536) else None
+    # ---- everything below up to the JSON line runs with --full only ----
+    # correctness of what was just timed: decrypt every output of the last step
+    decrypt_ok = words_ok = weak = roofline = None
+    if args.full:
+        got = arena_t[2 * G_alloc: 2 * G_alloc + G_mine].cpu().numpy().view(np.uint32)
+        want = np.array([PLAIN[args.op](int(a), int(b)) for a, b in zip(bits[:G_mine], bits[G_alloc: G_alloc + G_mine])],
+                        dtype=np.uint8)
+        decrypt_ok = bool(np.array_equal(client.decrypt_bits(keys, got), want))
+        # ... and, on rank 0 (whose inputs are the committed workload's), the WORDS of the timed step against the oracle's digests
+        words_ok = word_check(args.params, args.op, 0, got) if (rank == 0 and G_alloc == 65536 and G_total == 65536) else None
 
-    weak = None
-    if world > 1 and not args.no_weak:
+    if args.full and world > 1 and not args.no_weak:
         w_elapsed, _, _, _, _ = timed(G_total, args.steps, 1)
         weak = {"value": G_total * world * args.steps / w_elapsed, "unit": "gates/s",
                 "gates_per_step_per_gpu": G_total, "ms_per_step": w_elapsed / args.steps * 1e3, "scaling": "weak"}
@@ -447,6 +487,7 @@ def main():
     if rank == 0:
         path = hip.ntt_path()                         # "fft" (default), "fp50", "goldilocks"
         value = G_total * args.steps / elapsed
+    if rank == 0 and args.full:
         b_gate = params.gate_algorithmic_bytes(rotations=1, inputs=2)
         # dominant kernel = blind_rotate: its share of B_gate is the BK stream at 8 bytes per key word + its own I/O
         br_bytes_per_gate = params.n * params.trgsw_rows * (params.k + 1) * params.N * 8 \
@@ -537,6 +578,7 @@ def main():
             "issue": issue,
             "build_id": hip.build_id(),
         })
+    if rank == 0:
         line = {
             "metric": baseline_metric() if args.params == "128bit" else "TFHE gate bootstraps/sec (80-bit params)",
             "value": value,
@@ -562,18 +604,22 @@ def main():
                 "gates_per_step": G_total,
                 "gates_per_step_per_gpu": G_mine,
                 "parallelism": f"frontier sharded over {world} GPU(s), no data-path collective (flat DAG)",
+            },
+            "full": args.full,
+        }
+        if args.full:
+            line["config"].update({
                 "decrypt_check": decrypt_ok,
                 "word_check": words_ok,
                 "word_check_note": "sha256 digests of the timed step's output ciphertexts (rank 0's block) == the CPU oracle's committed "
                                    "digests for this workload (tests/golden/fullsize_nand_fresh_*.bin); null = not the committed workload",
-            },
-            "roofline": roofline,
-            "weak": weak,
-        }
-        if world == 1 and args.cpu_sample != 0:
-            line["cpu_baseline"] = cpu_baseline(keys, params, op_code, args.cpu_sample, data_seed=99)
-        else:
-            line["cpu_baseline"] = None
+            })
+            line["roofline"] = roofline
+            line["weak"] = weak
+            if world == 1 and args.cpu_sample != 0:
+                line["cpu_baseline"] = cpu_baseline(keys, params, op_code, args.cpu_sample, data_seed=99)
+            else:
+                line["cpu_baseline"] = None
         print(json.dumps(line), flush=True)
 
     st.destroy()
@@ -581,7 +627,7 @@ def main():
     hip.cleanup()
     if distributed:
         dist.destroy_process_group()
-    if not decrypt_ok:
+    if decrypt_ok is False:
         raise SystemExit("decrypt check failed")
     if rank == 0 and words_ok is False:
         raise SystemExit("word check failed: the timed step's ciphertexts differ from the oracle's")

@@ -163,3 +163,39 @@ def test_counters_are_tied_to_the_build(tmp_path, monkeypatch):
     assert got is not None
     got, why = bench.counters(argparse.Namespace(params="80bit", op="NAND"), 65536, "aaaa", 2)
     assert got is None
+
+
+def test_dump_outputs_writes_a_fixed_sample_exactly_and_the_same_over_ranks(tmp_path):
+    """bench.dump_outputs (--dump-outputs): every body word and a seeded sample of whole rows, u32 words exact in float64; the
+    sample is the same from run to run and the same whether one rank or several hold the batch; the files of the full-size
+    workload stay under 64 MB."""
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from iyokan_amd.params import params_128bit
+
+    total, width = bench.DUMP_ROWS + 1000, 9
+    words = np.random.default_rng(5).integers(0, 2**32, size=(total, width), dtype=np.uint64).astype(np.uint32)
+    words[0, -1] = 0xFFFFFFFF
+    out = torch.from_numpy(words.view(np.int32))
+    bench.dump_outputs(str(tmp_path / "one"), out, 0, total, 0, 1)
+    body = np.load(tmp_path / "one" / "out_body.npy")
+    rows = np.load(tmp_path / "one" / "out_ciphertexts.npy")
+    idx = np.load(tmp_path / "one" / "out_gate_index.npy")
+    assert body.dtype == rows.dtype == idx.dtype == np.float64
+    assert np.array_equal(body, words[:, -1].astype(np.float64)) and body[0] == 4294967295.0
+    assert len(idx) == bench.DUMP_ROWS and np.all(np.diff(idx) > 0)
+    assert np.array_equal(rows, words[idx.astype(np.int64)].astype(np.float64))
+    bench.dump_outputs(str(tmp_path / "again"), out, 0, total, 0, 1)
+    assert np.array_equal(np.load(tmp_path / "again" / "out_gate_index.npy"), idx)
+    world = 3
+    for r in range(world):
+        lo, cnt = bench.shard(total, world, r)
+        bench.dump_outputs(str(tmp_path / "three"), out[lo: lo + cnt], lo, total, r, world)
+    three = {name: np.concatenate([np.load(tmp_path / "three" / f"{name}_rank{r}.npy") for r in range(world)])
+             for name in ("out_body", "out_ciphertexts", "out_gate_index")}
+    assert np.array_equal(three["out_body"], body) and np.array_equal(three["out_gate_index"], idx)
+    assert np.array_equal(three["out_ciphertexts"], rows)
+    p = params_128bit()
+    assert (bench.DUMP_ROWS * (p.n + 1) + 65536 + bench.DUMP_ROWS) * 8 <= 64 * 2**20

@@ -18,7 +18,8 @@ def _run(cmd, timeout):
 
 
 def test_bench_one_gpu_through_the_launcher():
-    r = _run(["bench.py", "--gpus", "1", "--spawn", "--steps", "1", "--warmup", "0", "--gates", "4096", "--cpu-sample", "0"], 900)
+    r = _run(["bench.py", "--gpus", "1", "--spawn", "--steps", "1", "--warmup", "0", "--gates", "4096", "--cpu-sample", "0",
+              "--full"], 900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["rccl_world_size"] == 1 and len(line["per_rank_ms_per_step"]) == 1
@@ -66,3 +67,27 @@ def test_scale_all_writes_lines_and_stops_at_the_first_refusal(tmp_path):
     assert n < 2 or lines[0]["status"] == 0, lines[0]
     assert len(lines) == 3 and lines[1]["n_gpus"] == n and lines[1]["config"]["decrypt_check"] is True
     assert lines[2]["refused"] == f"bench 128bit x{n + 1}" and lines[2]["status"] == 3
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_what_they_computed(tmp_path, keys128):
+    """A plain run (no --full) times exactly --steps steps and prints the headline fields only; --dump-outputs then holds what
+    the last timed step computed: every body word, and a seeded sample of whole ciphertexts that decrypt to the gates' truth."""
+    import numpy as np
+
+    from iyokan_amd import client
+
+    gates = 16384
+    r = _run(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--gates", str(gates), "--dump-outputs", str(tmp_path)], 900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["full"] is False and line["steps"] == 2 and line["higher_is_better"] is True and line["unit"] == "gates/s"
+    assert abs(line["value"] - gates * 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]
+    assert not {"roofline", "weak", "cpu_baseline"} & set(line) and "decrypt_check" not in line["config"]
+    body = np.load(tmp_path / "out_body.npy")
+    rows = np.load(tmp_path / "out_ciphertexts.npy")
+    idx = np.load(tmp_path / "out_gate_index.npy").astype(np.int64)
+    assert body.shape == (gates,) and rows.shape == (8192, keys128.params.n + 1) and rows.dtype == np.float64
+    assert np.array_equal(rows[:, -1], body[idx])
+    bits = np.random.default_rng(1000).integers(0, 2, size=2 * gates).astype(np.uint8)   # bench.py's inputs of rank 0
+    want = 1 - (bits[:gates] & bits[gates:])
+    assert np.array_equal(client.decrypt_bits(keys128, rows.astype(np.uint32)), want[idx])

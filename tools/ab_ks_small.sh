@@ -7,7 +7,7 @@ T=${1:-r05}
 out=gpurun_out/${T}_ks_small_ab.txt
 : > $out
 one() {  # label, params, gates
-  echo "$1 $2 gates=$3 $(timeout 300 python bench.py --params $2 --gates $3 --steps 20 --warmup 3 --cpu-sample 0 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('ks_ms', round(d['roofline']['keyswitch_avg_launch_ms'],4), 'rot_ms', round(d['roofline']['avg_launch_ms'],4), 'ok', d['config']['decrypt_check'])")" >> $out
+  echo "$1 $2 gates=$3 $(timeout 300 python bench.py --full --params $2 --gates $3 --steps 20 --warmup 3 --cpu-sample 0 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('ks_ms', round(d['roofline']['keyswitch_avg_launch_ms'],4), 'rot_ms', round(d['roofline']['avg_launch_ms'],4), 'ok', d['config']['decrypt_check'])")" >> $out
 }
 for rep in 1 2; do
 for g in ${GATES:-8 16 64 256 1024 4096}; do

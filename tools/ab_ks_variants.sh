@@ -9,7 +9,7 @@ for rep in 1 2; do
 for v in $VARIANTS; do
   cp iyokan_amd/lib/variant_$v.so iyokan_amd/lib/libiyokan_hip.so
   for ps in 128bit 80bit; do
-  echo "$v $ps $(timeout 300 python bench.py --params $ps --steps 2 --warmup 1 --cpu-sample 0 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), round(d['roofline']['avg_launch_ms'],2), round(d['roofline']['keyswitch_avg_launch_ms'],2), d['config']['decrypt_check'])")" >> $out
+  echo "$v $ps $(timeout 300 python bench.py --full --params $ps --steps 2 --warmup 1 --cpu-sample 0 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), round(d['roofline']['avg_launch_ms'],2), round(d['roofline']['keyswitch_avg_launch_ms'],2), d['config']['decrypt_check'])")" >> $out
   done
 done
 done

@@ -6,7 +6,7 @@ T=${1:-r05}
 out=gpurun_out/${T}_latfft_ab.txt
 : > $out
 cp iyokan_amd/lib/libiyokan_hip.so /tmp/keep.so
-ms() { IYK_HIP_ROT_KERNEL=latfft timeout 200 python bench.py --params $1 --gates $2 --steps 10 --warmup 2 --cpu-sample 0 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['roofline']['avg_launch_ms'],4), d['config']['decrypt_check'])"; }
+ms() { IYK_HIP_ROT_KERNEL=latfft timeout 200 python bench.py --full --params $1 --gates $2 --steps 10 --warmup 2 --cpu-sample 0 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['roofline']['avg_launch_ms'],4), d['config']['decrypt_check'])"; }
 last=""
 for rep in 1 2; do
 for v in $VARIANTS; do

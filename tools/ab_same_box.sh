@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.." && export TMPDIR=/tmp
 T=${1:-r06}
 out=gpurun_out/${T}_ab.txt; mkdir -p gpurun_out; : > $out
 cp iyokan_amd/lib/libiyokan_hip.so /tmp/keep.so
-line() { timeout 300 python bench.py $1 --steps ${STEPS:-3} --warmup 1 --cpu-sample 0 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), round(d['roofline']['avg_launch_ms'],2), d['config']['word_check'], d.get('build_id') or d['config'].get('build_id'))"; }
+line() { timeout 300 python bench.py --full $1 --steps ${STEPS:-3} --warmup 1 --cpu-sample 0 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), round(d['roofline']['avg_launch_ms'],2), d['config']['word_check'], d.get('build_id') or d['config'].get('build_id'))"; }
 for rep in $(seq 1 ${REPS:-3}); do for v in $VARIANTS; do
   cp iyokan_amd/lib/variant_$v.so iyokan_amd/lib/libiyokan_hip.so
   echo "$v 128bit $(line)" >> $out

@@ -35,7 +35,7 @@ fi
 T=${2:-r06b_lat_stagger}
 out=gpurun_out/${T}_ab.txt; : > $out
 cp iyokan_amd/lib/libiyokan_hip.so /tmp/keep.so
-ms() { timeout 200 python bench.py --gates $1 --steps 6 --warmup 2 --cpu-sample 0 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['roofline']['avg_launch_ms'],4), d['config']['decrypt_check'])"; }
+ms() { timeout 200 python bench.py --full --gates $1 --steps 6 --warmup 2 --cpu-sample 0 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['roofline']['avg_launch_ms'],4), d['config']['decrypt_check'])"; }
 for rep in 1 2; do for v in ${VARIANTS:-base lx4 lc4 lxc1 lxc4}; do
   cp iyokan_amd/lib/variant_$v.so iyokan_amd/lib/libiyokan_hip.so
   for g in ${WIDTHS:-16 64 256}; do echo "$v gates=$g $(ms $g)" >> $out; done

@@ -8,7 +8,7 @@ cp iyokan_amd/lib/libiyokan_hip.so /tmp/keep.so
 for rep in 1 2; do
 for v in $VARIANTS; do
   cp iyokan_amd/lib/variant_$v.so iyokan_amd/lib/libiyokan_hip.so
-  echo "$v $(timeout 300 python bench.py --steps 2 --warmup 1 --cpu-sample 0 ${BENCH_ARGS} 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), round(d['roofline']['avg_launch_ms'],2), d['config']['decrypt_check'])")" >> $out
+  echo "$v $(timeout 300 python bench.py --full --steps 2 --warmup 1 --cpu-sample 0 ${BENCH_ARGS} 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), round(d['roofline']['avg_launch_ms'],2), d['config']['decrypt_check'])")" >> $out
 done
 done
 cp /tmp/keep.so iyokan_amd/lib/libiyokan_hip.so

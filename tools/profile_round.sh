@@ -1,7 +1,7 @@
 #!/bin/bash
 # One-shot profile of the headline workload on the GPU box (run through gpurun):
 #   bash tools/profile_round.sh <tag>
-# writes gpurun_out/<tag>_bench.json, <tag>_kernel_trace.txt, <tag>_pmc.txt, <tag>_counters.json
+# writes $OUT/<tag>_bench.json (a bench.py --full line), <tag>_kernel_trace.txt, <tag>_pmc.txt, <tag>_counters.json (OUT: default results)
 # (copy the ones to keep into profiles/; bench.py reads profiles/r06_counters.json and uses it only while its build_id —
 # the hash of the kernel sources, tools/src_hash.py — equals the loaded library's).  Counters are collected in their own
 # --pmc passes, never together with trace domains.  PARAMS=80bit profiles the 80-bit set; DECOMP=direct its opt-in
@@ -10,11 +10,12 @@ tag=${1:-r06}
 PARAMS=${PARAMS:-128bit}
 DEC=${DECOMP:+--decomp $DECOMP}
 cd "$(dirname "$0")/.." && export TMPDIR=/tmp
-mkdir -p gpurun_out
+export OUT=${OUT:-results}
+mkdir -p "$OUT"
 if [ -z "$PMC_ONLY" ]; then
-timeout 600 python bench.py --params $PARAMS $DEC 2>/dev/null | tail -1 > gpurun_out/${tag}_bench.json
+timeout 600 python bench.py --full --params $PARAMS $DEC 2>/dev/null | tail -1 > "$OUT/${tag}_bench.json"
 rm -rf /tmp/prof_kt && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_kt -o kt -- python bench.py --params $PARAMS $DEC --cpu-sample 0 > /tmp/kt.log 2>&1
-python tools/rocprof_summary.py $(find /tmp/prof_kt -name "*.db" | head -1) > gpurun_out/${tag}_kernel_trace.txt
+python tools/rocprof_summary.py $(find /tmp/prof_kt -name "*.db" | head -1) > "$OUT/${tag}_kernel_trace.txt"
 fi
 {
   echo "# rocprofv3 --pmc passes, 65536 NAND / launch (bench.py --steps 1 --warmup 0); FETCH/WRITE in KiB (gfx950: double FETCH_SIZE)"
@@ -28,7 +29,7 @@ fi
       python tools/rocprof_summary.py $db --pmc | grep -v "^#\|^ calls" | grep "blind_rotate\|keyswitch\|^ *[0-9]" | grep -v "copyBuffer\|at::native"
     else echo "# pass failed: $grp"; tail -5 /tmp/pmc.log | sed 's/^/#   /'; fi
   done
-} > gpurun_out/${tag}_pmc.txt
+} > "$OUT/${tag}_pmc.txt"
 python - "$tag" "$PARAMS" "${DECOMP:-default}" <<'PY'
 import json, re, sys
 sys.path.insert(0, ".")
@@ -38,7 +39,7 @@ import os
 levels = {"128bit": 3, "80bit": 2 if (sys.argv[3] == "direct" or os.environ.get("IYK_HIP_NTT", "fft") == "fft") else 4}[params_name]   # iyk_hip_decomposition_levels of the profiled run
 kname = None
 vals, durs = {}, []
-for line in open(f"gpurun_out/{tag}_pmc.txt"):
+for line in open(os.path.join(os.environ["OUT"], f"{tag}_pmc.txt")):
     m = re.match(r"(\w+)\s+([\d.]+)\s+n=\d+\s+(.*)", line)
     if m and "blind_rotate" in m.group(3):
         vals[m.group(1)] = float(m.group(2))
@@ -87,7 +88,7 @@ if "FETCH_SIZE" in vals:
             out["issue_ceiling"] = prev["issue_ceiling"]
     except (OSError, ValueError):
         pass
-    json.dump(out, open(f"gpurun_out/{tag}_counters.json", "w"), indent=1)
+    json.dump(out, open(os.path.join(os.environ["OUT"], f"{tag}_counters.json"), "w"), indent=1)
     print(out)
 PY
-cat gpurun_out/${tag}_kernel_trace.txt | head -12
+head -12 "$OUT/${tag}_kernel_trace.txt"

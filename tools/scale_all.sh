@@ -49,7 +49,7 @@ else
 fi
 for params in 128bit 80bit; do
   for n in $GPUS; do
-    run "bench $params x$n" python bench.py --gpus $n --params $params --steps ${STEPS:-4} --warmup 1 --cpu-sample 0
+    run "bench $params x$n" python bench.py --gpus $n --params $params --steps ${STEPS:-4} --warmup 1 --cpu-sample 0 --full
   done
 done
 for net in mux-ram cahp-system; do
