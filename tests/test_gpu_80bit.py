@@ -111,7 +111,7 @@ def test_80bit_key_switch_forms_agree(ng, keys80, oracle80, monkeypatch):
     assert np.array_equal(got["shared"][out[sample]], ref[out[sample]])
 
 
-@pytest.mark.parametrize("ng", [4097, 6000])
+@pytest.mark.parametrize("ng", [4097, 6000, 9000, 16385])
 def test_80bit_key_switch_table_kernel_agrees(ng, keys80, oracle80, monkeypatch):
     """The table key switch (round 6, batches wider than 4 096 gates) at the 80-bit set: t = 8 = four digit pairs, KSK rows of
     504 words against table rows of 512.  Same words as the wave kernel, and the oracle's on a sample."""

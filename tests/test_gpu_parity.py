@@ -437,7 +437,7 @@ def test_key_switch_kernels_agree(gpu128, keys128, oracle128, ng, monkeypatch):
     assert np.array_equal(results["1"][out[sample]], ref[out[sample]])
 
 
-@pytest.mark.parametrize("ng", [4097, 4224, 9000])
+@pytest.mark.parametrize("ng", [4097, 4224, 9000, 16385, 32769])
 def test_key_switch_table_kernel_agrees(gpu128, keys128, oracle128, ng, monkeypatch):
     """Round 6: batches wider than 4 096 gates take keyswitch_lut_kernel — digits in pairs, a table of pre-added KSK rows, the
     row selected by address (IYK_HIP_KS_KERNEL=2, the default).  It subtracts the same rows as the wave kernel (1) in another
