@@ -339,6 +339,195 @@ def balanced_levels(nl, world=1, cost=mi355x_level_cost, quanta=None):
     return out
 
 
+# ---- two lanes: a model of running critical levels on a CU subset beside deferrable bulk ---------------
+# Upstream's ready queue (/root/reference/src/iyokan.hpp:775-883) starts a gate as soon as its inputs exist and has no level
+# barrier; the level plan above has one after every level, so the narrow tail of a clock waits for the wide write-back levels in
+# front of it.  Two lanes would own DISJOINT CUs (a rotation workgroup takes a whole CU's registers and LDS: profiles/HISTORY.md):
+# lane A runs one batch per level of the plan on `a` CUs of every XCD, lane B runs bulk sets on the rest, ordered against lane A
+# only by wait edges.  This is the pricing such a plan would be chosen by; profiles/r07_two_lane_model.txt holds what it says of
+# the benchmark netlists (tools/scale_model.py --two-lane).
+
+XCDS = 8                                                       # MI355X: 8 XCDs of 32 CUs; a lane owns the same CUs on every XCD
+PENALTY_LOADED = 2.4 / 2.10                                    # narrow pass at the part's 2.4 GHz vs the clock of a busy chip
+PENALTY_WORST = 2.4 / 1.97                                     # ... vs the clock a full pass starts at (profiles/r06_level_gaps.txt)
+
+
+def lane_table(table, cus):
+    """The level-cost table of a lane that owns `cus` of the device's CUs: its round is 8 x its CUs and its pass its CUs, at the
+    full chip's milliseconds per round / pass (the device table's pass is one rotation on each of the device's CUs)."""
+    out = dict(table)
+    out["round"] = int(table["round"]) * cus // int(table["pass"])
+    out["pass"] = int(cus)
+    return out
+
+
+def _split_ms(cost, rotations):
+    """(ms in full rounds, ms in the pass kernel or the partial round) of one batch: the part a clock penalty applies to"""
+    full = rotations // cost.quanta[0]
+    base = cost(full * cost.quanta[0]) if full else 0.0
+    return base, cost(rotations) - base
+
+
+def simulate_lanes(a_ms, b_ms, after, before, penalty=1.0):
+    """Milliseconds from the first batch to the last of a two-lane plan.  a_ms[k] = (ms in full rounds, ms in the pass kernel) of
+    lane A's level k, b_ms[j] = ms of lane B's set j.  Each lane runs its batches in order; set j starts once lane A has finished
+    level after[j] (-1: at once), level k starts once every set with before[j] <= k has finished.  While lane B is busy, lane A's
+    pass kernel runs `penalty` times longer (rounds are priced at the loaded clock already)."""
+    nb = len(b_ms)
+    need = [-1] * len(a_ms)                                     # last set level k waits for
+    for j, m in enumerate(before):
+        if m < len(a_ms):
+            need[m] = max(need[m], j)
+    for k in range(1, len(need)):
+        need[k] = max(need[k], need[k - 1])
+    ka = jb = 0                                                 # next batch of each lane
+    left_a = left_b = None                                      # [round ms, pass ms] / ms still to run of the running batch
+    t = 0.0
+    while ka < len(a_ms) or jb < nb:
+        if left_a is None and ka < len(a_ms) and need[ka] < jb:
+            left_a = list(a_ms[ka])
+        if left_b is None and jb < nb and after[jb] < ka:
+            left_b = b_ms[jb]
+        if left_a is None and left_b is None:
+            raise ValueError("two-lane plan deadlocks")
+        slow = penalty if (left_b is not None and left_a is not None and left_a[0] <= 0.0) else 1.0
+        steps = []
+        if left_a is not None:
+            steps.append(left_a[0] if left_a[0] > 0.0 else left_a[1] * slow)
+        if left_b is not None:
+            steps.append(left_b)
+        dt = min(steps)
+        t += dt
+        if left_a is not None:
+            if left_a[0] > 0.0:
+                left_a[0] -= dt
+            else:
+                left_a[1] -= dt / slow
+            if left_a[0] <= 1e-12 and left_a[1] <= 1e-12:
+                left_a, ka = None, ka + 1
+        if left_b is not None:
+            left_b -= dt
+            if left_b <= 1e-12:
+                left_b, jb = None, jb + 1
+    return t
+
+
+def _rot(nl):
+    return [2 if k == "MUX" else 1 if k in BINARY else 0 for k in nl.kinds]
+
+
+def two_lane_levels(nl, levels, table, lane_cus, horizon=0, slack=1, head=0, xcds=XCDS):
+    """A two-lane plan made of the level plan `levels` (plan_levels): every gate keeps its level, on lane A or in lane B's set of
+    that level.  To lane B go, from level `head` on:
+      * deferred gates: at level >= horizon, at least `slack` levels before their latest level (ALAP in `levels`), and every
+        consumer of theirs in the clock deferred too (RAM and register write-backs: their sets end with the clock);
+      * split gates: of a level whose remaining rotations take longer on lane A's CUs than split over both lanes, the share that
+        evens the two lanes out, latest consumers first.
+    NOT / CONST follow the same rules, so a NOT of a deferred gate is deferred with it or read by lane A after a wait edge.
+    Returns (lane A's levels, lane B's sets as {"nodes", "level", "after", "before"}): a set reads lane A's outputs up to level
+    `after` and lane A's level `before` (len(levels): end of clock) is the first to read its outputs."""
+    rot = _rot(nl)
+    n, depth = nl.num_nodes, len(levels)
+    level = [-1] * n
+    for k, lv in enumerate(levels):
+        for i in lv:
+            level[i] = k
+    root = nl.roots()
+    src = lambda j: root[j] if nl.kinds[j] == "OUTPUT" else j
+    succ = [[] for _ in range(n)]
+    for lv in levels:
+        for i in lv:
+            for j in nl.ins[i]:
+                if level[src(j)] >= 0:
+                    succ[src(j)].append(i)
+    alap = [depth - 1] * n
+    on_b = [False] * n
+    for k in range(depth - 1, -1, -1):
+        for i in levels[k]:
+            alap[i] = min([alap[s] - 1 for s in succ[i]], default=depth - 1)
+            on_b[i] = k >= max(horizon, head) and alap[i] - k >= slack and all(on_b[s] for s in succ[i])
+    dev = int(table["pass"])
+    ca = make_level_cost(lane_table(table, lane_cus * xcds))
+    cb = make_level_cost(lane_table(table, dev - lane_cus * xcds))
+    for k in range(head, depth):
+        boots = [i for i in levels[k] if rot[i] and not on_b[i]]
+        total = sum(rot[i] for i in boots)
+        best, best_t = 0, ca(total)
+        for q in ca.quanta:
+            for mult in range(total // q + 2):
+                ra = min(total, mult * q)
+                if max(ca(ra), cb(total - ra)) < best_t - 1e-9:
+                    best, best_t = total - ra, max(ca(ra), cb(total - ra))
+        boots.sort(key=lambda i: (-min([level[s] for s in succ[i] if not on_b[s]], default=depth), i))
+        acc = 0
+        for i in boots:
+            if acc + rot[i] > best:
+                break
+            on_b[i] = True
+            acc += rot[i]
+    a_levels = [[i for i in lv if not on_b[i]] for lv in levels]
+    sets = []
+    for k, lv in enumerate(levels):
+        nodes = [i for i in lv if on_b[i]]
+        if nodes:
+            after = max([level[src(j)] for i in nodes for j in nl.ins[i] if level[src(j)] >= 0 and not on_b[src(j)]], default=-1)
+            before = min([level[s] for i in nodes for s in succ[i] if not on_b[s]], default=depth)
+            sets.append({"nodes": nodes, "level": k, "after": after, "before": before})
+    return a_levels, sets
+
+
+def two_lane_price(nl, a_levels, sets, table, lane_cus, penalty=PENALTY_LOADED, head=0, xcds=XCDS, extra_ms=None):
+    """Model milliseconds per clock of a two-lane plan (two_lane_levels) by the device cost table `table` rescaled to each lane
+    (lane_table): lane A's levels on lane_cus CUs per XCD (the levels before `head` on the whole device, lane B idle), lane B's
+    sets on the rest.  A pass on lane A costs `penalty` times more while lane B runs.  extra_ms(gates, cus) adds the per-batch
+    milliseconds that are not rotations (key switch, fixed cost) where the caller has them."""
+    rot = _rot(nl)
+    dev = int(table["pass"])
+    whole = with_sub_pass_shape(make_level_cost(table))
+    ca = with_sub_pass_shape(make_level_cost(lane_table(table, lane_cus * xcds)))
+    cb = make_level_cost(lane_table(table, dev - lane_cus * xcds))
+    extra = extra_ms or (lambda gates, cus: 0.0)
+
+    def gates(nodes):
+        return sum(1 for i in nodes if rot[i])
+
+    a_ms = []
+    for k, lv in enumerate(a_levels):
+        r = sum(rot[i] for i in lv)
+        base, pas = _split_ms(ca, r) if k >= head else (whole(r), 0.0)
+        a_ms.append((base + (extra(gates(lv), dev if k < head else lane_cus * xcds) if r else 0.0), pas))
+    b_ms = []
+    for s in sets:
+        r = sum(rot[i] for i in s["nodes"])
+        b_ms.append(cb(r) + (extra(gates(s["nodes"]), dev - lane_cus * xcds) if r else 0.0))
+    return simulate_lanes(a_ms, b_ms, [s["after"] for s in sets], [s["before"] for s in sets], penalty)
+
+
+def two_lane_bound(nl, table, lane_cus, penalties=(PENALTY_LOADED,), levels=None, whole_head=False, xcds=XCDS, extra_ms=None,
+                   slacks=(1, 2, 4, 8, 16, 1 << 30)):
+    """For each clock penalty in `penalties`, the cheapest two-lane plan of `levels` (default plan_levels by `table`) that
+    two_lane_levels makes over every deferral horizon and the minimum slacks `slacks` (1 << 30: nothing deferred, split levels
+    only), priced by two_lane_price: a dict of ms, horizon, slack, head, lane A's levels and lane B's sets.  whole_head=True also
+    lets the levels before the horizon run on the whole device (a third, full-device stream: an optimistic bound beyond two
+    lanes)."""
+    if levels is None:
+        levels = plan_levels(nl, 1, make_level_cost(table))
+    best = [None] * len(penalties)
+    for horizon in range(len(levels)):
+        for slack in slacks:
+            if horizon and not whole_head and slack >= len(levels):
+                continue                                        # nothing deferred: the horizon changes nothing
+            head = horizon if whole_head else 0
+            a_levels, sets = two_lane_levels(nl, levels, table, lane_cus, horizon, slack, head, xcds)
+            if not sets:
+                continue
+            for p, penalty in enumerate(penalties):
+                ms = two_lane_price(nl, a_levels, sets, table, lane_cus, penalty, head, xcds, extra_ms)
+                if best[p] is None or ms < best[p]["ms"] - 1e-9:
+                    best[p] = {"ms": ms, "horizon": horizon, "slack": slack, "head": head, "a_levels": a_levels, "sets": sets}
+    return best
+
+
 class FrontierPlan:
     """Slot assignment + per-level, per-rank gate descriptor arrays.  `balance` (default): gates with slack are placed in
     the level where the kernels' step-shaped cost is lowest (plan_levels; `cost` = make_level_cost(hip.rotation_round()) on

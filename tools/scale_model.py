@@ -165,6 +165,55 @@ def model(inputs, exch_lat_us, exch_gbps):
     return res
 
 
+TWO_LANE_CUS = (4, 8, 16)
+
+
+def two_lane(inputs, lane_cus=TWO_LANE_CUS):
+    """One-GPU bounds of configs #3 and #4 with one lane (the plan the executor runs, priced as model() prices it) and with two
+    lanes (frontier.two_lane_bound: lane A on `a` CUs per XCD, lane B on the rest) at the clock penalties of a loaded chip and of
+    the worst case, each batch charged the key switch (at the lane's share of the chip: a batch of g gates on c of 256 CUs as
+    g * 256 / c gates) and the fixed cost of a level, as model() charges a level.  "two_lane" keeps both lanes for the whole
+    clock; "whole_head" lets the levels before the deferral horizon run on the whole device (a third stream, beyond the two-lane
+    design: an optimistic bound).  Yields one dict per line of the report."""
+    from iyokan_amd import frontier as F
+    from iyokan_amd import netlist as N
+    from netlist_util import gold
+
+    import bench_netlist
+
+    rec = inputs["128bit"]
+    table = rec["cost_table"]
+    cost = F.make_level_cost(table)
+    price = F.with_sub_pass_shape(cost)
+    dev = int(table["pass"])
+    fixed = max(min(rec["step_ms"][k] - rec["rot_ms"][k] - rec["ks_ms"][k] for k in ("16", "64", "256")), 0.0)
+
+    def extra(gates, cus):
+        return interp(rec["ks_ms"], gates * dev / cus) + fixed
+
+    penalties = (("loaded", F.PENALTY_LOADED), ("worst", F.PENALTY_WORST))
+    for cfg, net in (("3_mux_ram_8_16_16", "mux-ram"), ("4_cahp_system", "cahp-system")):
+        fname, kind, _pkt = bench_netlist.NETS[net]
+        if kind == "blueprint":
+            from iyokan_amd.system import load_blueprint
+
+            nl = load_blueprint(gold(fname)).nl
+        else:
+            nl = (N.load_iyokanl1_json if kind == "l1" else N.load_yosys_json)(gold(fname))
+        levels = F.plan_levels(nl, 1, cost)
+        rot = F._rot(nl)
+        one = sum(price(r) + extra(sum(1 for i in lv if rot[i]), dev) for lv, r in zip(levels, F.level_rotations(nl, levels)) if r)
+        yield {"config": cfg, "lanes": 1, "ms_per_clock": round(one, 3)}
+        for whole_head in (False, True):
+            for a in lane_cus:
+                best = F.two_lane_bound(nl, table, a, [p for _, p in penalties], levels, whole_head, extra_ms=extra)
+                for (pname, pen), b in zip(penalties, best):
+                    yield {"config": cfg, "lanes": 2, "mode": "whole_head" if whole_head else "two_lane", "lane_cus_per_xcd": a,
+                           "penalty": pname, "penalty_factor": round(pen, 4), "ms_per_clock": round(b["ms"], 3),
+                           "vs_one_lane": round(b["ms"] / one - 1.0, 4), "horizon": b["horizon"], "slack": b["slack"],
+                           "lane_b_sets": len(b["sets"]), "lane_b_rotations": sum(rot[i] for s in b["sets"] for i in s["nodes"])}
+
+
 def check(table_path, model_path, tolerance=0.10):
     """A measured scaling table (tools/scale_all.sh's JSON lines, or the driver's SCALE_rNN.json) against the model's prediction.
     Returns a list of (label, measured, predicted, verdict) and prints it; the two numeric targets the round-5 review named are
@@ -219,7 +268,15 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06_scale_model.json"))
     ap.add_argument("--exch-lat-us", type=float, default=40.0)
     ap.add_argument("--exch-gbps", type=float, default=45.0)
+    ap.add_argument("--two-lane", action="store_true",
+                    help="print one- and two-lane bounds of configs #3 and #4 at one GPU (JSON lines; profiles/r07_two_lane_model.txt)")
     args = ap.parse_args()
+    if args.two_lane:
+        with open(args.inputs) as f:
+            inputs = json.load(f)
+        for line in two_lane(inputs):
+            print(json.dumps(line), flush=True)
+        return
     if args.check:
         rows = check(args.check, args.out)
         sys.exit(0 if rows and all(v in ("ok", "met") for *_, v in rows) else 1)
