@@ -1,0 +1,123 @@
+// dispatch.hpp — which kernel runs a batch and with what launch shape, as pure functions of their arguments.
+//
+// Host only: no HIP include, no global state, plain C++17.  iyokan_hip.hip reads the environment and the device, calls these
+// and launches what they say; emul.cpp (test support) exports them as iyk_emul_*, so the tests see every decision without a
+// GPU.  A threshold is changed HERE, and these tests object until their mirrors follow:
+//   tests/test_ks_words.py   ks_words.ks_geometry (what tests/test_gpu_keyswitch.py builds its case list from) == ks_plan
+//   tests/test_netlist.py    frontier.make_level_cost / with_sub_pass_shape == level_cost_ms / level_price_ms;
+//                            what rot_split launches costs what level_cost_ms says
+#pragma once
+
+#include <algorithm>
+
+#include "../../include/iyokan_level_cost.h"
+
+namespace iyk {
+namespace dispatch {
+
+// ---- blind rotation -------------------------------------------------------------------------------------------------------------
+
+constexpr int ROT_WAVES = 8;   // rotations per workgroup of the wave-per-rotation kernels, one workgroup per CU (kernels.hpp: BR_WAVES)
+
+// The compiled-in cost table (the only copy of these figures: iyokan_amd/frontier.py and host/iyokan_hip.hpp ask the library for
+// it through iyk_hip_level_cost_*; build_id is left empty here, the library stamps its own).  Milliseconds: MI355X, this source
+// revision (profiles/r04_sweep_*.txt); iyk_hip_calibrate() overwrites them with what the GPU at hand measures.
+// path: 2 = complex FFT (the default: the wave-per-rotation kernel's round is the shortest), 1 = FP64 field, 0 = Goldilocks
+// integers (ONE kernel, no narrow-frontier dispatch: max_passes = 0, a level costs whole rounds); set80: the 80-bit parameter set
+// (n = 500, two digit levels: shorter rounds and passes).  ADVICE r04: the defaults used to be the 128-bit FFT figures whatever ran.
+inline iyk_level_cost default_level_cost(int cus, int path, bool set80)
+{
+    iyk_level_cost c{};
+    c.round = ROT_WAVES * cus;
+    c.pass = cus;
+    c.calibrated = 0;
+    // one full round as iyk_hip_calibrate measures it (profiles/r05_model_inputs.json; inside a long launch a round is ~4 % shorter),
+    // field paths: r03_bench*.json
+    c.round_ms = path == 2 ? (set80 ? 9.4f : 14.5f) : path == 1 ? (set80 ? 20.0f : 19.7f) : (set80 ? 52.0f : 86.0f);
+    // workgroup-per-rotation kernels, one pass = one rotation per CU: the FFT one (profiles/r05_model_inputs.json), the field one
+    const float pass_fft[8] = {2.62f, 5.11f, 7.57f, 10.09f, 12.52f, 15.00f, 17.62f, 20.05f};
+    const float pass_fft80[8] = {1.86f, 3.66f, 5.31f, 6.88f, 8.42f, 10.08f, 11.76f, 13.44f};
+    const float pass_fp[8] = {3.33f, 6.96f, 10.23f, 13.52f, 16.79f, 20.1f, 23.4f, 26.7f};
+    for (int j = 0; j < 8; ++j) c.pass_ms[j] = path == 2 ? (set80 ? pass_fft80[j] : pass_fft[j]) : pass_fp[j];
+    c.max_passes = 0;
+    if (path != 0)
+        while (c.max_passes < 8 && c.pass_ms[c.max_passes] < c.round_ms) ++c.max_passes;
+    return c;
+}
+inline double level_cost_ms(const iyk_level_cost& c, long rot) { return iyk_level_cost_ms(&c, rot); }
+inline double level_price_ms(const iyk_level_cost& c, long rot) { return iyk_level_price_ms(&c, rot); }
+
+// Which rotation kernel a batch is forced onto (IYK_HIP_ROT_KERNEL = fft / w32 / lat3 / latfft); ROT_AUTO: no override.
+enum { ROT_AUTO = 0, ROT_W32 = 32, ROT_LAT3 = 3, ROT_FFT = 8, ROT_LATFFT = 9 };
+// Which pair of kernels a split names: the active path's (FFT where the key spectra are resident, else the field), or one a
+// forced kind names whatever is active.
+enum { ROT_FAMILY_ACTIVE = 0, ROT_FAMILY_FFT = 1, ROT_FAMILY_FIELD = 2 };
+struct RotSplit {
+    int family;
+    int tp_first, tp_count;           // [first, first + count) on the wave-per-rotation (throughput) kernel
+    int narrow_first, narrow_count;   // ... on the workgroup-per-rotation (narrow-frontier) kernel; either part may be empty
+};
+// Full rounds (one job per resident wave: `round` = 8 x CUs) on the wave-per-rotation kernel; a remainder of up to max_passes x
+// pass_cus rotations on the workgroup-per-rotation kernel (one CU per rotation, pass after pass); above that one more (partial)
+// round of the wave-per-rotation kernel is faster, and the whole batch is one launch of it.  max_passes comes from the GPU's
+// iyk_level_cost table, so that level_cost_ms prices exactly what this launches.  A forced kind takes the whole batch.
+inline RotSplit rot_split(int njobs, int round, int pass_cus, int max_passes, int forced)
+{
+    if (forced == ROT_FFT) return {ROT_FAMILY_FFT, 0, njobs, njobs, 0};
+    if (forced == ROT_LATFFT) return {ROT_FAMILY_FFT, 0, 0, 0, njobs};
+    if (forced == ROT_W32) return {ROT_FAMILY_FIELD, 0, njobs, njobs, 0};
+    if (forced == ROT_LAT3) return {ROT_FAMILY_FIELD, 0, 0, 0, njobs};
+    const int rem = njobs % round, full = njobs - rem;
+    if (rem > max_passes * pass_cus) return {ROT_FAMILY_ACTIVE, 0, njobs, njobs, 0};
+    return {ROT_FAMILY_ACTIVE, 0, full, full, rem};
+}
+
+// ---- key switch -----------------------------------------------------------------------------------------------------------------
+
+constexpr int KS_N = 1024;              // coefficients of a TLWE lvl1 mask: the i range the slices of a launch divide (NTT_N)
+constexpr int KS_KIND0_GATES = 16;      // gates per workgroup of keyswitch_kernel (kernels.hpp: KS_G)
+constexpr int KS_WAVE_GATES = 16;       // gates per wave of keyswitch_wave_kernel (its GW); a workgroup of the shared form holds GW, of the wide form 4 GW
+constexpr int KS_TABLE_GATES = 128;     // gates per workgroup of keyswitch_lut_kernel (kernels.hpp: KSL_WAVES * KSL_G)
+constexpr int KS_KIND_DEFAULT = 2;      // IYK_HIP_KS_KERNEL unset: the table for wide batches (round 6), the wave kernel's shared-gates form for narrow ones
+constexpr int KS_LUT_MIN_JOBS = 4096;   // kind 2 up to here: the shared-gates form of keyswitch_wave_kernel (narrow frontiers)
+constexpr int KS_SHARED_MAX_DEFAULT = 4096;   // IYK_HIP_KS_SHARED_MAX unset: largest batch on the shared-gates form (0 = never)
+constexpr int KS_SHARED_WG_DEFAULT = 512;     // IYK_HIP_KS_SHARED_WG unset: workgroups a shared-form launch is sliced up to (A/B: profiles/r05_ks_small_ab.txt)
+
+enum { KS_FORM_KIND0 = 0, KS_FORM_SHARED = 1, KS_FORM_WIDE = 2, KS_FORM_TABLE = 3 };
+struct KsPlan {
+    int form;          // KS_FORM_*: keyswitch_kernel, keyswitch_wave_kernel<SHARED = true / false>, keyswitch_lut_kernel
+    int groups;        // grid x: workgroups along the gates
+    int slices;        // grid y: parts of the i range, a power of two
+    int i_per_slice;   // KS_N / slices
+};
+// Key switch: the outputs are initialised to (0,..,0,b'), then the partial sums are subtracted with integer atomics.  The i range
+// is sliced so that at least ~2 workgroups per CU exist even for small frontiers.
+// kind (IYK_HIP_KS_KERNEL): 2 = keyswitch_lut_kernel (pre-added rows selected by address) for batches above KS_LUT_MIN_JOBS and the
+// wave kernel below, 1 = keyswitch_wave_kernel (a wave per 16 gates and whole rows), 0 = keyswitch_kernel (16 gates per
+// workgroup, 3 words per thread).  The table and the wave kernel are instantiated for the (t, nc = row words / 128) of the two
+// parameter sets only: every other shape runs keyswitch_kernel.
+inline KsPlan ks_plan(int kind, int shared_max, int shared_wg, int njobs, int T, int nc, int cus)
+{
+    auto plan = [njobs](int form, int gates, int max_slices, int min_wg) {
+        const int groups = (njobs + gates - 1) / gates;
+        int slices = 1;
+        while (slices < max_slices && groups * slices < min_wg) slices *= 2;
+        return KsPlan{form, groups, slices, KS_N / slices};
+    };
+    const bool instantiated = (T == 7 && nc == 5) || (T == 8 && nc == 4);
+    if (instantiated && kind == 2 && njobs > KS_LUT_MIN_JOBS) return plan(KS_FORM_TABLE, KS_TABLE_GATES, 8, cus);   // one workgroup per CU at a time
+    if (instantiated && kind >= 1) {
+        if (njobs > shared_max) return plan(KS_FORM_WIDE, 4 * KS_WAVE_GATES, 256, 512);
+        // narrow frontier: a workgroup's four waves share GW gates and split the i range; a quarter of the atomics (kernels.hpp).
+        // From four groups on a workgroup keeps at least 16 coefficients (64 slices), from two on at least 8 (128): cut finer, a launch
+        // of 17 .. 127 gates spends its time on the atomics of its slices — 96 gates: 89 -> 68 us, 48 gates: 70 -> 48.5 us, 32 gates:
+        // 49 -> 43 us, 64 gates: 59.5 -> 56 us (profiles/r06_plan_ab.txt; round 6's level plans make ~100-gate levels the common
+        // case of a depth-bound netlist).  Per workgroup i_per_slice >= 4: one i per wave at least.
+        const int groups = (njobs + KS_WAVE_GATES - 1) / KS_WAVE_GATES;
+        return plan(KS_FORM_SHARED, KS_WAVE_GATES, groups >= 4 ? 64 : groups >= 2 ? 128 : 256, std::max(1, shared_wg));
+    }
+    return plan(KS_FORM_KIND0, KS_KIND0_GATES, 64, 512);
+}
+
+}  // namespace dispatch
+}  // namespace iyk

@@ -16,6 +16,7 @@
 #include "blind_rotate_t16.hpp"
 #include "blind_rotate_fft.hpp"
 #include "fft256.hpp"
+#include "dispatch.hpp"
 
 using namespace iyk;
 
@@ -944,6 +945,29 @@ double iyk_emul_fft_round_error(int reset)
     return w;
 }
 
+
+// ---- the host dispatch of iyokan_hip.hip (dispatch.hpp), for the tests that pin its Python mirrors -----------------------------
+void iyk_emul_default_level_cost(int cus, int path, int set80, iyk_level_cost* out) { *out = dispatch::default_level_cost(cus, path, set80 != 0); }
+double iyk_emul_level_cost_ms(const iyk_level_cost* c, long rot) { return dispatch::level_cost_ms(*c, rot); }
+double iyk_emul_level_price_ms(const iyk_level_cost* c, long rot) { return dispatch::level_price_ms(*c, rot); }
+/* out: family (0 active path, 1 FFT, 2 field), then [first, count) of the throughput and of the narrow part */
+void iyk_emul_rot_split(int njobs, int round, int pass_cus, int max_passes, int forced, int out[5])
+{
+    const dispatch::RotSplit s = dispatch::rot_split(njobs, round, pass_cus, max_passes, forced);
+    const int v[5] = {s.family, s.tp_first, s.tp_count, s.narrow_first, s.narrow_count};
+    std::copy(v, v + 5, out);
+}
+/* ks_plan for every njobs[i], i < count: form (0 kind0, 1 shared, 2 wide, 3 table), groups, slices, i_per_slice.  A negative kind /
+ * shared_max / shared_wg stands for the unset environment variable: dispatch.hpp's default. */
+void iyk_emul_ks_plan(int kind, int shared_max, int shared_wg, const int* njobs, int count, int T, int nc, int cus, int* form,
+                      int* groups, int* slices, int* i_per_slice)
+{
+    for (int i = 0; i < count; ++i) {
+        const dispatch::KsPlan k = dispatch::ks_plan(kind < 0 ? dispatch::KS_KIND_DEFAULT : kind, shared_max < 0 ? dispatch::KS_SHARED_MAX_DEFAULT : shared_max,
+                                                     shared_wg < 0 ? dispatch::KS_SHARED_WG_DEFAULT : shared_wg, njobs[i], T, nc, cus);
+        form[i] = k.form, groups[i] = k.groups, slices[i] = k.slices, i_per_slice[i] = k.i_per_slice;
+    }
+}
 
 // NTT of every polynomial q of the torus-domain BK, stored in the device layout (bk_dev_index)
 int iyk_emul_bk_ntt(const iyk_params* p, const uint32_t* bk, uint64_t* bk_ntt)

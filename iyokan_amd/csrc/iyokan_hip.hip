@@ -4,7 +4,9 @@
 // twiddle tables) per GPU, streams with their (ring of 8) staging buffers, and turns a batch of
 // gate descriptors into a fixed launch sequence: elementwise (NOT/COPY/CONST), modswitch, blind rotation
 // (wave-per-rotation kernel for full rounds of 2048 + a workgroup-per-rotation kernel for the remainder),
-// keyswitch_init + keyswitch.  Chooses the exact-arithmetic field at init (FP64 p = 3*2^48+1097729 where its
+// keyswitch_init + keyswitch.  WHICH kernel takes which part of a batch, and with what launch shape, is decided by the pure
+// functions of dispatch.hpp (host only, visible to the CPU tests through libiyk_emul.so); this file reads the environment and
+// the device, calls them and launches what they say.  Chooses the exact-arithmetic field at init (FP64 p = 3*2^48+1097729 where its
 // bound holds, else / on request the 64-bit Goldilocks integers).  Replaces the cuFHE host API used at
 // /root/reference/src/iyokan_cufhe.cpp:530-536,721 and /root/reference/src/iyokan_cufhe.hpp:8-27,249-261,601,634.
 //
@@ -28,6 +30,7 @@
 #include <vector>
 
 #include "../../include/iyokan_hip.h"
+#include "dispatch.hpp"
 #include "kernels.hpp"
 #ifdef IYK_EXPERIMENT_KERNELS_FFT   // A/B builds only (tools/ab_*.sh): a header of tools/experiments/ in place of the product's FFT kernels
 #include IYK_EXPERIMENT_KERNELS_FFT
@@ -38,6 +41,11 @@
 #endif
 
 using namespace iyk;
+using namespace iyk::dispatch;
+
+// dispatch.hpp restates these figures of the kernel headers (it includes none of them)
+static_assert(ROT_WAVES == BR_WAVES && KS_N == NTT_N && KS_KIND0_GATES == KS_G && KS_TABLE_GATES == KSL_WAVES * KSL_G,
+              "dispatch.hpp and kernels.hpp disagree about a workgroup's share of a batch");
 
 namespace {
 
@@ -110,41 +118,13 @@ struct Device {
 #define IYK_BUILD_ID "unknown"
 #endif
 
-// THE cost table (the only copy of these figures: iyokan_amd/frontier.py and host/iyokan_hip.hpp ask for it through
-// iyk_hip_level_cost_*).  Compiled-in milliseconds: MI355X, 128-bit set, this source revision (profiles/r04_sweep_*.txt);
-// iyk_hip_calibrate() overwrites them with what the GPU at hand measures.  `fft`: the wave-per-rotation kernel of the
-// default path; the field path's round is longer.
-// path: 2 = complex FFT, 1 = FP64 field, 0 = Goldilocks integers (ONE kernel, no narrow-frontier dispatch: max_passes = 0, a level
-// costs whole rounds); set80: the 80-bit parameter set (n = 500, two digit levels: shorter rounds and passes).  ADVICE r04: the
-// defaults used to be the 128-bit FFT figures whatever ran.
-iyk_level_cost default_level_cost(int cus, int path, bool set80)
+// The compiled-in cost table of dispatch.hpp (default_level_cost: the only copy of the figures; level_cost_ms, the function that
+// prices a level from a table, is include/iyokan_level_cost.h's), stamped with the build it describes.
+iyk_level_cost built_in_level_cost(int cus, int path, bool set80)
 {
-    iyk_level_cost c{};
-    c.round = BR_WAVES * cus;
-    c.pass = cus;
-    c.calibrated = 0;
-    // one full round as iyk_hip_calibrate measures it (profiles/r05_model_inputs.json; inside a long launch a round is ~4 % shorter),
-    // field paths: r03_bench*.json
-    c.round_ms = path == 2 ? (set80 ? 9.4f : 14.5f) : path == 1 ? (set80 ? 20.0f : 19.7f) : (set80 ? 52.0f : 86.0f);
-    // workgroup-per-rotation kernels, one pass = one rotation per CU: the FFT one (profiles/r05_model_inputs.json), the field one
-    const float pass_fft[8] = {2.62f, 5.11f, 7.57f, 10.09f, 12.52f, 15.00f, 17.62f, 20.05f};
-    const float pass_fft80[8] = {1.86f, 3.66f, 5.31f, 6.88f, 8.42f, 10.08f, 11.76f, 13.44f};
-    const float pass_fp[8] = {3.33f, 6.96f, 10.23f, 13.52f, 16.79f, 20.1f, 23.4f, 26.7f};
-    for (int j = 0; j < 8; ++j) c.pass_ms[j] = path == 2 ? (set80 ? pass_fft80[j] : pass_fft[j]) : pass_fp[j];
-    c.max_passes = 0;
-    if (path != 0)
-        while (c.max_passes < 8 && c.pass_ms[c.max_passes] < c.round_ms) ++c.max_passes;
+    iyk_level_cost c = default_level_cost(cus, path, set80);
     std::snprintf(c.build_id, sizeof c.build_id, "%s", IYK_BUILD_ID IYK_BUILD_ID_SUFFIX);
     return c;
-}
-double level_cost_ms(const iyk_level_cost& c, long rot)
-{
-    if (rot <= 0) return 0.0;
-    const long full = rot / c.round, rem = rot % c.round;
-    const double t = (double)c.round_ms * (double)full;
-    if (rem == 0) return t;
-    if (rem <= (long)c.max_passes * c.pass) return t + c.pass_ms[(rem + c.pass - 1) / c.pass - 1];
-    return t + c.round_ms;
 }
 
 void coalescer_free(Device& D);
@@ -158,7 +138,7 @@ struct Global {
     bool coalesce = true;         // IYK_HIP_COALESCE=0 at init: iyk_hip_gate_host launches per gate on the caller's stream
     iyk_params p{};
     u32 ksk_stride = 0;
-    int ks_kernel = 1;    // 1: keyswitch_wave_kernel where instantiated, 0: keyswitch_kernel, 2: keyswitch_lut_kernel for wide batches (IYK_HIP_KS_KERNEL)
+    int ks_kernel = KS_KIND_DEFAULT;   // ks_plan's kind where IYK_HIP_KS_KERNEL does not name one
     bool use_fp = false;          // FP64 path (fp50.hpp) instead of Goldilocks integers
     bool use_fft = false;         // wave-per-rotation kernel on the complex-FFT path (fft512.hpp); implies use_fp for the narrow-frontier kernel
     size_t bk_fft_bytes = 0;
@@ -360,9 +340,8 @@ int launch_br_fp_lat3(iyk_hip_stream* st, int first, int njobs, const RotOut& o)
     return IYK_OK;
 }
 
-// which rotation kernel a batch is forced onto: IYK_HIP_ROT_KERNEL = fft / w32 / lat3 (A/B, tests; read per batch).
-// IYK_HIP_LATENCY_KERNEL = 0 / 3 is the older spelling of w32 / lat3.  0 = no override.
-enum { ROT_AUTO = 0, ROT_W32 = 32, ROT_LAT3 = 3, ROT_FFT = 8, ROT_LATFFT = 9 };
+// which rotation kernel a batch is forced onto: IYK_HIP_ROT_KERNEL = fft / w32 / lat3 / latfft (A/B, tests; read per batch).
+// IYK_HIP_LATENCY_KERNEL = 0 / 3 is the older spelling of w32 / lat3.  ROT_AUTO = no override.
 int forced_rot_kernel()
 {
     if (const char* k = std::getenv("IYK_HIP_ROT_KERNEL")) {
@@ -379,30 +358,34 @@ int forced_rot_kernel()
     return ROT_AUTO;
 }
 
-// Dispatch: full rounds (one job per resident wave: 8 x CUs) on the wave-per-rotation kernel; a remainder of up to
-// max_passes x CUs rotations on the workgroup-per-rotation kernel (one CU per rotation, pass after pass); above that one more
-// (partial) round of the wave-per-rotation kernel is faster.  max_passes and every millisecond a scheduler may want to know
-// come from ONE table, level_cost_of(gpu) below — compiled-in figures of this source revision until iyk_hip_calibrate()
-// replaces them by what this GPU measures.
+// The active parameter set as template arguments: f(fp::Decomp<..>{}, fft::Gadget<..>{}) for (l, Bgbit) and, at (2, 10), for the
+// field path's digit split.  THE place a parameter set is added: every launch, attribute and calibration goes through here.
+template <class F>
+int with_rot_set(const iyk_params& p, int split, F&& f)
+{
+    if (p.l == 3 && p.Bgbit == 6) return f(fp::Decomp<3, 6, 1>{}, fft::Gadget<3, 6>{});
+    if (p.l == 2 && p.Bgbit == 10)
+        return split == 1 ? f(fp::Decomp<2, 10, 1>{}, fft::Gadget<2, 10>{}) : f(fp::Decomp<2, 10, 2>{}, fft::Gadget<2, 10>{});
+    return fail(IYK_ERR_INVALID, "unsupported (l, Bgbit)");
+}
+
+// Dispatch on the FP64 paths: what dispatch.hpp's rot_split says — full rounds on the wave-per-rotation kernel, a short remainder on
+// the workgroup-per-rotation kernel.  max_passes and every millisecond a scheduler may want to know come from ONE table,
+// iyk_hip_level_cost_table(gpu) — compiled-in figures of this source revision until iyk_hip_calibrate() replaces them by what
+// this GPU measures.
 template <class DC, class GD>
 int dispatch_fp(iyk_hip_stream* st, int njobs, const RotOut& o)
 {
+    const Device& D = G.devs[st->gpu];
+    const RotSplit s = rot_split(njobs, BR_WAVES * D.cus, D.cus, __atomic_load_n(&D.max_passes, __ATOMIC_RELAXED), forced_rot_kernel());
+    if (s.family == ROT_FAMILY_FFT && !G.use_fft)
+        return fail(IYK_ERR_STATE, "IYK_HIP_ROT_KERNEL=fft / latfft needs the FFT key spectra (IYK_HIP_NTT=fft at init)");
+    const bool fft = s.family == ROT_FAMILY_FFT || (s.family == ROT_FAMILY_ACTIVE && G.use_fft);
     int rc;
-    const int forced = forced_rot_kernel();
-    if (forced == ROT_FFT || forced == ROT_LATFFT) {
-        if (!G.use_fft) return fail(IYK_ERR_STATE, "IYK_HIP_ROT_KERNEL=fft / latfft needs the FFT key spectra (IYK_HIP_NTT=fft at init)");
-        return forced == ROT_FFT ? launch_br_fft<GD>(st, 0, njobs, o) : launch_br_fft_lat<GD>(st, 0, njobs, o);
-    }
-    if (forced == ROT_LAT3) return launch_br_fp_lat3<DC>(st, 0, njobs, o);
-    if (forced == ROT_W32) return launch_br_fp<DC>(st, 0, njobs, o);
-    const int round = BR_WAVES * G.devs[st->gpu].cus;
-    const int rem = njobs % round, full = njobs - rem;
-    auto tp = [&](int first, int count) {
-        return G.use_fft ? launch_br_fft<GD>(st, first, count, o) : launch_br_fp<DC>(st, first, count, o);
-    };
-    if (rem > __atomic_load_n(&G.devs[st->gpu].max_passes, __ATOMIC_RELAXED) * G.devs[st->gpu].cus) return tp(0, njobs);
-    if (full && (rc = tp(0, full))) return rc;
-    if (rem) return G.use_fft ? launch_br_fft_lat<GD>(st, full, rem, o) : launch_br_fp_lat3<DC>(st, full, rem, o);
+    if (s.tp_count && (rc = fft ? launch_br_fft<GD>(st, s.tp_first, s.tp_count, o) : launch_br_fp<DC>(st, s.tp_first, s.tp_count, o)))
+        return rc;
+    if (s.narrow_count)
+        return fft ? launch_br_fft_lat<GD>(st, s.narrow_first, s.narrow_count, o) : launch_br_fp_lat3<DC>(st, s.narrow_first, s.narrow_count, o);
     return IYK_OK;
 }
 
@@ -415,57 +398,29 @@ int launch_blind_rotate(iyk_hip_stream* st, const u32* d_arena, const RotJob* d_
     hipLaunchKernelGGL(modswitch_kernel, dim3(njobs), dim3(256), 0, st->s, d_arena, d_jobs, st->d_abar, p.n,
                        ABAR_STRIDE);
     HIP_TRY(hipGetLastError());
-    if (G.use_fp) {
-        if (p.l == 3) return dispatch_fp<fp::Decomp<3, 6, 1>, fft::Gadget<3, 6>>(st, njobs, o);
-        if (G.split == 1) return dispatch_fp<fp::Decomp<2, 10, 1>, fft::Gadget<2, 10>>(st, njobs, o);
-        return dispatch_fp<fp::Decomp<2, 10, 2>, fft::Gadget<2, 10>>(st, njobs, o);
-    }
-    if (p.l == 3 && p.Bgbit == 6) return launch_br<3, 6>(st, njobs, o);
-    if (p.l == 2 && p.Bgbit == 10) return launch_br<2, 10>(st, njobs, o);
-    return fail(IYK_ERR_INVALID, "unsupported (l, Bgbit)");
+    return with_rot_set(p, G.split, [&](auto dc, auto gd) {
+        typedef decltype(dc) DC;
+        return G.use_fp ? dispatch_fp<DC, decltype(gd)>(st, njobs, o) : launch_br<DC::L, DC::BGBIT>(st, njobs, o);
+    });
 }
 
-// Key switch: init outputs to (0,..,0,b'), then the partial sums are subtracted with integer atomics.  The i range
-// is sliced so that at least ~2 workgroups per CU exist even for small frontiers.  Default: keyswitch_wave_kernel
-// (a wave per 16 gates and whole rows) for the (t, n) shapes it is instantiated for; IYK_HIP_KS_KERNEL=0 (or any
-// other shape) selects keyswitch_kernel (16 gates per workgroup, 3 words per thread).
+// Key switch: init outputs to (0,..,0,b'), then the partial sums are subtracted with integer atomics.  Which kernel and which grid:
+// dispatch.hpp's ks_plan.  keyswitch_wave_kernel (a wave per GW gates and whole rows), shared-gates or wide form:
 template <int T, int NC, int GW>
-int launch_keyswitch_wave(iyk_hip_stream* st, u32* d_arena, const KsJob* d_jobs, int njobs)
+int launch_keyswitch_wave(iyk_hip_stream* st, u32* d_arena, const KsJob* d_jobs, int njobs, const KsPlan& k)
 {
     const Device& D = G.devs[st->gpu];
-    // IYK_HIP_KS_SHARED_MAX: largest batch on the shared-gates form (0 = never); read per batch like IYK_HIP_KS_KERNEL (A/B, tests)
-    const char* smax = std::getenv("IYK_HIP_KS_SHARED_MAX");
-    const int shared_max = smax ? std::atoi(smax) : 4096;
-    if (njobs <= shared_max) {
-        // narrow frontier: a workgroup's four waves share GW gates and split the i range; a quarter of the atomics (kernels.hpp)
-        const char* swg = std::getenv("IYK_HIP_KS_SHARED_WG");   // workgroups a launch is sliced up to (A/B: profiles/r05_ks_small_ab.txt)
-        const int min_wg = swg ? std::max(1, std::atoi(swg)) : 512;
-        const int groups = (njobs + GW - 1) / GW;
-        // From four groups on a workgroup keeps at least 16 coefficients (64 slices), from two on at least 8 (128): cut finer, a launch
-        // of 17 .. 127 gates spends its time on the atomics of its slices — 96 gates: 89 -> 68 us, 48 gates: 70 -> 48.5 us, 32 gates:
-        // 49 -> 43 us, 64 gates: 59.5 -> 56 us (profiles/r06_plan_ab.txt; round 6's level plans make ~100-gate levels the common
-        // case of a depth-bound netlist).
-        const int max_slices = groups >= 4 ? 64 : groups >= 2 ? 128 : 256;
-        int slices = 1;
-        while (slices < max_slices && groups * slices < min_wg) slices *= 2;
-        const u32 i_per_slice = (u32)NTT_N / (u32)slices;   // per workgroup: >= 4, one i per wave at least
-        hipLaunchKernelGGL((keyswitch_wave_kernel<T, NC, GW, true>), dim3((unsigned)groups, (unsigned)slices), dim3(256),
+    const dim3 grid((unsigned)k.groups, (unsigned)k.slices);
+    if (k.form == KS_FORM_SHARED)
+        hipLaunchKernelGGL((keyswitch_wave_kernel<T, NC, GW, true>), grid, dim3(256),
                            (size_t)4 * GW * KS2_CHUNK * 2 + (size_t)GW * NC * 128 * 4, st->s, (const u32*)st->d_rot, d_jobs, njobs,
-                           (const u32*)D.ksk, d_arena, G.p.n, G.ksk_stride, i_per_slice);
-        HIP_TRY(hipGetLastError());
-        return IYK_OK;
-    }
-    const int groups = (njobs + 4 * GW - 1) / (4 * GW);
-    int slices = 1;
-    while (slices < 256 && groups * slices < 512) slices *= 2;
-    const u32 i_per_slice = (u32)NTT_N / (u32)slices;
-    hipLaunchKernelGGL((keyswitch_wave_kernel<T, NC, GW>), dim3((unsigned)groups, (unsigned)slices), dim3(256),
-                       (size_t)4 * GW * KS2_CHUNK * 2, st->s, (const u32*)st->d_rot, d_jobs, njobs, (const u32*)D.ksk,
-                       d_arena, G.p.n, G.ksk_stride, i_per_slice);
+                           (const u32*)D.ksk, d_arena, G.p.n, G.ksk_stride, (u32)k.i_per_slice);
+    else
+        hipLaunchKernelGGL((keyswitch_wave_kernel<T, NC, GW>), grid, dim3(256), (size_t)4 * GW * KS2_CHUNK * 2, st->s,
+                           (const u32*)st->d_rot, d_jobs, njobs, (const u32*)D.ksk, d_arena, G.p.n, G.ksk_stride, (u32)k.i_per_slice);
     HIP_TRY(hipGetLastError());
     return IYK_OK;
 }
-static constexpr int KS_LUT_MIN_JOBS = 4096;   // below: the shared-gates form of keyswitch_wave_kernel (narrow frontiers)
 // The table of pre-added key-switch rows on GPU `gpu` (kernels.hpp: keyswitch_lut_kernel), built from the resident KSK on first use.
 template <int T, int NC>
 int ensure_ks_lut(int gpu)
@@ -495,23 +450,41 @@ int ensure_ks_lut(int gpu)
     return IYK_OK;
 }
 template <int T, int NC>
-int launch_keyswitch_lut(iyk_hip_stream* st, u32* d_arena, const KsJob* d_jobs, int njobs)
+int launch_keyswitch_lut(iyk_hip_stream* st, u32* d_arena, const KsJob* d_jobs, int njobs, const KsPlan& k)
 {
     int rc = ensure_ks_lut<T, NC>(st->gpu);
     if (rc) return rc;
     const Device& D = G.devs[st->gpu];
-    const int groups = (njobs + KSL_WAVES * KSL_G - 1) / (KSL_WAVES * KSL_G);
-    int slices = 1;
-    while (slices < 8 && groups * slices < D.cus) slices *= 2;   // one workgroup per CU at a time
-    const u32 i_per_slice = (u32)NTT_N / (u32)slices;
     const size_t lds = KsLut<T, NC>::LDS_BYTES;
-    hipLaunchKernelGGL((keyswitch_lut_kernel<T, NC>), dim3((unsigned)groups, (unsigned)slices), dim3(64 * KSL_WAVES),
-                       lds, st->s, (const u32*)st->d_rot, d_jobs, njobs, (const u32*)D.ksk_lut, d_arena, G.p.n,
-                       i_per_slice);
+    hipLaunchKernelGGL((keyswitch_lut_kernel<T, NC>), dim3((unsigned)k.groups, (unsigned)k.slices), dim3(64 * KSL_WAVES), lds,
+                       st->s, (const u32*)st->d_rot, d_jobs, njobs, (const u32*)D.ksk_lut, d_arena, G.p.n, (u32)k.i_per_slice);
     HIP_TRY(hipGetLastError());
     return IYK_OK;
 }
-template <int T>
+// ks_plan for this batch: IYK_HIP_KS_KERNEL ("0" .. "2"), IYK_HIP_KS_SHARED_MAX and IYK_HIP_KS_SHARED_WG are read per batch (A/B, tests),
+// like IYK_HIP_ROT_KERNEL
+KsPlan ks_plan_of_batch(const Device& D, int njobs, int T)
+{
+    const char* force = std::getenv("IYK_HIP_KS_KERNEL");
+    const char* smax = std::getenv("IYK_HIP_KS_SHARED_MAX");
+    const char* swg = std::getenv("IYK_HIP_KS_SHARED_WG");
+    return ks_plan(force && (force[0] >= '0' && force[0] <= '2') ? force[0] - '0' : G.ks_kernel, smax ? std::atoi(smax) : KS_SHARED_MAX_DEFAULT,
+                   swg ? std::atoi(swg) : KS_SHARED_WG_DEFAULT, njobs, T, (int)((G.ksk_stride + 127u) / 128u), D.cus);
+}
+// The key-switch kernels of a parameter set as template arguments: f(T, NC), NC = row words / 128 of the one set the wave and the
+// table kernel are instantiated for at that t, 0 where only keyswitch_kernel<T> exists.
+template <class F>
+int with_ks_set(u32 t, F&& f)
+{
+    using std::integral_constant;
+    switch (t) {
+    case 7: return f(integral_constant<int, 7>{}, integral_constant<int, 5>{});
+    case 8: return f(integral_constant<int, 8>{}, integral_constant<int, 4>{});
+    case 5: return f(integral_constant<int, 5>{}, integral_constant<int, 0>{});
+    default: return fail(IYK_ERR_INVALID, "key-switch kernel is instantiated for t in {5, 7, 8}");
+    }
+}
+template <int T, int NC>
 int launch_keyswitch_t(iyk_hip_stream* st, u32* d_arena, const KsJob* d_jobs, int njobs)
 {
     const Device& D = G.devs[st->gpu];
@@ -519,35 +492,20 @@ int launch_keyswitch_t(iyk_hip_stream* st, u32* d_arena, const KsJob* d_jobs, in
     hipLaunchKernelGGL(keyswitch_init_kernel, dim3((unsigned)njobs), dim3(KS_THREADS), 0, st->s,
                        (const u32*)st->d_rot, d_jobs, d_arena, p.n);
     HIP_TRY(hipGetLastError());
-    const char* force = std::getenv("IYK_HIP_KS_KERNEL");  // "0" / "1" per call (A/B, tests), like IYK_HIP_LATENCY_KERNEL
-    const int kind = force && (force[0] >= '0' && force[0] <= '2') ? force[0] - '0' : G.ks_kernel;
-    const u32 nc = (G.ksk_stride + 127u) / 128u;
-    if (kind == 2 && njobs > KS_LUT_MIN_JOBS) {   // pre-added rows selected by address: wide batches (narrow ones: the shared-gates form below)
-        if (T == 7 && nc == 5) return launch_keyswitch_lut<7, 5>(st, d_arena, d_jobs, njobs);
-        if (T == 8 && nc == 4) return launch_keyswitch_lut<8, 4>(st, d_arena, d_jobs, njobs);
+    const KsPlan k = ks_plan_of_batch(D, njobs, T);
+    if constexpr (NC != 0) {   // ks_plan names these forms for (T, NC) only
+        if (k.form == KS_FORM_TABLE) return launch_keyswitch_lut<T, NC>(st, d_arena, d_jobs, njobs, k);
+        if (k.form != KS_FORM_KIND0) return launch_keyswitch_wave<T, NC, KS_WAVE_GATES>(st, d_arena, d_jobs, njobs, k);
     }
-    if (kind >= 1) {
-        if (T == 7 && nc == 5) return launch_keyswitch_wave<7, 5, 16>(st, d_arena, d_jobs, njobs);
-        if (T == 8 && nc == 4) return launch_keyswitch_wave<8, 4, 16>(st, d_arena, d_jobs, njobs);
-    }
-    const int groups = (njobs + KS_G - 1) / KS_G;
-    int slices = 1;
-    while (slices < 64 && groups * slices < 512) slices *= 2;
-    const u32 i_per_slice = (u32)NTT_N / (u32)slices;
-    hipLaunchKernelGGL(keyswitch_kernel<T>, dim3((unsigned)groups, (unsigned)slices), dim3(KS_THREADS),
-                       (size_t)KS_G * i_per_slice * 2, st->s, (const u32*)st->d_rot, d_jobs, njobs,
-                       (const u32*)D.ksk, d_arena, p.n, G.ksk_stride, i_per_slice);
+    hipLaunchKernelGGL(keyswitch_kernel<T>, dim3((unsigned)k.groups, (unsigned)k.slices), dim3(KS_THREADS),
+                       (size_t)KS_G * k.i_per_slice * 2, st->s, (const u32*)st->d_rot, d_jobs, njobs,
+                       (const u32*)D.ksk, d_arena, p.n, G.ksk_stride, (u32)k.i_per_slice);
     HIP_TRY(hipGetLastError());
     return IYK_OK;
 }
 int launch_keyswitch(iyk_hip_stream* st, u32* d_arena, const KsJob* d_jobs, int njobs)
 {
-    switch (G.p.t) {
-    case 7: return launch_keyswitch_t<7>(st, d_arena, d_jobs, njobs);
-    case 8: return launch_keyswitch_t<8>(st, d_arena, d_jobs, njobs);
-    case 5: return launch_keyswitch_t<5>(st, d_arena, d_jobs, njobs);
-    default: return fail(IYK_ERR_INVALID, "key-switch kernel is instantiated for t in {5, 7, 8}");
-    }
+    return with_ks_set(G.p.t, [&](auto t, auto nc) { return launch_keyswitch_t<decltype(t)::value, decltype(nc)::value>(st, d_arena, d_jobs, njobs); });
 }
 
 // Dynamic-LDS limits of every kernel this parameter set can launch, for the CURRENT device.  Called once per
@@ -577,19 +535,19 @@ int set_fft_attrs()
 }
 int set_kernel_attrs(const iyk_params& p, bool use_fp, int split)
 {
-    int rc;
-    if (use_fp && (rc = (p.l == 3) ? set_fft_attrs<fft::Gadget<3, 6>>() : set_fft_attrs<fft::Gadget<2, 10>>())) return rc;
-    if (use_fp) rc = (p.l == 3) ? set_fp_attrs<fp::Decomp<3, 6, 1>>() : split == 1 ? set_fp_attrs<fp::Decomp<2, 10, 1>>() : set_fp_attrs<fp::Decomp<2, 10, 2>>();
-    else rc = (p.l == 3) ? set_lds(blind_rotate_kernel<3, 6>, BR_LDS_BYTES) : set_lds(blind_rotate_kernel<2, 10>, BR_LDS_BYTES);
+    int rc = with_rot_set(p, split, [&](auto dc, auto gd) {
+        typedef decltype(dc) DC;
+        if (!use_fp) return set_lds(blind_rotate_kernel<DC::L, DC::BGBIT>, BR_LDS_BYTES);
+        if (int e = set_fft_attrs<decltype(gd)>()) return e;
+        return set_fp_attrs<DC>();
+    });
     if (rc) return rc;
-    const size_t ks_lds = (size_t)KS_G * NTT_N * 2;
-    if (p.t == 7 && (rc = set_lds(keyswitch_lut_kernel<7, 5>, KsLut<7, 5>::LDS_BYTES))) return rc;
-    if (p.t == 8 && (rc = set_lds(keyswitch_lut_kernel<8, 4>, KsLut<8, 4>::LDS_BYTES))) return rc;
-    switch (p.t) {
-    case 7: return set_lds(keyswitch_kernel<7>, ks_lds);
-    case 8: return set_lds(keyswitch_kernel<8>, ks_lds);
-    default: return set_lds(keyswitch_kernel<5>, ks_lds);
-    }
+    return with_ks_set(p.t, [&](auto t, auto nc) {
+        constexpr int T = decltype(t)::value, NC = decltype(nc)::value;
+        if constexpr (NC != 0)
+            if (int e = set_lds(keyswitch_lut_kernel<T, NC>, KsLut<T, NC>::LDS_BYTES)) return e;
+        return set_lds(keyswitch_kernel<T>, (size_t)KS_G * NTT_N * 2);
+    });
 }
 
 // linear-step coefficients of TFHEpp HomGate (SURVEY.md §8 a-ext)
@@ -777,7 +735,7 @@ int init_devices(std::vector<Device>& devs, const int* device_ids, int avail, co
                                &D.fftc->c, polys);
             INIT_TRY(hipGetLastError());
         }
-        D.cost = default_level_cost(D.cus, use_fft ? 2 : use_fp ? 1 : 0, p.n < 600);
+        D.cost = built_in_level_cost(D.cus, use_fft ? 2 : use_fp ? 1 : 0, p.n < 600);
         __atomic_store_n(&D.max_passes, D.cost.max_passes, __ATOMIC_RELAXED);
         init_note("enqueue", (int)g, now_ms() - t0);
     }
@@ -961,8 +919,8 @@ int iyk_hip_rotation_round(int gpu_index)
 int iyk_hip_level_cost_defaults(iyk_level_cost* out)
 {
     if (!out) return fail(IYK_ERR_INVALID, "null out");
-    if (G.init.load()) *out = default_level_cost(256, G.use_fft ? 2 : G.use_fp ? 1 : 0, G.p.n < 600);
-    else *out = default_level_cost(256, 2, false);
+    if (G.init.load()) *out = built_in_level_cost(256, G.use_fft ? 2 : G.use_fp ? 1 : 0, G.p.n < 600);
+    else *out = built_in_level_cost(256, 2, false);
     return IYK_OK;
 }
 
@@ -979,7 +937,7 @@ int iyk_hip_level_cost_table(int gpu_index, iyk_level_cost* out)
 
 double iyk_hip_level_cost_ms(int gpu_index, int rotations)
 {
-    if (!G.init.load() || gpu_index < 0 || gpu_index >= (int)G.devs.size()) return level_cost_ms(default_level_cost(256, 2, false), rotations);
+    if (!G.init.load() || gpu_index < 0 || gpu_index >= (int)G.devs.size()) return level_cost_ms(built_in_level_cost(256, 2, false), rotations);
     std::lock_guard<std::mutex> lock(G.mu);
     return level_cost_ms(G.devs[gpu_index].cost, rotations);
 }
@@ -1073,14 +1031,14 @@ static int calibrate_one(int gpu_index)
         return IYK_OK;
     };
     auto tp = [&](int count) {
-        if (G.p.l == 3) return G.use_fft ? launch_br_fft<fft::Gadget<3, 6>>(st, 0, count, o) : launch_br_fp<fp::Decomp<3, 6, 1>>(st, 0, count, o);
-        if (G.use_fft) return launch_br_fft<fft::Gadget<2, 10>>(st, 0, count, o);
-        return G.split == 1 ? launch_br_fp<fp::Decomp<2, 10, 1>>(st, 0, count, o) : launch_br_fp<fp::Decomp<2, 10, 2>>(st, 0, count, o);
+        return with_rot_set(G.p, G.split, [&](auto dc, auto gd) {
+            return G.use_fft ? launch_br_fft<decltype(gd)>(st, 0, count, o) : launch_br_fp<decltype(dc)>(st, 0, count, o);
+        });
     };
     auto lat = [&](int count) {
-        if (G.use_fft) return G.p.l == 3 ? launch_br_fft_lat<fft::Gadget<3, 6>>(st, 0, count, o) : launch_br_fft_lat<fft::Gadget<2, 10>>(st, 0, count, o);
-        if (G.p.l == 3) return launch_br_fp_lat3<fp::Decomp<3, 6, 1>>(st, 0, count, o);
-        return G.split == 1 ? launch_br_fp_lat3<fp::Decomp<2, 10, 1>>(st, 0, count, o) : launch_br_fp_lat3<fp::Decomp<2, 10, 2>>(st, 0, count, o);
+        return with_rot_set(G.p, G.split, [&](auto dc, auto gd) {
+            return G.use_fft ? launch_br_fft_lat<decltype(gd)>(st, 0, count, o) : launch_br_fp_lat3<decltype(dc)>(st, 0, count, o);
+        });
     };
     float ms = 0.f;
     if ((rc = timed([&] { return tp(c.round); }, &ms))) return done(rc);   // warm-up (clocks, caches, code upload)
@@ -1229,7 +1187,7 @@ int iyk_hip_init(int ngpu, const int* device_ids, const iyk_params* params, cons
     if (const char* co = std::getenv("IYK_HIP_COALESCE")) G.coalesce = co[0] != '0';
     else G.coalesce = true;
     const char* dbg = std::getenv("IYK_HIP_DEBUG");
-    G.ks_kernel = 2;   // wide batches: pre-added rows selected by address (round 6); narrow ones: the wave kernel's shared-gates form
+    G.ks_kernel = KS_KIND_DEFAULT;
     G.debug = dbg && dbg[0] == '1';
     G.p = p;
     G.use_fp = use_fp;

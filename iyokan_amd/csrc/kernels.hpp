@@ -1151,9 +1151,7 @@ __host__ __device__ constexpr int ksl_stages(int T) { return (T + 1) / 2; }
 __host__ __device__ constexpr int ksl_rows_per_i(int T) { return 16 * (T / 2) + 4 * (T % 2); }
 __host__ __device__ constexpr int ksl_stage_rows(int T, int s) { return 2 * s + 1 < T ? 16 : 4; }
 static constexpr int KSL_WAVES = 8, KSL_G = 16;
-#ifndef KSL_GG
-#define KSL_GG 4   // gates whose rows are in flight together
-#endif
+static constexpr int KSL_GG = 4;   // gates whose rows are in flight together
 
 template <int T>
 __global__ __launch_bounds__(256) void ks_lut_build_kernel(const u32* __restrict__ ksk, u32* __restrict__ lut, u32 stride,

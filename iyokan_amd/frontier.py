@@ -26,7 +26,8 @@ from .params import OPS
 
 
 def make_level_cost(table=None):
-    """Milliseconds one rank spends on a level of r blind rotations, as the dispatch of csrc/iyokan_hip.hip prices it: full
+    """Milliseconds one rank spends on a level of r blind rotations, as the library's dispatch prices it (include/
+    iyokan_level_cost.h: iyk_level_cost_ms, restated here for the planner's inner loop; tests/test_netlist.py holds the two equal): full
     rounds on the wave-per-rotation kernel, a remainder of up to max_passes passes of the workgroup-per-rotation kernel (one
     rotation per CU and pass), a larger remainder as one more full round.  The FIGURES are the library's (include/
     iyokan_hip.h: iyk_level_cost; this module holds none): `table` = hip.level_cost_table(gpu) / hip.calibrate(gpu) on a

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../../include/iyokan_hip.h"
+#include "../../include/iyokan_level_cost.h"
 #include "engine.hpp"
 
 namespace iyk {
@@ -497,25 +498,11 @@ inline iyk_level_cost levelCostTable()
     }
     return c;
 }
-// iyk_hip_gate_batch's dispatch as a pure function of a table (csrc/iyokan_hip.hip: level_cost_ms)
-inline double levelCostMs(const iyk_level_cost& c, long rot)
-{
-    if (rot <= 0) return 0.0;
-    const long full = rot / c.round, rem = rot % c.round;
-    const double t = (double)c.round_ms * (double)full;
-    if (rem == 0) return t;
-    if (rem <= (long)c.max_passes * c.pass) return t + c.pass_ms[(rem + c.pass - 1) / c.pass - 1];
-    return t + c.round_ms;
-}
-// What plans are COMPARED by (round 6; iyokan_amd/frontier.py: with_sub_pass_shape): levelCostMs with the first pass of the
-// narrow-frontier kernel priced by how full it is — up to a quarter of the CUs busy it runs at the part's full clock, with all of
-// them busy into the power limit (2.466 / 2.497 / 2.554 / 2.635 ms at 64 / 128 / 192 / 256 rotations, profiles/r06_plan_ab.txt).
-inline double levelPriceMs(const iyk_level_cost& c, long rot)
-{
-    static constexpr double SUB_PASS_SHAPE[4] = {0.936, 0.947, 0.969, 1.0};
-    if (rot > 0 && rot <= c.pass) return levelCostMs(c, c.pass) * SUB_PASS_SHAPE[std::min(3L, (4 * rot - 1) / c.pass)];
-    return levelCostMs(c, rot);
-}
+// iyk_hip_gate_batch's dispatch as a pure function of a table, and what plans are COMPARED by (round 6; iyokan_amd/frontier.py:
+// with_sub_pass_shape): the first pass of the narrow-frontier kernel priced by how full it is.  Both live in
+// include/iyokan_level_cost.h, shared with the library's own dispatch.
+inline double levelCostMs(const iyk_level_cost& c, long rot) { return iyk_level_cost_ms(&c, rot); }
+inline double levelPriceMs(const iyk_level_cost& c, long rot) { return iyk_level_price_ms(&c, rot); }
 inline long rotationRound() { return (long)levelCostTable().round; }
 inline long rotationPass() { return (long)levelCostTable().pass; }
 inline double levelCostMs(long rot) { return levelCostMs(levelCostTable(), rot); }

@@ -18,9 +18,9 @@ The b word (t1[N]) cycles through 0, 0xFFFFFFFF and uniform values.
 import numpy as np
 
 MASK32 = (1 << 32) - 1
-TABLE_MIN_JOBS = 4096     # iyokan_hip.hip: KS_LUT_MIN_JOBS
-SHARED_MAX_DEFAULT = 4096  # iyokan_hip.hip: launch_keyswitch_wave, IYK_HIP_KS_SHARED_MAX unset
-KSL_GROUP = 128           # kernels.hpp: KSL_WAVES * KSL_G gates per workgroup of keyswitch_lut_kernel
+TABLE_MIN_JOBS = 4096     # csrc/dispatch.hpp: KS_LUT_MIN_JOBS
+SHARED_MAX_DEFAULT = 4096  # csrc/dispatch.hpp: KS_SHARED_MAX_DEFAULT (IYK_HIP_KS_SHARED_MAX unset)
+KSL_GROUP = 128           # csrc/dispatch.hpp: KS_TABLE_GATES (kernels.hpp: KSL_WAVES * KSL_G gates per workgroup of keyswitch_lut_kernel)
 
 
 def prec_of(t):
@@ -179,14 +179,14 @@ def chosen_images(p, seed=0):
 # ---- launch geometry ----------------------------------------------------------------------------------------------------------
 
 def ks_geometry(kind, shared_max, n, t, cus, shared_wg=None):
-    """(form, groups, slices) of the key-switch launch of n jobs at t digits, as iyokan_amd/csrc/iyokan_hip.hip decides it:
-      launch_keyswitch_t (line 515): IYK_HIP_KS_KERNEL = kind ('0' .. '2'; anything else: the default 2); kind 2 and n > 4096 ->
-        launch_keyswitch_lut; kind >= 1 -> launch_keyswitch_wave; else keyswitch_kernel: ceil(n / 16) groups, slices doubled
-        while < 64 and groups * slices < 512;
-      launch_keyswitch_wave (line 433): n <= IYK_HIP_KS_SHARED_MAX (default 4096) -> the shared form: ceil(n / 16) groups,
-        slices doubled while < max_slices (256 / 128 / 64 from 1 / 2 / 4 groups on) and groups * slices < IYK_HIP_KS_SHARED_WG
-        (default 512); else the wide form: ceil(n / 64) groups, slices doubled while < 256 and groups * slices < 512;
-      launch_keyswitch_lut (line 498): ceil(n / 128) groups, slices doubled while < 8 and groups * slices < cus.
+    """(form, groups, slices) of the key-switch launch of n jobs at t digits, as ks_plan of iyokan_amd/csrc/dispatch.hpp decides it
+    (tests/test_ks_words.py holds this mirror to ks_plan itself, case by case):
+      IYK_HIP_KS_KERNEL = kind ('0' .. '2'; anything else: KS_KIND_DEFAULT = 2); kind 2 and n > KS_LUT_MIN_JOBS = 4096 -> the table form:
+        ceil(n / 128) groups, slices doubled while < 8 and groups * slices < cus; kind >= 1 -> the wave kernel; else
+        keyswitch_kernel: ceil(n / 16) groups, slices doubled while < 64 and groups * slices < 512;
+      the wave kernel: n <= IYK_HIP_KS_SHARED_MAX (KS_SHARED_MAX_DEFAULT = 4096) -> the shared form: ceil(n / 16) groups, slices
+        doubled while < max_slices (256 / 128 / 64 from 1 / 2 / 4 groups on) and groups * slices < IYK_HIP_KS_SHARED_WG
+        (KS_SHARED_WG_DEFAULT = 512); else the wide form: ceil(n / 64) groups, slices doubled while < 256 and groups * slices < 512.
     Forms: 'table' (keyswitch_lut_kernel), 'shared' / 'wide' (keyswitch_wave_kernel, SHARED = true / false), 'kind0'
     (keyswitch_kernel).  The table and the wave kernel exist for t = 7 (128-bit set) and t = 8 (80-bit set) only."""
     kind = int(kind) if kind is not None and str(kind)[:1] in ("0", "1", "2") else 2

@@ -25,6 +25,16 @@ def test_product_fft_header_has_no_knobs():
     assert os.path.exists(os.path.join(ROOT, "tools", "experiments", "kernels_fft_r05_knobs.hpp"))
 
 
+def test_product_kernel_header_has_no_knobs():
+    """kernels.hpp: no `#ifndef X / #define X value` build knob (KSL_GG was the last one, now a constexpr), and no conditional other
+    than the allowed exception — the IYK_LAT3_TRACE blocks, phase stamps compiled in by tools/ubench/lat3_trace.hip only."""
+    text = open(os.path.join(ROOT, "iyokan_amd", "csrc", "kernels.hpp")).read()
+    assert not re.search(r"^\s*#\s*ifndef\s+(\w+)\s*\n\s*#\s*define\s+\1\b", text, flags=re.M)
+    conditionals = re.findall(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b.*$", text, flags=re.M)
+    assert conditionals and all(re.fullmatch(r"\s*#\s*ifdef\s+IYK_LAT3_TRACE\s*", c) for c in conditionals), conditionals
+    assert re.search(r"static constexpr int KSL_GG = \d+;", text)
+
+
 def test_build_id_covers_flags():
     import src_hash
 

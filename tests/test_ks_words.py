@@ -2,6 +2,8 @@
 row of the pair table, the TRLWE images extract to the intended TLWE1 words, the table restatement equals the oracle on the edge
 families, and the case list reaches every launch shape of the three key-switch kernels."""
 import ctypes
+import itertools
+import os
 
 import numpy as np
 import pytest
@@ -120,6 +122,32 @@ def test_case_list_reaches_every_launch_shape(t):
     assert K.ks_geometry("1", None, 100, 5, 256)[0] == "kind0"       # no wave or table kernel at t = 5
     # more CUs: the table keeps 8 slices longer; the boundary sizes follow
     assert K.reached_shapes(K.cases(304, t), t, 304) >= {s for s in K.expected_shapes() if s[0] == "table"}
+
+
+def test_geometry_mirror_equals_the_library_dispatch():
+    """ks_words.ks_geometry (what the GPU test's case list and its claim "every (form, slices) shape is reached" rest on) is ks_plan
+    of csrc/dispatch.hpp — the function iyokan_hip.hip launches by, exported by the test-support library — for every batch size
+    1 .. 40 000 at the default IYK_HIP_KS_SHARED_MAX / _WG, and on 1 .. 5 000 (both of their thresholds lie below) at the others."""
+    em = ctypes.CDLL(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "iyokan_amd", "lib", "libiyk_emul.so"))
+    ip = ctypes.POINTER(ctypes.c_int)
+    em.iyk_emul_ks_plan.argtypes = [ctypes.c_int] * 3 + [ip, ctypes.c_int] + [ctypes.c_int] * 3 + [ip] * 4
+    em.iyk_emul_ks_plan.restype = None
+    forms = ["kind0", "shared", "wide", "table"]
+    unset = lambda v: -1 if v is None else int(v)
+    checked = 0
+    for kind, smax, swg, t, cus in itertools.product(("0", "1", "2", None), (None, "0", "1000"), (None, "64"), (5, 7, 8), (64, 256, 304)):
+        ns = np.arange(1, (40000 if smax is None and swg is None else 5000) + 1, dtype=np.intc)
+        out = [np.zeros(len(ns), dtype=np.intc) for _ in range(4)]
+        em.iyk_emul_ks_plan(unset(kind), unset(smax), unset(swg), ns.ctypes.data_as(ip), len(ns), t, {7: 5, 8: 4}.get(t, 5), cus,
+                            *[o.ctypes.data_as(ip) for o in out])
+        form, groups, slices, ips = (o.tolist() for o in out)
+        for k, n in enumerate(ns.tolist()):
+            got = (forms[form[k]], groups[k], slices[k])
+            if got != K.ks_geometry(kind, smax, n, t, cus, swg):
+                raise AssertionError((kind, smax, swg, t, cus, n, got, K.ks_geometry(kind, smax, n, t, cus, swg)))
+        assert all(i * s == 1024 for i, s in zip(ips, slices))
+        checked += len(ns)
+    assert checked == 4 * 3 * 3 * (40000 + 5 * 5000)
 
 
 def test_job_layout_places_the_chosen_cells():

@@ -292,3 +292,96 @@ def test_planner_follows_the_library_cost_table():
     assert total(plan, cost) <= total(default_plan, cost) + 1e-9       # ... better than the plan made for the default table
     rots = F.level_rotations(nl, plan, 1)
     assert sum(1 for r in rots if r and r % 96 == 0) > sum(1 for r in F.level_rotations(nl, default_plan, 1) if r and r % 96 == 0)
+
+
+def _dispatch_lib():
+    """csrc/dispatch.hpp — the decisions iyokan_hip.hip launches by — as the test-support library exports it."""
+    import ctypes
+
+    from iyokan_amd import hip
+
+    em = ctypes.CDLL(os.path.join(os.path.dirname(hip.LIB_PATH), "libiyk_emul.so"))
+    cp = ctypes.POINTER(hip.IykLevelCost)
+    em.iyk_emul_default_level_cost.argtypes = [ctypes.c_int] * 3 + [cp]
+    em.iyk_emul_default_level_cost.restype = None
+    for fn in (em.iyk_emul_level_cost_ms, em.iyk_emul_level_price_ms):
+        fn.argtypes = [cp, ctypes.c_long]
+        fn.restype = ctypes.c_double
+    em.iyk_emul_rot_split.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)]
+    em.iyk_emul_rot_split.restype = None
+    return em
+
+
+def _cost_struct(table):
+    from iyokan_amd import hip
+
+    c = hip.IykLevelCost(table["round"], table["pass"], table["max_passes"], int(table["calibrated"]), table["round_ms"])
+    c.pass_ms[:] = table["pass_ms"]
+    return c
+
+
+def _cost_tables(em):
+    """The compiled-in table of the loaded library, the 80-bit and field-path defaults, and the odd table of the test above."""
+    import ctypes
+
+    from iyokan_amd import hip
+
+    t = hip.level_cost_defaults()
+    out = [t]
+    for cus, path, set80 in ((256, 2, 0), (256, 2, 1), (256, 1, 0), (256, 1, 1), (304, 2, 0), (64, 0, 0)):
+        c = hip.IykLevelCost()
+        em.iyk_emul_default_level_cost(cus, path, set80, ctypes.byref(c))
+        out.append(c.as_dict())
+    assert dict(out[1], build_id=t["build_id"]) == t and out[1]["build_id"] == ""   # the library's defaults are these, stamped with its build
+    odd = dict(t, round=768, max_passes=2, round_ms=9.0, pass_ms=[4.0, 7.5, 11.0, 14.5, 18.0, 21.5, 25.0, 28.5])
+    odd["pass"] = 96
+    return out + [odd]
+
+
+def test_python_level_cost_equals_the_library_one():
+    """frontier.make_level_cost / with_sub_pass_shape restate include/iyokan_level_cost.h (what the library's dispatch and the C++ host
+    planner call) in Python for the planner's inner loop: the same doubles, exactly, for every rotation count up to three rounds."""
+    import ctypes
+
+    from iyokan_amd import frontier as F
+
+    em = _dispatch_lib()
+    for t in _cost_tables(em):
+        c = _cost_struct(t)
+        cost = F.make_level_cost(t)
+        price = F.with_sub_pass_shape(cost)
+        for r in range(0, 3 * t["round"] + 2):
+            assert cost(r) == em.iyk_emul_level_cost_ms(ctypes.byref(c), r), (t, r)
+            assert price(r) == em.iyk_emul_level_price_ms(ctypes.byref(c), r), (t, r)
+
+
+def test_rotation_split_costs_what_the_table_says():
+    """What the planners rely on: rot_split (csrc/dispatch.hpp, what iyk_hip_gate_batch launches) sends whole rounds to the throughput
+    kernel and at most max_passes passes to the narrow one, the two parts tile the batch, and what it chose, priced from the table
+    (rounds x round_ms + pass_ms[passes - 1]), is level_cost_ms of the batch."""
+    import ctypes
+
+    em = _dispatch_lib()
+    out = (ctypes.c_int * 5)()
+    t0 = _cost_tables(em)[0]
+    for cus in (64, 256):
+        rnd = 8 * cus
+        for maxp in range(0, 9):
+            t = dict(t0, round=rnd, max_passes=maxp)
+            t["pass"] = cus
+            c = _cost_struct(t)
+            for n in range(1, 3 * rnd + 2):
+                em.iyk_emul_rot_split(n, rnd, cus, maxp, 0, out)
+                family, tp0, tpn, na0, nan = list(out)
+                assert family == 0 and tpn >= 0 and nan >= 0 and tpn + nan == n
+                assert (tp0 == 0 and na0 == tpn) or tpn == 0 or nan == 0          # disjoint, covering [0, n)
+                if nan:
+                    assert tpn % rnd == 0 and nan <= maxp * cus and na0 == tpn
+                else:
+                    assert tp0 == 0
+                ms = float(c.round_ms) * (-(-tpn // rnd)) + (float(c.pass_ms[-(-nan // cus) - 1]) if nan else 0.0)
+                assert ms == em.iyk_emul_level_cost_ms(ctypes.byref(c), n), (cus, maxp, n)
+    # a forced kind takes the whole batch: w32 / lat3 on the field kernels, fft / latfft on the FFT ones
+    for forced, want in ((32, [2, 0, 1000, 1000, 0]), (3, [2, 0, 0, 0, 1000]), (8, [1, 0, 1000, 1000, 0]), (9, [1, 0, 0, 0, 1000])):
+        em.iyk_emul_rot_split(1000, 2048, 256, 5, forced, out)
+        assert list(out) == want
