@@ -255,6 +255,41 @@ int iyk_hip_sample_extract_keyswitch_batch(iyk_hip_stream* st, const uint32_t* d
                                            uint64_t count, const int32_t* trlwe_index, const int32_t* out_slot,
                                            uint32_t* d_arena, uint64_t arena_slots);
 
+/* Sample-extract at coefficient index coeff_index[g] in [0, N) + identity key switch: the same with TFHEpp's
+ * SampleExtractIndex<Lvl1>(res, trlwe, index) in front (TaskTFHEppSEI, /root/reference/src/iyokan_tfhepp.hpp:340-352: one output
+ * bit of a ROM / RAM word per task).  a'[j] = a[h - j] for j <= h, -a[N + h - j] for j > h, b' = b[h]; index 0 gives the words of
+ * iyk_hip_sample_extract_keyswitch_batch. */
+int iyk_hip_sample_extract_index_keyswitch_batch(iyk_hip_stream* st, const uint32_t* d_trlwe, uint64_t trlwe_slots,
+                                                 uint64_t count, const int32_t* trlwe_index, const int32_t* coeff_index,
+                                                 const int32_t* out_slot, uint32_t* d_arena, uint64_t arena_slots);
+
+/* ---- CMUX memories (ROM / RAM): the CMUX tree over TRLWE rows on the GPU --------------------------------------------------
+ * Available on the default (FFT) path; after IYK_HIP_NTT=fp / goldilocks at init the trgsw_* and cmux calls return IYK_ERR_STATE.
+ *
+ * TRGSW lvl1 selector store in spectrum form: one slot = one step of the bootstrapping key's spectra,
+ * (k+1) l * (k+1) * 2 * 512 * 16 bytes (192 KiB at the 128-bit set, 128 KiB at the 80-bit set).  Holds what TFHEpp keeps as
+ * TRGSWFFT<lvl1param> (the TRGSWLvl1FFT inputs of TaskTFHEppROMUX / RAMUX, /root/reference/src/iyokan_tfhepp.hpp:238-240). */
+int iyk_hip_trgsw_alloc(int gpu_index, uint64_t count, void** d_trgsw_out);
+int iyk_hip_trgsw_free(int gpu_index, void* d_trgsw);
+/* host rows are TFHEpp::TRGSW<lvl1param>: u32 [(k+1) l][k+1][N], torus domain (row c l + j = a TRLWE of zero plus
+ * bit * 2^(32 - (j+1) Bgbit) at coefficient 0 of polynomial c).  Replaces TFHEpp::ApplyFFT2trgsw<lvl1param>.  The rows are copied
+ * before return; the transform runs on st, ordered with the batches before and after it. */
+int iyk_hip_trgsw_upload(iyk_hip_stream* st, void* d_trgsw, uint64_t trgsw_slots, uint64_t first, uint64_t count,
+                         const uint32_t* host_trgsw);
+/* `count` independent CMUXes on rows of a TRLWE store (iyk_hip_trlwe_*), asynchronous on st.  Job g:
+ *     in1[g] >= 0:  T[out] = T[in0] + S[sel] [.] (T[in1] - T[in0])
+ *                   replaces TFHEpp::CMUXFFT<Lvl1>(res, cs, c1, c0), res = c0 + cs [.] (c1 - c0), with c0 = T[in0], c1 = T[in1]:
+ *                   a selector of 1 selects in1 (/root/reference/src/iyokan_tfhepp.hpp:267, 426-443, 627)
+ *     in1[g] <  0:  T[out] = T[in0] + S[sel] [.] ((X^rot - 1) T[in0]),  rot[g] in [0, 2N)
+ *                   replaces trgswfftExternalProduct after PolynomialMulByXaiMinusOne (/root/reference/src/iyokan_tfhepp.hpp:282-291)
+ * [.] is the external product with the blind rotation's gadget, computed exactly mod 2^32 (TFHEpp's FFT product is not exact:
+ * results agree after decryption, not word for word).  The five arrays are host arrays, copied before return.  A job may write
+ * over its own inputs; no out[g] may be the in0 / in1 / out of ANOTHER job of the batch — checked on every call, as is every
+ * index against the sizes stated: a violation is IYK_ERR_INVALID and nothing is launched. */
+int iyk_hip_cmux_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe,
+                       uint64_t trlwe_slots, uint64_t count, const int32_t* sel, const int32_t* in0,
+                       const int32_t* in1, const int32_t* rot, const int32_t* out);
+
 /* Kernel-only time of the most recent iyk_hip_gate_batch on this stream, from HIP events
  * recorded on the stream around the blind-rotate and key-switch launches (milliseconds).
  * Blocks until those events have completed. */

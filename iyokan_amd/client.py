@@ -98,6 +98,20 @@ def trlwe_phases(keys: KeySet, ct) -> np.ndarray:
     return out
 
 
+def encrypt_trgsw(keys: KeySet, bits, seed=None) -> np.ndarray:
+    """trgswSymEncrypt<Lvl1> of bits -> u32 [count][(k+1) l][k+1][N], torus domain (the host form of TFHEpp::TRGSW<lvl1param>): row
+    c l + j is a fresh encrypt_trlwe of zero plus bit * 2^(32 - (j+1) Bgbit) at coefficient 0 of polynomial c — the layout of one
+    step of the bootstrapping key (csrc/client.cpp)."""
+    bits = np.asarray(bits, dtype=np.uint8).ravel()
+    p = keys.params
+    rows = (p.k + 1) * p.l
+    out = encrypt_trlwe(keys, np.zeros((bits.size * rows, p.N), dtype=np.uint32), seed).reshape(bits.size, rows, p.k + 1, p.N)
+    for c in range(p.k + 1):
+        for j in range(p.l):
+            out[:, c * p.l + j, c, 0] += bits.astype(np.uint32) << np.uint32(32 - (j + 1) * p.Bgbit)
+    return out
+
+
 def encrypt_ram_trlwe(keys: KeySet, bits, seed=None) -> np.ndarray:
     """encryptRAM (/root/reference/src/packet.hpp:104-118): one TRLWE per bit, +-mu in coefficient 0."""
     bits = np.asarray(bits, dtype=np.uint8).ravel()

@@ -186,4 +186,12 @@ IYK_HD void br_init_acc(int h, int t, u32 bbar, u32 mu, u32* acc_h)
     }
 }
 
+// word j <= N of the TLWE lvl1 that TFHEpp's SampleExtractIndex(., h) takes from a TRLWE (a(X) then b(X)), h < N:
+// a'[j] = a[h - j] for j <= h, -a[N + h - j] for j > h; b' = b[h]
+IYK_HD u32 sample_extract_index_word(const u32* trlwe, int h, int j)
+{
+    if (j == NTT_N) return trlwe[NTT_N + h];
+    return j <= h ? trlwe[h - j] : 0u - trlwe[NTT_N + h - j];
+}
+
 }  // namespace iyk

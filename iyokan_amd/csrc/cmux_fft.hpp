@@ -1,0 +1,163 @@
+// cmux_fft.hpp — one CMUX (TRGSW selector x TRLWE) per 64-lane wavefront on the complex-FFT path: the CMUX tree of Iyokan's ROM / RAM.
+//
+// A job {sel, in0, in1, rot, out} on a TRLWE store T (rows of 2N words: a(X), then b(X)) and a selector store S:
+//     D   = (in1 >= 0) ? T[in1] - T[in0] : (X^rot - 1) T[in0]            (both polynomials, mod 2^32, rot in [0, 2N))
+//     out = T[in0] + sum_r digits_r(D) (*) S[sel][r]                       (r over the (k+1) l rows, Gadget<L, BGBIT> digits)
+// i.e. ONE step of the blind rotation (blind_rotate_fft.hpp) whose difference comes from two rows instead of a rotation of the
+// accumulator, and whose key row is the caller's TRGSW instead of BK[i].  sel = 1 selects in1.  A selector slot has the layout of
+// one step of the key spectra: cplx [(k+1) l][k+1][2][512], scaled by 1/512 (bk_fft_kernel makes both).  The product is the exact
+// schoolbook one mod 2^32: the rounding bound of DESIGN.md section 2b holds for any key words and any digits.
+//
+// Per job: T[in0] -> the wave's LDS accumulator (so that out may be in0 or in1), u[16] per polynomial, 2 L rows of digits ->
+// forward transform -> MAC into four spectra, two inverse transforms per output polynomial, rounded and added, accumulator -> T[out].
+//
+// Replaces TFHEpp::CMUXFFT<Lvl1>(res, cs, c1, c0) (res = c0 + cs [.] (c1 - c0)) and trgswfftExternalProduct after
+// PolynomialMulByXaiMinusOne in TaskTFHEppROMUX / TaskTFHEppRAMUX / TaskTFHEppRAMCMUXs
+// (/root/reference/src/iyokan_tfhepp.hpp:267,282-291,426-443,627); TFHEpp's product is an inexact FP64 FFT, this one is exact.
+#pragma once
+#include "blind_rotate_fft.hpp"
+
+namespace iyk {
+
+struct CmuxJob {
+    int32_t sel, in0, in1, rot, out;
+};
+
+namespace fft {
+
+// cplx per selector slot: (k+1) l rows of (k+1) polynomials of two half spectra
+template <class G>
+constexpr u32 trgsw_slot_cplx() { return (u32)(2 * G::L) * 4u * (u32)M; }
+
+// T[in0] -> accumulator: word L + 64 e, e < 32
+IYK_HD void cmux_load_acc(int L, const u32* t_in0, u32* acc)
+{
+#pragma unroll
+    for (int e = 0; e < 32; ++e) acc[L + 64 * e] = t_in0[L + 64 * e];
+}
+IYK_HD void cmux_store_acc(int L, const u32* acc, u32* t_out)
+{
+#pragma unroll
+    for (int e = 0; e < 32; ++e) t_out[L + 64 * e] = acc[L + 64 * e];
+}
+// u[q] = prepare((T[in1]_c - T[in0]_c)[L + 64 q]), q < 16; in1_c = polynomial c of T[in1] in global memory, acc_c = of T[in0] in LDS
+template <class G>
+IYK_HD void cmux_diff16(int L, const u32* in1_c, const u32* acc_c, u32 (&u)[16])
+{
+    u32 w[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) w[q] = in1_c[L + 64 * q];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) u[q] = G::prepare(w[q] - acc_c[L + 64 * q]);
+}
+
+}  // namespace fft
+
+#if defined(__HIPCC__)
+// One wavefront per job, BR_WAVES jobs per workgroup, the LDS map of blind_rotate_fft_kernel (kernels_fft.hpp, included first).  The
+// waves of a workgroup are independent (own selector, form, rot); idle waves of the last workgroup recompute the last job and
+// discard it.  The buffer descriptor is built per job on the selector's own base: its 32-bit offsets never limit the store's size.
+template <class G, bool CHECK>
+__global__ __launch_bounds__(64 * BR_WAVES, 2) void cmux_fft_kernel(const CmuxJob* __restrict__ jobs, int njobs,
+                                                                    const fft::cplx* __restrict__ trgsw, u32* trlwe,
+                                                                    const fft::Consts* __restrict__ Cp,
+                                                                    unsigned long long* __restrict__ max_err_bits)
+{
+    const fft::Consts& C = *Cp;
+    constexpr int L = G::L;
+    extern __shared__ __attribute__((aligned(4096))) unsigned char smem[];
+    fft::cplx* s_t1 = reinterpret_cast<fft::cplx*>(smem);                                   // [k0][lane]
+    u32* s_acc = reinterpret_cast<u32*>(smem + BR_FFT_T1_BYTES);                            // [BR_WAVES][2][NTT_N]
+    fft::cplx* s_xb = reinterpret_cast<fft::cplx*>(smem + BR_FFT_T1_BYTES + (size_t)BR_WAVES * 2 * NTT_N * sizeof(u32));
+    fft::cplx* s_t2 = s_xb + (size_t)BR_WAVES * (fft::XCHG_BYTES / sizeof(fft::cplx));      // [b][a]
+    fft::Lf* s_lf3 = reinterpret_cast<fft::Lf*>(s_t2 + 64);   // [which][lane'']
+    fft::Lf* s_lf2 = s_lf3 + 4 * 64;                           // [which][k0]
+    for (int e = threadIdx.x; e < 8 * 64; e += 64 * BR_WAVES) s_t1[e] = C.t1[e >> 6][e & 63];
+    if (threadIdx.x < 64) s_t2[threadIdx.x] = C.t2t[threadIdx.x >> 3][threadIdx.x & 7];
+    if (threadIdx.x < 4 * 64) s_lf3[threadIdx.x] = C.lf3[threadIdx.x >> 6][threadIdx.x & 63];
+    if (threadIdx.x < 4 * 8) s_lf2[threadIdx.x] = C.lf2[threadIdx.x >> 3][threadIdx.x & 7];
+    __syncthreads();
+
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane0 = threadIdx.x & 63;
+    int job = blockIdx.x * BR_WAVES + wave;
+    const bool live = job < njobs;
+    if (!live) job = njobs - 1;
+    // the job's five words are wave-uniform: said so to the compiler (scalar registers, a provably uniform descriptor)
+    const int j_sel = __builtin_amdgcn_readfirstlane(jobs[job].sel), j_in0 = __builtin_amdgcn_readfirstlane(jobs[job].in0);
+    const int j_in1 = __builtin_amdgcn_readfirstlane(jobs[job].in1), j_out = __builtin_amdgcn_readfirstlane(jobs[job].out);
+    const u32 j_rot = (u32)__builtin_amdgcn_readfirstlane(jobs[job].rot);
+
+    u32* acc_lds = s_acc + wave * 2 * NTT_N;
+    fft::cplx* xb = s_xb + (size_t)wave * (fft::XCHG_BYTES / sizeof(fft::cplx));
+    fft::cmux_load_acc(lane0, trlwe + (size_t)j_in0 * (2 * NTT_N), acc_lds);
+    lds_sync();
+
+    constexpr u32 SLOT = fft::trgsw_slot_cplx<G>();
+    const fft::Keys keys(trgsw + (size_t)j_sel * SLOT, SLOT * (u32)sizeof(fft::cplx), lane0);
+    fft::Twist U = C.u;
+    asm volatile("" : "+s"(U.c1), "+s"(U.s1), "+s"(U.c2), "+s"(U.s2), "+s"(U.c3), "+s"(U.s3));
+    fft::LfU LU = C.lu;
+    asm volatile("" : "+s"(LU.t2), "+s"(LU.c2), "+s"(LU.t1), "+s"(LU.c1), "+s"(LU.t1w), "+s"(LU.c1w));
+
+    fft::cplx S[2][2][8];   // [c'][half][k2]
+    u32 u[16];
+#pragma unroll
+    for (int e = 0; e < 32; ++e) S[e >> 4][(e >> 3) & 1][e & 7] = {0.0, 0.0};
+#pragma unroll 1
+    for (int r = 0; r < 2 * L; ++r) {
+        const int lane = fft_lane_id(lane0);   // recomputed where it is needed, as in blind_rotate_fft_kernel: never worth a spill
+        const int c = r >= L ? 1 : 0, lvl = r - c * L;
+        if (lvl == 0) {
+            if (j_in1 >= 0) fft::cmux_diff16<G>(lane, trlwe + (size_t)j_in1 * (2 * NTT_N) + c * NTT_N, acc_lds + c * NTT_N, u);
+            else fft::diff16<G>(lane, j_rot, acc_lds + c * NTT_N, u);
+        }
+        fft::cplx a[8];
+        fft::digits8<G>(lvl, u, a);
+        // the row's first key words go out before the transform and land under it; the rest a frequency block ahead of its products
+        const u32 row_off = (u32)r * 4u * (u32)fft::M;
+        const u32 koff = (u32)lane * 16u;
+        fft::cplx k0[4], k1[4];
+#pragma unroll
+        for (int pc = 0; pc < 4; ++pc) k0[pc] = keys.at_lane(koff, row_off, pc, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        fft_forward_lf(lane, a, LU, s_lf2, s_lf3, xb);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            fft::cplx (&cur)[4] = (q & 1) ? k1 : k0;
+            fft::cplx (&nxt)[4] = (q & 1) ? k0 : k1;
+            __builtin_amdgcn_sched_barrier(0);   // the loads stay where they are written: hoisted, a row's 32 values do not fit
+            if (q + 1 < 8) {
+#pragma unroll
+                for (int pc = 0; pc < 4; ++pc) nxt[pc] = keys.at_lane(koff, row_off, pc, q + 1);
+            }
+#pragma unroll
+            for (int pc = 0; pc < 4; ++pc) fft::cmac<false>(S[pc >> 1][pc & 1][q], a[q], cur[pc]);
+        }
+    }
+    double worst = 0.0;
+#pragma unroll
+    for (int cc = 0; cc < 2; ++cc) {
+        const int lane = fft_lane_id(lane0);
+        u32 lo[16];
+        fft_inverse2(lane, S[cc][0], S[cc][1], U, s_t1 + lane, s_t2 + (lane & 7), xb);
+        if (CHECK) {
+            const double e0 = fft::round_err8(S[cc][0]), e1 = fft::round_err8(S[cc][1]);
+            worst = e0 > worst ? e0 : worst;
+            worst = e1 > worst ? e1 : worst;
+        }
+        fft::round16(S[cc][0], lo);
+        fft::acc_update16(lane, S[cc][1], lo, acc_lds + cc * NTT_N);
+    }
+    set_prio<0>();
+    lds_sync();
+    if (CHECK && max_err_bits) {   // non-negative doubles order like their bit patterns
+        unsigned long long b;
+        __builtin_memcpy(&b, &worst, 8);
+        atomicMax(max_err_bits, b);
+    }
+    if (live) fft::cmux_store_acc(lane0, acc_lds, trlwe + (size_t)j_out * (2 * NTT_N));
+}
+#endif
+
+}  // namespace iyk

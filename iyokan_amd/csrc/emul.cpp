@@ -15,6 +15,7 @@
 #include "blind_rotate_lat3.hpp"
 #include "blind_rotate_t16.hpp"
 #include "blind_rotate_fft.hpp"
+#include "cmux_fft.hpp"
 #include "fft256.hpp"
 #include "dispatch.hpp"
 
@@ -616,6 +617,49 @@ void blind_rotate_fft(const iyk_params* p, const u32* lin, const fft::cplx* bk_f
     tlwe1[NTT_N] = acc[NTT_N];
 }
 
+// lane-by-lane run of cmux_fft.hpp::cmux_fft_kernel for one job, in place on the TRLWE rows T (same phase functions, same order)
+template <class G>
+void cmux_fft(const CmuxJob& j, const fft::cplx* trgsw, u32* T)
+{
+    constexpr int L = G::L;
+    std::vector<u32> acc(2 * NTT_N);
+    std::vector<fft::cplx> xbuf(fft::XCHG_BYTES / sizeof(fft::cplx));
+    fft::cplx* xb = xbuf.data();
+    const fft::cplx* slot = trgsw + (size_t)j.sel * fft::trgsw_slot_cplx<G>();
+    static thread_local fft::cplx S[2][2][64][8], a[64][8];
+    static thread_local u32 u[64][16], lo[64][16];
+    ALL_LANES fft::cmux_load_acc(lane, T + (size_t)j.in0 * (2 * NTT_N), acc.data());
+    ALL_LANES for (int e = 0; e < 32; ++e) S[e >> 4][(e >> 3) & 1][lane][e & 7] = {0.0, 0.0};
+    for (int r = 0; r < 2 * L; ++r) {
+        const int c = r >= L ? 1 : 0, lvl = r - c * L;
+        if (lvl == 0) {
+            if (j.in1 >= 0) ALL_LANES fft::cmux_diff16<G>(lane, T + (size_t)j.in1 * (2 * NTT_N) + c * NTT_N, acc.data() + c * NTT_N, u[lane]);
+            else ALL_LANES fft::diff16<G>(lane, (u32)j.rot, acc.data() + c * NTT_N, u[lane]);
+        }
+        ALL_LANES fft::digits8<G>(lvl, u[lane], a[lane]);
+        fft_forward_lf_wave(a, xb);
+        const u32 row_off = (u32)r * 4u * (u32)fft::M;
+        ALL_LANES
+        {
+            const fft::Keys keys(slot, 0, lane);
+            for (int q = 0; q < 8; ++q)
+                for (int pc = 0; pc < 4; ++pc) fft::cmac<false>(S[pc >> 1][pc & 1][lane][q], a[lane][q], keys.at(row_off, pc, q));
+        }
+    }
+    for (int cc = 0; cc < 2; ++cc) {
+        fft_inverse_wave(S[cc][0], xb);
+        fft_inverse_wave(S[cc][1], xb);
+        ALL_LANES
+        {
+            const double e0 = fft::round_err8(S[cc][0][lane]), e1 = fft::round_err8(S[cc][1][lane]);
+            g_fft_worst = std::max(g_fft_worst, std::max(e0, e1));
+            fft::round16(S[cc][0][lane], lo[lane]);
+        }
+        ALL_LANES fft::acc_update16(lane, S[cc][1][lane], lo[lane], acc.data() + cc * NTT_N);
+    }
+    ALL_LANES fft::cmux_store_acc(lane, acc.data(), T + (size_t)j.out * (2 * NTT_N));
+}
+
 // one inverse transform of one wave (kernels_fft.hpp::fft_inverse1)
 void fft_inverse1_wave(fft::cplx (*a)[8], fft::cplx* xb)
 {
@@ -844,6 +888,30 @@ int iyk_emul_blind_rotate_fft_lat(const iyk_params* p, const uint32_t* lin, cons
     if (p->l == 3 && p->Bgbit == 6) blind_rotate_fft_lat<fft::Gadget<3, 6>>(p, lin, k, tlwe1);
     else if (p->l == 2 && p->Bgbit == 10) blind_rotate_fft_lat<fft::Gadget<2, 10>>(p, lin, k, tlwe1);
     else return -1;
+    return 0;
+}
+/* cmux_fft.hpp: the jobs {sel, in0, in1, rot, out} one after the other, in place on `rows` TRLWE rows of 2N words.  set: 0 = the 128-bit
+ * set's Gadget<3, 6>, 1 = the 80-bit set's Gadget<2, 10>; trgsw_fft: `sels` selector slots in the device layout (iyk_emul_bk_fft of
+ * one TRGSW per slot).  -1: unknown set or an index outside its store. */
+int emu_cmux_fft(int set, uint32_t* trlwe, uint64_t rows, const double* trgsw_fft, uint64_t sels, const int32_t* jobs, uint64_t count)
+{
+    if (set != 0 && set != 1) return -1;
+    const fft::cplx* k = reinterpret_cast<const fft::cplx*>(trgsw_fft);
+    for (uint64_t g = 0; g < count; ++g) {
+        const CmuxJob j{jobs[5 * g], jobs[5 * g + 1], jobs[5 * g + 2], jobs[5 * g + 3], jobs[5 * g + 4]};
+        auto row_ok = [&](int32_t r) { return r >= 0 && (uint64_t)r < rows; };
+        if (j.sel < 0 || (uint64_t)j.sel >= sels || !row_ok(j.in0) || !row_ok(j.out) || (j.in1 >= 0 && !row_ok(j.in1))) return -1;
+        if (j.in1 < 0 && (j.rot < 0 || j.rot >= 2 * NTT_N)) return -1;
+        if (set == 0) cmux_fft<fft::Gadget<3, 6>>(j, k, trlwe);
+        else cmux_fft<fft::Gadget<2, 10>>(j, k, trlwe);
+    }
+    return 0;
+}
+/* kernels.hpp::sample_extract_index_kernel for one TRLWE: N + 1 words of the TLWE lvl1 at coefficient index h < N */
+int emu_sample_extract_index(const uint32_t* trlwe, int h, uint32_t* tlwe1)
+{
+    if (h < 0 || h >= NTT_N) return -1;
+    for (int j = 0; j <= NTT_N; ++j) tlwe1[j] = sample_extract_index_word(trlwe, h, j);
     return 0;
 }
 /* The half transforms of fft256.hpp against the full ones of fft512.hpp on the same random input: forward — F_0 +- W^k' F_1

@@ -17,6 +17,7 @@
 
 #include <chrono>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -39,6 +40,7 @@
 #include "kernels_fft.hpp"
 #define IYK_BUILD_ID_SUFFIX ""
 #endif
+#include "cmux_fft.hpp"
 
 using namespace iyk;
 using namespace iyk::dispatch;
@@ -531,7 +533,9 @@ int set_fft_attrs()
     if ((rc = set_lds(blind_rotate_fft_kernel<GD, false>, BR_FFT_LDS_BYTES))) return rc;
     if ((rc = set_lds(blind_rotate_fft_kernel<GD, true>, BR_FFT_LDS_BYTES))) return rc;
     if ((rc = set_lds(blind_rotate_fft_lat_kernel<GD, false>, BrLatFft<GD>::LDS_BYTES))) return rc;
-    return set_lds(blind_rotate_fft_lat_kernel<GD, true>, BrLatFft<GD>::LDS_BYTES);
+    if ((rc = set_lds(blind_rotate_fft_lat_kernel<GD, true>, BrLatFft<GD>::LDS_BYTES))) return rc;
+    if ((rc = set_lds(cmux_fft_kernel<GD, false>, BR_FFT_LDS_BYTES))) return rc;
+    return set_lds(cmux_fft_kernel<GD, true>, BR_FFT_LDS_BYTES);
 }
 int set_kernel_attrs(const iyk_params& p, bool use_fp, int split)
 {
@@ -2027,6 +2031,154 @@ int iyk_hip_sample_extract_keyswitch_batch(iyk_hip_stream* st, const uint32_t* d
     HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, total, hipMemcpyHostToDevice, st->s));
     hipLaunchKernelGGL(sample_extract_kernel, dim3((unsigned)count), dim3(256), 0, st->s, d_trlwe,
                        (const int32_t*)(st->d_stage + soff + idx_off), st->d_rot);
+    HIP_TRY(hipGetLastError());
+    if ((rc = launch_keyswitch(st, d_arena, (const KsJob*)(st->d_stage + soff), (int)count))) return rc;
+    return release_stage(st);
+    IYK_API_END
+}
+
+/* ---- CMUX memories: TRGSW selectors, batched CMUX, extraction at a coefficient index ------------------------------------ */
+
+namespace {
+
+// the spectra these entry points read and write exist on the default path only
+int need_fft_path(const char* what)
+{
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    if (!G.use_fft) return fail(IYK_ERR_STATE, std::string(what) + " needs the FFT key spectra: not available with IYK_HIP_NTT=fp / goldilocks");
+    return IYK_OK;
+}
+size_t trgsw_polys() { return (size_t)(G.p.k + 1) * G.p.l * (G.p.k + 1); }                 // torus polynomials per TRGSW
+size_t trgsw_slot_bytes() { return trgsw_polys() * 2 * fft::M * sizeof(fft::cplx); }      // spectrum form
+constexpr uint64_t TRGSW_UPLOAD_CHUNK = 16;   // selectors per staging slot (768 KiB at the 128-bit set)
+
+}  // namespace
+
+int iyk_hip_trgsw_alloc(int gpu_index, uint64_t count, void** d_trgsw_out)
+{
+    if (int rc = need_fft_path("iyk_hip_trgsw_alloc")) return rc;
+    if (!d_trgsw_out || count == 0 || count > (1ull << 24)) return fail(IYK_ERR_INVALID, "bad argument");
+    int rc = set_device(gpu_index);
+    if (rc) return rc;
+    HIP_TRY(hipMalloc(d_trgsw_out, count * trgsw_slot_bytes()));
+    return IYK_OK;
+}
+
+int iyk_hip_trgsw_free(int gpu_index, void* d_trgsw)
+{
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    int rc = set_device(gpu_index);
+    if (rc) return rc;
+    HIP_TRY(hipFree(d_trgsw));
+    return IYK_OK;
+}
+
+int iyk_hip_trgsw_upload(iyk_hip_stream* st, void* d_trgsw, uint64_t trgsw_slots, uint64_t first, uint64_t count,
+                         const uint32_t* host_trgsw)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_trgsw_upload")) return rc;
+    if (!st || !d_trgsw || !host_trgsw) return fail(IYK_ERR_INVALID, "null argument");
+    if (trgsw_slots > (1ull << 24) || first > trgsw_slots || count > trgsw_slots - first)
+        return fail(IYK_ERR_INVALID, "slot range outside the selector store");
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    const Device& D = G.devs[st->gpu];
+    const size_t polys = trgsw_polys(), words = polys * NTT_N;
+    for (uint64_t done = 0; done < count; done += TRGSW_UPLOAD_CHUNK) {
+        const uint64_t c = std::min<uint64_t>(TRGSW_UPLOAD_CHUNK, count - done);
+        const size_t bytes = (size_t)c * words * sizeof(u32);
+        size_t soff = 0;
+        if ((rc = acquire_stage(st, bytes, &soff))) return rc;
+        std::memcpy(st->h_stage + soff, host_trgsw + (size_t)done * words, bytes);   // the caller's rows are free on return
+        HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+        fft::cplx* dst = (fft::cplx*)d_trgsw + (size_t)(first + done) * polys * 2 * fft::M;
+        hipLaunchKernelGGL(bk_fft_kernel, dim3((unsigned)(c * polys * 2)), dim3(64), 0, st->s, (const u32*)(st->d_stage + soff), dst,
+                           &D.fftc->c, (size_t)c * polys);
+        HIP_TRY(hipGetLastError());
+        if ((rc = release_stage(st))) return rc;
+    }
+    return IYK_OK;
+    IYK_API_END
+}
+
+int iyk_hip_cmux_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
+                       uint64_t count, const int32_t* sel, const int32_t* in0, const int32_t* in1, const int32_t* rot,
+                       const int32_t* out)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_cmux_batch")) return rc;
+    if (!st || !d_trgsw || !d_trlwe || !sel || !in0 || !in1 || !rot || !out) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    if (count > (1u << 24)) return fail(IYK_ERR_INVALID, "batch too large");
+    if (trgsw_slots > (1ull << 24) || trlwe_slots > (1ull << 28)) return fail(IYK_ERR_INVALID, "store larger than an allocation can be");
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    std::vector<CmuxJob> jobs(count);
+    std::unordered_map<int32_t, uint64_t> writer;   // out row -> its job
+    writer.reserve(count * 2);
+    for (uint64_t g = 0; g < count; ++g) {
+        if (!slot_ok(sel[g], trgsw_slots)) return fail(IYK_ERR_INVALID, "selector index outside the selector store");
+        if (!slot_ok(in0[g], trlwe_slots) || !slot_ok(out[g], trlwe_slots) || (in1[g] >= 0 && !slot_ok(in1[g], trlwe_slots)))
+            return fail(IYK_ERR_INVALID, "TRLWE index outside the buffer");
+        if (in1[g] < 0 && (rot[g] < 0 || rot[g] >= 2 * NTT_N)) return fail(IYK_ERR_INVALID, "rot outside [0, 2N)");
+        if (!writer.emplace(out[g], g).second) return fail(IYK_ERR_INVALID, "two jobs of one batch write the same TRLWE row");
+        jobs[g] = CmuxJob{sel[g], in0[g], in1[g] >= 0 ? in1[g] : -1, in1[g] >= 0 ? 0 : rot[g], out[g]};
+    }
+    for (uint64_t g = 0; g < count; ++g)   // a job may write over its own inputs, never over another job's
+        for (const int32_t in : {in0[g], in1[g]}) {
+            if (in < 0) continue;
+            const auto w = writer.find(in);
+            if (w != writer.end() && w->second != g) return fail(IYK_ERR_INVALID, "a job reads a TRLWE row that another job of the batch writes");
+        }
+    const size_t bytes = jobs.size() * sizeof(CmuxJob);
+    size_t soff = 0;
+    if ((rc = acquire_stage(st, bytes, &soff))) return rc;
+    std::memcpy(st->h_stage + soff, jobs.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+    const Device& D = G.devs[st->gpu];
+    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
+        typedef decltype(gd) GD;
+        auto kern = G.debug ? cmux_fft_kernel<GD, true> : cmux_fft_kernel<GD, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((count + BR_WAVES - 1) / BR_WAVES)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s,
+                           (const CmuxJob*)(st->d_stage + soff), (int)count, (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
+        HIP_TRY(hipGetLastError());
+        return (int)IYK_OK;
+    });
+    if (rc) return rc;
+    return release_stage(st);
+    IYK_API_END
+}
+
+int iyk_hip_sample_extract_index_keyswitch_batch(iyk_hip_stream* st, const uint32_t* d_trlwe, uint64_t trlwe_slots, uint64_t count,
+                                                 const int32_t* trlwe_index, const int32_t* coeff_index, const int32_t* out_slot,
+                                                 uint32_t* d_arena, uint64_t arena_slots)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    if (!st || !d_trlwe || !trlwe_index || !coeff_index || !out_slot || !d_arena) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    if (count > (1u << 30)) return fail(IYK_ERR_INVALID, "batch too large");
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    std::vector<KsJob> ks(count);
+    for (uint64_t g = 0; g < count; ++g) {
+        if (!slot_ok(trlwe_index[g], trlwe_slots)) return fail(IYK_ERR_INVALID, "TRLWE index outside the buffer");
+        if (coeff_index[g] < 0 || coeff_index[g] >= NTT_N) return fail(IYK_ERR_INVALID, "coefficient index outside [0, N)");
+        if (!slot_ok(out_slot[g], arena_slots)) return fail(IYK_ERR_INVALID, "output slot outside the arena");
+        ks[g] = KsJob{(int32_t)g, -1, 0u, out_slot[g]};
+    }
+    const size_t ks_bytes = ks.size() * sizeof(KsJob), idx_off = (ks_bytes + 15) & ~(size_t)15;
+    const size_t idx_bytes = (count * sizeof(int32_t) + 15) & ~(size_t)15, total = idx_off + 2 * idx_bytes;
+    size_t soff = 0;
+    if ((rc = acquire_stage(st, total, &soff))) return rc;
+    if ((rc = ensure_rot(st, count))) return rc;
+    std::memcpy(st->h_stage + soff, ks.data(), ks_bytes);
+    std::memcpy(st->h_stage + soff + idx_off, trlwe_index, count * sizeof(int32_t));
+    std::memcpy(st->h_stage + soff + idx_off + idx_bytes, coeff_index, count * sizeof(int32_t));
+    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, total, hipMemcpyHostToDevice, st->s));
+    hipLaunchKernelGGL(sample_extract_index_kernel, dim3((unsigned)count), dim3(256), 0, st->s, d_trlwe,
+                       (const int32_t*)(st->d_stage + soff + idx_off), (const int32_t*)(st->d_stage + soff + idx_off + idx_bytes), st->d_rot);
     HIP_TRY(hipGetLastError());
     if ((rc = launch_keyswitch(st, d_arena, (const KsJob*)(st->d_stage + soff), (int)count))) return rc;
     return release_stage(st);

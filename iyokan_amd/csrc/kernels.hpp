@@ -9,6 +9,7 @@
 //                                                     narrow frontiers of IYK_HIP_NTT=fp (3.35 ms per rotation)
 //               blind_rotate_kernel<L,BGBIT>          one wavefront per rotation, Goldilocks integers (IYK_HIP_NTT=goldilocks)
 //               sample_extract_kernel                 TRLWE -> TLWE lvl1 (CMUX-memory helper entry point only)
+//               sample_extract_index_kernel           the same at a per-job coefficient index (the bits of a ROM / RAM word; the CMUX itself: cmux_fft.hpp)
 //               keyswitch_init_kernel + keyswitch_wave_kernel<T,NC,16>   lvl1 -> lvl0 identity key switch, 16 gates and whole rows
 //                                                     per wavefront (keyswitch_kernel<T>: round 1's 16 gates per workgroup, A/B + fallback);
 //                                                     <.., SHARED = true> for batches <= 4096 gates: a workgroup's four waves on the
@@ -888,6 +889,17 @@ __global__ __launch_bounds__(256) void sample_extract_kernel(const u32* __restri
     u32* out = rot + (size_t)blockIdx.x * (NTT_N + 1);
     for (int j = threadIdx.x; j < NTT_N; j += 256) out[j] = (j == 0) ? in[0] : 0u - in[NTT_N - j];
     if (threadIdx.x == 0) out[NTT_N] = in[NTT_N];
+}
+// The same at coefficient index coeff_index[job] < N (TFHEpp SampleExtractIndex(., h), TaskTFHEppSEI): the bits of a ROM / RAM word.
+__global__ __launch_bounds__(256) void sample_extract_index_kernel(const u32* __restrict__ trlwe,
+                                                                   const int32_t* __restrict__ src_index,
+                                                                   const int32_t* __restrict__ coeff_index,
+                                                                   u32* __restrict__ rot)
+{
+    const u32* in = trlwe + (size_t)src_index[blockIdx.x] * (2 * NTT_N);
+    const int h = coeff_index[blockIdx.x];
+    u32* out = rot + (size_t)blockIdx.x * (NTT_N + 1);
+    for (int j = threadIdx.x; j <= NTT_N; j += 256) out[j] = sample_extract_index_word(in, h, j);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -35,6 +35,8 @@ EXPORTS = [
     "iyk_hip_arena_sync_slots", "iyk_hip_trlwe_alloc", "iyk_hip_trlwe_free", "iyk_hip_trlwe_upload",
     "iyk_hip_trlwe_download", "iyk_hip_rotation_round", "iyk_hip_arena_sync_slots_multi", "iyk_hip_peer_access",
     "iyk_hip_build_id", "iyk_hip_host_alloc", "iyk_hip_host_free", "iyk_hip_init_profile",
+    "iyk_hip_trgsw_alloc", "iyk_hip_trgsw_free", "iyk_hip_trgsw_upload", "iyk_hip_cmux_batch",
+    "iyk_hip_sample_extract_index_keyswitch_batch",
 ]
 
 
@@ -83,6 +85,11 @@ def lib():
         L.iyk_hip_blind_rotate_batch.argtypes = [_vp, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p, _u32p, _vp]
         L.iyk_hip_bootstrap_trlwe_batch.argtypes = [_vp, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p, _u32p, _vp, u64, _i32p]
         L.iyk_hip_sample_extract_keyswitch_batch.argtypes = [_vp, _vp, u64, u64, _i32p, _i32p, _vp, u64]
+        L.iyk_hip_sample_extract_index_keyswitch_batch.argtypes = [_vp, _vp, u64, u64, _i32p, _i32p, _i32p, _vp, u64]
+        L.iyk_hip_trgsw_alloc.argtypes = [ctypes.c_int, u64, ctypes.POINTER(_vp)]
+        L.iyk_hip_trgsw_free.argtypes = [ctypes.c_int, _vp]
+        L.iyk_hip_trgsw_upload.argtypes = [_vp, _vp, u64, u64, u64, _u32p]
+        L.iyk_hip_cmux_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p, _i32p]
         L.iyk_hip_last_batch_timing.argtypes = [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.iyk_hip_resident_key_bytes.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
         L.iyk_hip_level_cost_ms.restype = ctypes.c_double
@@ -249,6 +256,58 @@ class Arena:
             pass
 
 
+class Trlwe:
+    """Device-resident rows of TRLWE lvl1 ciphertexts (2N words each: a(X), then b(X)) — the cells of a ROM / RAM."""
+
+    def __init__(self, slots, gpu_index=0):
+        self.slots, self.gpu_index = int(slots), gpu_index
+        self.words = 2 * current_params().N
+        ptr = _vp()
+        _check(lib().iyk_hip_trlwe_alloc(gpu_index, self.slots, ctypes.byref(ptr)), "iyk_hip_trlwe_alloc")
+        self.ptr = ptr.value
+
+    def upload(self, stream, first, host):
+        host = np.ascontiguousarray(host, dtype=np.uint32).reshape(-1, self.words)
+        _check(lib().iyk_hip_trlwe_upload(stream.h, self.ptr, self.slots, first, host.shape[0], host.ctypes.data_as(_u32p)),
+               "iyk_hip_trlwe_upload")
+        stream.sync()  # host buffer is pageable: finish before it can be garbage collected
+
+    def download(self, stream, first, count):
+        out = np.zeros((count, self.words), dtype=np.uint32)
+        _check(lib().iyk_hip_trlwe_download(stream.h, self.ptr, self.slots, first, count, out.ctypes.data_as(_u32p)),
+               "iyk_hip_trlwe_download")
+        stream.sync()
+        return out
+
+    def free(self):
+        if self.ptr:
+            _check(lib().iyk_hip_trlwe_free(self.gpu_index, self.ptr), "iyk_hip_trlwe_free")
+        self.ptr = None
+
+
+class Trgsw:
+    """Device-resident TRGSW lvl1 selectors in spectrum form (the TRGSWLvl1FFT inputs of the reference's ROM / RAM tasks)."""
+
+    def __init__(self, slots, gpu_index=0):
+        self.slots, self.gpu_index = int(slots), gpu_index
+        p = current_params()
+        self.words = (p.k + 1) * p.l * (p.k + 1) * p.N   # torus words of one host-side TRGSW
+        ptr = _vp()
+        _check(lib().iyk_hip_trgsw_alloc(gpu_index, self.slots, ctypes.byref(ptr)), "iyk_hip_trgsw_alloc")
+        self.ptr = ptr.value
+
+    def upload(self, stream, first, host):
+        """Torus-domain rows u32 [count][(k+1) l][k+1][N] (client.encrypt_trgsw); copied before return, transformed on the stream."""
+        host = np.ascontiguousarray(host, dtype=np.uint32).reshape(-1, self.words)
+        _check(lib().iyk_hip_trgsw_upload(stream.h, self.ptr, self.slots, first, host.shape[0], host.ctypes.data_as(_u32p)),
+               "iyk_hip_trgsw_upload")
+
+    def free(self):
+        if self.ptr:
+            _check(lib().iyk_hip_trgsw_free(self.gpu_index, self.ptr), "iyk_hip_trgsw_free")
+        self.ptr = None
+
+
 class Stream:
     """CUFHEStream equivalent (/root/reference/src/iyokan_cufhe.hpp:8-27)."""
 
@@ -375,6 +434,25 @@ class Stream:
         _check(lib().iyk_hip_sample_extract_keyswitch_batch(self.h, _vp(int(d_trlwe_ptr)), nt, len(ti), p(ti), p(os_),
                                                             arena.ptr, arena.slots),
                "iyk_hip_sample_extract_keyswitch_batch")
+
+    def sample_extract_index_keyswitch_batch(self, trlwe, trlwe_index, coeff_index, out_slot, arena):
+        """TaskTFHEppSEI shape: coefficient coeff_index[g] of row trlwe_index[g] of a Trlwe store -> TLWE lvl0 in arena slot out_slot[g]."""
+        ti, ci, os_ = _i32(trlwe_index), _i32(coeff_index), _i32(out_slot)
+        assert len(ti) == len(ci) == len(os_)
+        p = lambda a: a.ctypes.data_as(_i32p)
+        _check(lib().iyk_hip_sample_extract_index_keyswitch_batch(self.h, trlwe.ptr, trlwe.slots, len(ti), p(ti), p(ci), p(os_),
+                                                                  arena.ptr, arena.slots),
+               "iyk_hip_sample_extract_index_keyswitch_batch")
+
+    def cmux_batch(self, trgsw, trlwe, sel, in0, in1, rot, out):
+        """len(sel) independent CMUXes on rows of a Trlwe store, asynchronous: T[out] = T[in0] + S[sel] [.] (T[in1] - T[in0]) where
+        in1 >= 0 (a selector of 1 selects in1), T[in0] + S[sel] [.] ((X^rot - 1) T[in0]) where in1 < 0.  A job may write over its
+        own inputs; no out may be an input or the out of another job of the batch."""
+        sel, in0, in1, rot, out = map(_i32, (sel, in0, in1, rot, out))
+        assert len(in0) == len(in1) == len(rot) == len(out) == len(sel)
+        p = lambda a: a.ctypes.data_as(_i32p)
+        _check(lib().iyk_hip_cmux_batch(self.h, trgsw.ptr, trgsw.slots, trlwe.ptr, trlwe.slots, len(sel), p(sel), p(in0), p(in1),
+                                        p(rot), p(out)), "iyk_hip_cmux_batch")
 
     def last_batch_timing(self):
         """(blind_rotate_ms, keyswitch_ms) of the most recent batch, from HIP events on this stream."""
