@@ -289,6 +289,31 @@ int iyk_hip_trgsw_upload(iyk_hip_stream* st, void* d_trgsw, uint64_t trgsw_slots
 int iyk_hip_cmux_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe,
                        uint64_t trlwe_slots, uint64_t count, const int32_t* sel, const int32_t* in0,
                        const int32_t* in1, const int32_t* rot, const int32_t* out);
+/* `count` independent CHAINS of CMUXes, asynchronous on st: the RAM write-back of one cell per job.  Job g, with S_j the selector
+ * slot sel0[g] + j and j over 0 .. steps[g] - 1:
+ *     acc = T[src]
+ *     bit j of pattern[g] = 1:  acc = T[mem] + S_j [.] (acc - T[mem])      the cmux job (sel0 + j, in0 = mem, in1 = acc)
+ *     bit j of pattern[g] = 0:  acc = acc    + S_j [.] (T[mem] - acc)      the cmux job (sel0 + j, in0 = acc, in1 = mem)
+ *     T[out] = acc
+ * so acc survives where selector j encrypts bit j of the pattern and T[mem] is chosen otherwise.  Replaces TaskTFHEppRAMCMUXs
+ * (/root/reference/src/iyokan_tfhepp.hpp:622-628: *output_ = written, then CMUXFFT(*output_, normal or inverted selector j, *output_,
+ * *mem_) per address bit, the NORMAL selector where bit j of the cell index is 1): pattern = the cell index, src = the written
+ * TRLWE, mem = out = the cell; the reference's inverted selectors are this call's choice of in0 / in1.  One kernel, the accumulator
+ * in LDS for all steps; word for word what steps[g] successive iyk_hip_cmux_batch jobs give (the product is exact).  The six arrays
+ * are host arrays, copied before return.  Checked on every call, in O(count): 1 <= steps <= 32, sel0 >= 0 and sel0 + steps <=
+ * trgsw_slots, every row < trlwe_slots, and no out[g] is the src / mem / out of ANOTHER job — a job may write over its own src or
+ * mem, and jobs may share src (or mem).  A violation is IYK_ERR_INVALID and nothing is launched; IYK_ERR_STATE off the FFT path. */
+int iyk_hip_cmux_chain_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe,
+                             uint64_t trlwe_slots, uint64_t count, const int32_t* sel0, const int32_t* steps,
+                             const uint32_t* pattern, const int32_t* src, const int32_t* mem, const int32_t* out);
+/* T[out] = T[a] + T[b] mod 2^32 per job, with b0_offset added to coefficient 0 of the b polynomial; asynchronous on st, host
+ * arrays copied before return.  The tail of TFHEpp::HomMUXwoSE<Lvl01> (TaskTFHEppGateMUXWoSE, /root/reference/src/iyokan_tfhepp.hpp:
+ * 500-508): with a, b the rows of the two blind rotations iyk_hip_bootstrap_trlwe_batch(cs + c1 - mu) and (-cs + c0 - mu) and
+ * b0_offset = mu, T[out] is the TRLWE of cs ? c1 : c0.  out[g] may be a[g] or b[g]; no out[g] may be the a / b / out of ANOTHER
+ * job, every row < trlwe_slots: checked on every call, a violation is IYK_ERR_INVALID and nothing is launched.  Available on every
+ * path. */
+int iyk_hip_trlwe_add_batch(iyk_hip_stream* st, uint32_t* d_trlwe, uint64_t trlwe_slots, uint64_t count, const int32_t* a,
+                            const int32_t* b, const int32_t* out, uint32_t b0_offset);
 
 /* Kernel-only time of the most recent iyk_hip_gate_batch on this stream, from HIP events
  * recorded on the stream around the blind-rotate and key-switch launches (milliseconds).

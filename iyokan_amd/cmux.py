@@ -1,7 +1,9 @@
-"""CMUX memories on the GPU: the read tree of a ROM over TRLWE rows (Stream.cmux_batch + index extraction).
+"""CMUX memories on the GPU: the read tree of a ROM over TRLWE rows (Stream.cmux_batch + index extraction), and a RAM — read tree,
+MUXwoSE, one fused chain of CMUXes per cell (Stream.cmux_chain_batch) and the refresh of every cell.
 
 Replaces the reference's TaskTFHEppROMUX (UROMUX + LROMUX, /root/reference/src/iyokan_tfhepp.hpp:238-300) followed by one
-TaskTFHEppSEI per output bit (:340-352).
+TaskTFHEppSEI per output bit (:340-352), and its RAM network (:409-787: TaskTFHEppRAMUX, TaskTFHEppGateMUXWoSE, TaskTFHEppRAMCMUXs,
+TaskTFHEppRAMGateBootstrapping).
 
 Orientation: a CMUX job computes T[out] = T[in0] + S [.] (T[in1] - T[in0]), so a selector that encrypts 1 selects in1.  The plan
 below puts the even row of a pair in in0 and the odd row in in1 and is driven by the address bits AS THEY ARE.  The reference calls
@@ -118,3 +120,134 @@ class Rom:
     def free(self):
         self.trlwe.free()
         self.trgsw.free()
+
+
+# ---- RAM ----------------------------------------------------------------------------------------------------------------------
+# One chain of CMUXes (Stream.cmux_chain_batch): acc = T[src]; step j < steps with selector slot sel0 + j keeps acc where that selector
+# encrypts bit j of pattern and takes T[mem] otherwise; T[out] = acc.
+ChainJob = namedtuple("ChainJob", "sel0 steps pattern src mem out")
+
+
+def ram_layout(addr_width, N):
+    """Rows of the read tree of one bit plane of a RAM: 2^addr_width cells of one bit each (at coefficient 0), the scratch rows of
+    the plan and the scratch row that holds the addressed cell after the last launch."""
+    return rom_layout(addr_width, int(N).bit_length() - 1, N)
+
+
+def ram_read_plan(addr_width, N):
+    """The reference's RAMUX as launches: rom_read_plan at ONE word per TRLWE — level b has 2^(addr_width-1-b) jobs selected by
+    address bit b, the even cell in in0 and the odd cell in in1, the address bits as they are (the reference feeds
+    CMUXFFT(out, inverted selector, even, odd), :421-443)."""
+    return rom_read_plan(addr_width, int(N).bit_length() - 1, N)
+
+
+def ram_write_jobs(addr_width, src, first_cell=0, sel0=0):
+    """The reference's RAMCMUXs of one bit plane, one chain job per cell i < 2^addr_width: pattern = i, steps = addr_width,
+    src = the row of the written TRLWE (MUXwoSE's output), mem = out = the cell's row first_cell + i.  Cell i keeps src where every
+    selector j encrypts bit j of i — the addressed cell — and gets its old content back otherwise."""
+    assert 1 <= addr_width <= 32
+    return [ChainJob(sel0, addr_width, i, src, first_cell + i, first_cell + i) for i in range(1 << addr_width)]
+
+
+def chain_steps(job, acc):
+    """A chain job as `steps` dependent cmux_batch jobs (sel, in0, in1, rot, out), one per launch, with the accumulator kept in row
+    `acc` between them: what Ram.clock(fused=False) sends."""
+    jobs = []
+    for j in range(job.steps):
+        cur = job.src if j == 0 else acc
+        out = job.out if j == job.steps - 1 else acc
+        jobs.append((job.sel0 + j, job.mem, cur, 0, out) if (job.pattern >> j) & 1 else (job.sel0 + j, cur, job.mem, 0, out))
+    return jobs
+
+
+class Ram:
+    """A RAM of 2^addr_width words of data_width bits on one GPU, one TRLWE per bit (the bit at coefficient 0), as the reference
+    keeps it.  One Trlwe store holds the data_width bit planes of 2^addr_width cell rows, then per plane the read tree's scratch
+    rows and two rows for MUXwoSE, then one accumulator row per cell for the unfused write-back; one Trgsw store holds the
+    addr_width selectors of the current clock; a private arena holds the TLWEs between the write-back and the refresh."""
+
+    def __init__(self, stream, cells_trlwe, addr_width, data_width):
+        from . import hip
+
+        p = hip.current_params()
+        self.stream, self.addr_width, self.data_width, self.N, self.mu = stream, int(addr_width), int(data_width), int(p.N), int(p.mu)
+        self.cells_per_plane = C = 1 << self.addr_width
+        self.layout = ram_layout(self.addr_width, p.N)
+        self.plan = ram_read_plan(self.addr_width, p.N)
+        data = np.ascontiguousarray(cells_trlwe, dtype=np.uint32).reshape(-1, 2 * p.N)
+        if data.shape[0] != self.data_width * C:
+            raise ValueError(f"expected {self.data_width} x {C} TRLWE rows, got {data.shape[0]}")
+        self.ncells = self.data_width * C
+        self.plane_scratch = self.layout.scratch_rows + 2
+        self.acc0 = self.ncells + self.data_width * self.plane_scratch
+        self.trlwe = hip.Trlwe(self.acc0 + self.ncells, stream.gpu_index)
+        self.trgsw = hip.Trgsw(self.addr_width, stream.gpu_index)
+        self.arena = hip.Arena(self.ncells, stream.gpu_index)
+        self.trlwe.upload(stream, 0, data)
+
+    def row(self, plane, plan_row):
+        """Row of the TRLWE store that row `plan_row` of the read plan is for bit plane `plane`."""
+        C = self.cells_per_plane
+        return plane * C + plan_row if plan_row < C else self.ncells + plane * self.plane_scratch + (plan_row - C)
+
+    def mux_rows(self, plane):
+        """The two MUXwoSE rows of a plane; the first one holds the written TRLWE after the add."""
+        base = self.ncells + plane * self.plane_scratch + self.layout.scratch_rows
+        return base, base + 1
+
+    def read_launches(self):
+        """The cmux_batch argument lists (sel, in0, in1, rot, out) of the read tree, all planes' jobs of a level in one launch."""
+        out = []
+        for jobs in self.plan:
+            rows = [(j.bit, self.row(d, j.in0), self.row(d, j.in1), 0, self.row(d, j.out)) for d in range(self.data_width) for j in jobs]
+            out.append(tuple(zip(*rows)))
+        return out
+
+    def write_jobs(self):
+        """One ChainJob per cell of every plane, in place on the cell rows, from the plane's written TRLWE."""
+        C = self.cells_per_plane
+        return [j for d in range(self.data_width) for j in ram_write_jobs(self.addr_width, self.mux_rows(d)[0], d * C)]
+
+    def clock(self, addr_trgsw, arena, wren_slot, wdata_slots, rdata_slots, fused=True):
+        """One clock of the reference's RAM network, asynchronous on the stream.  addr_trgsw: u32 [addr_width][(k+1) l][k+1][N]
+        (client.encrypt_trgsw of the address bits, bit 0 first); arena holds the TLWEs of wren (one slot) and wdata (data_width
+        slots) and receives rdata (data_width slots, the addressed word BEFORE the write).  fused=False sends the write-back as
+        addr_width cmux_batch launches instead of one cmux_chain_batch: the same words."""
+        st, w, C = self.stream, self.data_width, self.cells_per_plane
+        wdata_slots, rdata_slots = np.asarray(wdata_slots, dtype=np.int32).ravel(), np.asarray(rdata_slots, dtype=np.int32).ravel()
+        if len(wdata_slots) != w or len(rdata_slots) != w:
+            raise ValueError(f"expected {w} wdata and {w} rdata slots")
+        self.trgsw.upload(st, 0, np.ascontiguousarray(addr_trgsw, dtype=np.uint32).reshape(self.addr_width, self.trgsw.words))
+        # 1, 2: RAMUX, SEI(0) + key switch -> rdata
+        for args in self.read_launches():
+            st.cmux_batch(self.trgsw, self.trlwe, *args)
+        result = [self.row(d, self.layout.result) for d in range(w)]
+        st.sample_extract_index_keyswitch_batch(self.trlwe, result, np.zeros(w, dtype=np.int32), rdata_slots, arena)
+        # 3: HomMUXwoSE: BlindRotate(wren + wdata - mu) + BlindRotate(-wren + rdata - mu), + mu at coefficient 0 of b
+        m1, m0 = zip(*(self.mux_rows(d) for d in range(w)))
+        minus_mu = np.full(2 * w, (-self.mu) & 0xFFFFFFFF, dtype=np.uint32)
+        st.bootstrap_trlwe_batch(arena, [wren_slot] * (2 * w), np.concatenate([wdata_slots, rdata_slots]), [1] * w + [-1] * w,
+                                 [1] * (2 * w), minus_mu, self.trlwe.ptr, trlwe_slots=self.trlwe.slots, trlwe_out=m1 + m0)
+        st.trlwe_add_batch(self.trlwe, m1, m0, m1, self.mu)
+        # 4: RAMCMUXs of every cell, in place
+        jobs = self.write_jobs()
+        if fused:
+            st.cmux_chain_batch(self.trgsw, self.trlwe, *zip(*jobs))
+        else:
+            steps = [chain_steps(j, self.acc0 + g) for g, j in enumerate(jobs)]
+            for s in range(self.addr_width):
+                st.cmux_batch(self.trgsw, self.trlwe, *zip(*(c[s] for c in steps)))
+        # 5, 6: SEI(0) + key switch of every cell, then the blind rotation back into the cell's row
+        cells = np.arange(self.ncells, dtype=np.int32)
+        st.sample_extract_index_keyswitch_batch(self.trlwe, cells, np.zeros(self.ncells, dtype=np.int32), cells, self.arena)
+        st.bootstrap_trlwe_batch(self.arena, cells, np.full(self.ncells, -1), np.ones(self.ncells), np.zeros(self.ncells),
+                                 np.zeros(self.ncells, dtype=np.uint32), self.trlwe.ptr, trlwe_slots=self.trlwe.slots, trlwe_out=cells)
+
+    def cells(self):
+        """The cell rows: u32 [data_width][2^addr_width][2N] (synchronises the stream)."""
+        return self.trlwe.download(self.stream, 0, self.ncells).reshape(self.data_width, self.cells_per_plane, 2 * self.N)
+
+    def free(self):
+        self.trlwe.free()
+        self.trgsw.free()
+        self.arena.free()

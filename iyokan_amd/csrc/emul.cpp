@@ -660,6 +660,54 @@ void cmux_fft(const CmuxJob& j, const fft::cplx* trgsw, u32* T)
     ALL_LANES fft::cmux_store_acc(lane, acc.data(), T + (size_t)j.out * (2 * NTT_N));
 }
 
+// lane-by-lane run of cmux_fft.hpp::cmux_chain_kernel for one job, in place on the TRLWE rows T (same phase functions, same order)
+template <class G>
+void cmux_chain(const CmuxChainJob& j, const fft::cplx* trgsw, u32* T)
+{
+    constexpr int L = G::L;
+    std::vector<u32> acc(2 * NTT_N);
+    std::vector<fft::cplx> xbuf(fft::XCHG_BYTES / sizeof(fft::cplx));
+    fft::cplx* xb = xbuf.data();
+    const u32* mem_row = T + (size_t)j.mem * (2 * NTT_N);
+    static thread_local fft::cplx S[2][2][64][8], a[64][8];
+    static thread_local u32 u[64][16], lo[64][16];
+    ALL_LANES fft::cmux_load_acc(lane, T + (size_t)j.src * (2 * NTT_N), acc.data());
+    for (int s = 0; s < j.steps; ++s) {
+        const bool rev = (j.pattern >> s) & 1u;
+        const fft::cplx* slot = trgsw + (size_t)(j.sel0 + s) * fft::trgsw_slot_cplx<G>();
+        ALL_LANES for (int e = 0; e < 32; ++e) S[e >> 4][(e >> 3) & 1][lane][e & 7] = {0.0, 0.0};
+        for (int r = 0; r < 2 * L; ++r) {
+            const int c = r >= L ? 1 : 0, lvl = r - c * L;
+            if (lvl == 0) {
+                if (rev) ALL_LANES fft::cmux_diff16_rev<G>(lane, mem_row + c * NTT_N, acc.data() + c * NTT_N, u[lane]);
+                else ALL_LANES fft::cmux_diff16<G>(lane, mem_row + c * NTT_N, acc.data() + c * NTT_N, u[lane]);
+            }
+            ALL_LANES fft::digits8<G>(lvl, u[lane], a[lane]);
+            fft_forward_lf_wave(a, xb);
+            const u32 row_off = (u32)r * 4u * (u32)fft::M;
+            ALL_LANES
+            {
+                const fft::Keys keys(slot, 0, lane);
+                for (int q = 0; q < 8; ++q)
+                    for (int pc = 0; pc < 4; ++pc) fft::cmac<false>(S[pc >> 1][pc & 1][lane][q], a[lane][q], keys.at(row_off, pc, q));
+            }
+        }
+        for (int cc = 0; cc < 2; ++cc) {
+            fft_inverse_wave(S[cc][0], xb);
+            fft_inverse_wave(S[cc][1], xb);
+            ALL_LANES
+            {
+                const double e0 = fft::round_err8(S[cc][0][lane]), e1 = fft::round_err8(S[cc][1][lane]);
+                g_fft_worst = std::max(g_fft_worst, std::max(e0, e1));
+                fft::round16(S[cc][0][lane], lo[lane]);
+            }
+            if (rev) ALL_LANES fft::cmux_acc_replace16(lane, mem_row + cc * NTT_N, S[cc][1][lane], lo[lane], acc.data() + cc * NTT_N);
+            else ALL_LANES fft::acc_update16(lane, S[cc][1][lane], lo[lane], acc.data() + cc * NTT_N);
+        }
+    }
+    ALL_LANES fft::cmux_store_acc(lane, acc.data(), T + (size_t)j.out * (2 * NTT_N));
+}
+
 // one inverse transform of one wave (kernels_fft.hpp::fft_inverse1)
 void fft_inverse1_wave(fft::cplx (*a)[8], fft::cplx* xb)
 {
@@ -904,6 +952,24 @@ int emu_cmux_fft(int set, uint32_t* trlwe, uint64_t rows, const double* trgsw_ff
         if (j.in1 < 0 && (j.rot < 0 || j.rot >= 2 * NTT_N)) return -1;
         if (set == 0) cmux_fft<fft::Gadget<3, 6>>(j, k, trlwe);
         else cmux_fft<fft::Gadget<2, 10>>(j, k, trlwe);
+    }
+    return 0;
+}
+/* cmux_fft.hpp::cmux_chain_kernel: the chain jobs {sel0, steps, pattern, src, mem, out} (six 32-bit words each, the pattern's bits in the
+ * third) one after the other, in place on `rows` TRLWE rows.  set and trgsw_fft as for emu_cmux_fft.  -1: unknown set, steps outside
+ * [1, 32], or an index outside its store. */
+int emu_cmux_chain(int set, uint32_t* trlwe, uint64_t rows, const double* trgsw_fft, uint64_t sels, const int32_t* jobs6, uint64_t count)
+{
+    if (set != 0 && set != 1) return -1;
+    const fft::cplx* k = reinterpret_cast<const fft::cplx*>(trgsw_fft);
+    for (uint64_t g = 0; g < count; ++g) {
+        const int32_t* w = jobs6 + 6 * g;
+        const CmuxChainJob j{w[0], w[1], (uint32_t)w[2], w[3], w[4], w[5]};
+        auto row_ok = [&](int32_t r) { return r >= 0 && (uint64_t)r < rows; };
+        if (j.steps < 1 || j.steps > CMUX_CHAIN_MAX_STEPS || j.sel0 < 0 || (uint64_t)j.sel0 + (uint64_t)j.steps > sels) return -1;
+        if (!row_ok(j.src) || !row_ok(j.mem) || !row_ok(j.out)) return -1;
+        if (set == 0) cmux_chain<fft::Gadget<3, 6>>(j, k, trlwe);
+        else cmux_chain<fft::Gadget<2, 10>>(j, k, trlwe);
     }
     return 0;
 }

@@ -535,7 +535,9 @@ int set_fft_attrs()
     if ((rc = set_lds(blind_rotate_fft_lat_kernel<GD, false>, BrLatFft<GD>::LDS_BYTES))) return rc;
     if ((rc = set_lds(blind_rotate_fft_lat_kernel<GD, true>, BrLatFft<GD>::LDS_BYTES))) return rc;
     if ((rc = set_lds(cmux_fft_kernel<GD, false>, BR_FFT_LDS_BYTES))) return rc;
-    return set_lds(cmux_fft_kernel<GD, true>, BR_FFT_LDS_BYTES);
+    if ((rc = set_lds(cmux_fft_kernel<GD, true>, BR_FFT_LDS_BYTES))) return rc;
+    if ((rc = set_lds(cmux_chain_kernel<GD, false>, BR_FFT_LDS_BYTES))) return rc;
+    return set_lds(cmux_chain_kernel<GD, true>, BR_FFT_LDS_BYTES);
 }
 int set_kernel_attrs(const iyk_params& p, bool use_fp, int split)
 {
@@ -2146,6 +2148,97 @@ int iyk_hip_cmux_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_s
         return (int)IYK_OK;
     });
     if (rc) return rc;
+    return release_stage(st);
+    IYK_API_END
+}
+
+namespace {
+
+// The independence contract of the chain and add batches, O(count): job g reads rows in_a[g] and in_b[g] and writes out[g].  No out may
+// be a row another job reads or writes; a job may write over what it reads itself, and jobs may share what they only read.
+int check_independent(uint64_t count, const int32_t* out, const int32_t* in_a, const int32_t* in_b)
+{
+    std::unordered_map<int32_t, uint64_t> writer;   // out row -> its job
+    writer.reserve(count * 2);
+    for (uint64_t g = 0; g < count; ++g)
+        if (!writer.emplace(out[g], g).second) return fail(IYK_ERR_INVALID, "two jobs of one batch write the same TRLWE row");
+    for (uint64_t g = 0; g < count; ++g)
+        for (const int32_t in : {in_a[g], in_b[g]}) {
+            const auto w = writer.find(in);
+            if (w != writer.end() && w->second != g) return fail(IYK_ERR_INVALID, "a job reads a TRLWE row that another job of the batch writes");
+        }
+    return IYK_OK;
+}
+
+}  // namespace
+
+int iyk_hip_cmux_chain_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
+                             uint64_t count, const int32_t* sel0, const int32_t* steps, const uint32_t* pattern, const int32_t* src,
+                             const int32_t* mem, const int32_t* out)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_cmux_chain_batch")) return rc;
+    if (!st || !d_trgsw || !d_trlwe || !sel0 || !steps || !pattern || !src || !mem || !out) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    if (count > (1u << 24)) return fail(IYK_ERR_INVALID, "batch too large");
+    if (trgsw_slots > (1ull << 24) || trlwe_slots > (1ull << 28)) return fail(IYK_ERR_INVALID, "store larger than an allocation can be");
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    std::vector<CmuxChainJob> jobs(count);
+    for (uint64_t g = 0; g < count; ++g) {
+        if (steps[g] < 1 || steps[g] > CMUX_CHAIN_MAX_STEPS) return fail(IYK_ERR_INVALID, "steps outside [1, 32]");
+        if (sel0[g] < 0 || (uint64_t)sel0[g] + (uint64_t)steps[g] > trgsw_slots)
+            return fail(IYK_ERR_INVALID, "selector slots sel0 .. sel0 + steps - 1 outside the selector store");
+        if (!slot_ok(src[g], trlwe_slots) || !slot_ok(mem[g], trlwe_slots) || !slot_ok(out[g], trlwe_slots))
+            return fail(IYK_ERR_INVALID, "TRLWE index outside the buffer");
+        jobs[g] = CmuxChainJob{sel0[g], steps[g], pattern[g], src[g], mem[g], out[g]};
+    }
+    if ((rc = check_independent(count, out, src, mem))) return rc;
+    const size_t bytes = jobs.size() * sizeof(CmuxChainJob);
+    size_t soff = 0;
+    if ((rc = acquire_stage(st, bytes, &soff))) return rc;
+    std::memcpy(st->h_stage + soff, jobs.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+    const Device& D = G.devs[st->gpu];
+    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
+        typedef decltype(gd) GD;
+        auto kern = G.debug ? cmux_chain_kernel<GD, true> : cmux_chain_kernel<GD, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((count + BR_WAVES - 1) / BR_WAVES)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s,
+                           (const CmuxChainJob*)(st->d_stage + soff), (int)count, (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
+        HIP_TRY(hipGetLastError());
+        return (int)IYK_OK;
+    });
+    if (rc) return rc;
+    return release_stage(st);
+    IYK_API_END
+}
+
+int iyk_hip_trlwe_add_batch(iyk_hip_stream* st, uint32_t* d_trlwe, uint64_t trlwe_slots, uint64_t count, const int32_t* a,
+                            const int32_t* b, const int32_t* out, uint32_t b0_offset)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    if (!st || !d_trlwe || !a || !b || !out) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    if (count > (1u << 24)) return fail(IYK_ERR_INVALID, "batch too large");
+    if (trlwe_slots > (1ull << 28)) return fail(IYK_ERR_INVALID, "store larger than an allocation can be");
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    std::vector<TrlweAddJob> jobs(count);
+    for (uint64_t g = 0; g < count; ++g) {
+        if (!slot_ok(a[g], trlwe_slots) || !slot_ok(b[g], trlwe_slots) || !slot_ok(out[g], trlwe_slots))
+            return fail(IYK_ERR_INVALID, "TRLWE index outside the buffer");
+        jobs[g] = TrlweAddJob{a[g], b[g], out[g]};
+    }
+    if ((rc = check_independent(count, out, a, b))) return rc;
+    const size_t bytes = jobs.size() * sizeof(TrlweAddJob);
+    size_t soff = 0;
+    if ((rc = acquire_stage(st, bytes, &soff))) return rc;
+    std::memcpy(st->h_stage + soff, jobs.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+    hipLaunchKernelGGL(trlwe_add_kernel, dim3((unsigned)count), dim3(256), 0, st->s, d_trlwe, (const TrlweAddJob*)(st->d_stage + soff),
+                       b0_offset);
+    HIP_TRY(hipGetLastError());
     return release_stage(st);
     IYK_API_END
 }

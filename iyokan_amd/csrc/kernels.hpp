@@ -902,6 +902,22 @@ __global__ __launch_bounds__(256) void sample_extract_index_kernel(const u32* __
     for (int j = threadIdx.x; j <= NTT_N; j += 256) out[j] = sample_extract_index_word(in, h, j);
 }
 
+// T[out] = T[a] + T[b] mod 2^32 on TRLWE rows, b0_offset added to coefficient 0 of the b polynomial: the tail of TFHEpp's HomMUXwoSE
+// (the sum of its two blind rotations, + mu).  One workgroup per job {a, b, out}; a word is read and written by the same thread, so
+// out may be a or b.
+struct TrlweAddJob {
+    int32_t a, b, out;
+};
+IYK_HD u32 trlwe_add_word(const u32* ra, const u32* rb, int j, u32 b0_offset) { return ra[j] + rb[j] + (j == NTT_N ? b0_offset : 0u); }
+__global__ __launch_bounds__(256) void trlwe_add_kernel(u32* trlwe, const TrlweAddJob* __restrict__ jobs, u32 b0_offset)
+{
+    const TrlweAddJob jb = jobs[blockIdx.x];
+    const u32* ra = trlwe + (size_t)jb.a * (2 * NTT_N);
+    const u32* rb = trlwe + (size_t)jb.b * (2 * NTT_N);
+    u32* out = trlwe + (size_t)jb.out * (2 * NTT_N);
+    for (int j = threadIdx.x; j < 2 * NTT_N; j += 256) out[j] = trlwe_add_word(ra, rb, j, b0_offset);
+}
+
 // ------------------------------------------------------------------------------------------
 // Identity key switch lvl1 -> lvl0 (TFHEpp IdentityKeySwitch<lvl10param>):
 //   out = (0,..,0,b') - sum_{i<N} sum_{j<t} KSK[i][j][v_ij - 1],  v_ij = digit j of (a'_i + prec)

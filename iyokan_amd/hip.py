@@ -36,7 +36,7 @@ EXPORTS = [
     "iyk_hip_trlwe_download", "iyk_hip_rotation_round", "iyk_hip_arena_sync_slots_multi", "iyk_hip_peer_access",
     "iyk_hip_build_id", "iyk_hip_host_alloc", "iyk_hip_host_free", "iyk_hip_init_profile",
     "iyk_hip_trgsw_alloc", "iyk_hip_trgsw_free", "iyk_hip_trgsw_upload", "iyk_hip_cmux_batch",
-    "iyk_hip_sample_extract_index_keyswitch_batch",
+    "iyk_hip_sample_extract_index_keyswitch_batch", "iyk_hip_cmux_chain_batch", "iyk_hip_trlwe_add_batch",
 ]
 
 
@@ -90,6 +90,8 @@ def lib():
         L.iyk_hip_trgsw_free.argtypes = [ctypes.c_int, _vp]
         L.iyk_hip_trgsw_upload.argtypes = [_vp, _vp, u64, u64, u64, _u32p]
         L.iyk_hip_cmux_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p, _i32p]
+        L.iyk_hip_cmux_chain_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _u32p, _i32p, _i32p, _i32p]
+        L.iyk_hip_trlwe_add_batch.argtypes = [_vp, _vp, u64, u64, _i32p, _i32p, _i32p, ctypes.c_uint32]
         L.iyk_hip_last_batch_timing.argtypes = [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.iyk_hip_resident_key_bytes.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
         L.iyk_hip_level_cost_ms.restype = ctypes.c_double
@@ -453,6 +455,27 @@ class Stream:
         p = lambda a: a.ctypes.data_as(_i32p)
         _check(lib().iyk_hip_cmux_batch(self.h, trgsw.ptr, trgsw.slots, trlwe.ptr, trlwe.slots, len(sel), p(sel), p(in0), p(in1),
                                         p(rot), p(out)), "iyk_hip_cmux_batch")
+
+    def cmux_chain_batch(self, trgsw, trlwe, sel0, steps, pattern, src, mem, out):
+        """len(sel0) independent chains of CMUXes on rows of a Trlwe store, asynchronous (the RAM write-back of one cell per job):
+        acc = T[src]; for j < steps, with S = selector slot sel0 + j: acc = T[mem] + S [.] (acc - T[mem]) where bit j of pattern is 1,
+        acc + S [.] (T[mem] - acc) where it is 0; T[out] = acc.  Word for word what `steps` dependent cmux_batch jobs give.  A job may
+        write over its own src or mem; no out may be the src / mem / out of another job of the batch."""
+        sel0, steps, src, mem, out = map(_i32, (sel0, steps, src, mem, out))
+        pattern = np.ascontiguousarray(pattern, dtype=np.uint32)
+        assert len(steps) == len(pattern) == len(src) == len(mem) == len(out) == len(sel0)
+        p = lambda a: a.ctypes.data_as(_i32p)
+        _check(lib().iyk_hip_cmux_chain_batch(self.h, trgsw.ptr, trgsw.slots, trlwe.ptr, trlwe.slots, len(sel0), p(sel0), p(steps),
+                                              pattern.ctypes.data_as(_u32p), p(src), p(mem), p(out)), "iyk_hip_cmux_chain_batch")
+
+    def trlwe_add_batch(self, trlwe, a, b, out, b0_offset=0):
+        """T[out] = T[a] + T[b] mod 2^32 on rows of a Trlwe store, b0_offset added to coefficient 0 of the b polynomial (the tail of
+        HomMUXwoSE with b0_offset = mu); asynchronous.  out may be a or b of its own job, never a row of another job."""
+        a, b, out = map(_i32, (a, b, out))
+        assert len(a) == len(b) == len(out)
+        p = lambda x: x.ctypes.data_as(_i32p)
+        _check(lib().iyk_hip_trlwe_add_batch(self.h, trlwe.ptr, trlwe.slots, len(a), p(a), p(b), p(out),
+                                             ctypes.c_uint32(int(b0_offset) & 0xFFFFFFFF)), "iyk_hip_trlwe_add_batch")
 
     def last_batch_timing(self):
         """(blind_rotate_ms, keyswitch_ms) of the most recent batch, from HIP events on this stream."""
