@@ -71,6 +71,17 @@ def sample_extract_index(row, h, N):
     return np.concatenate([ap, b[h : h + 1]]).astype(np.uint32)
 
 
+def rom_read(p, data, trgsw, addr_width, log2_word_bits):
+    """One ROM read through iyokan_amd.cmux.rom_read_plan with the exact CMUX: the result row (bit i of the word at coefficient i)."""
+    from iyokan_amd import cmux as plan
+
+    lay = plan.rom_layout(addr_width, log2_word_bits, p.N)
+    T = np.concatenate([data, np.zeros((lay.scratch_rows, 2 * p.N), dtype=np.uint32)])
+    for jobs in plan.rom_read_plan(addr_width, log2_word_bits, p.N):
+        run_jobs(p, T, trgsw, [(j.bit, j.in0, j.in1, j.rot, j.out) for j in jobs])
+    return T[lay.result]
+
+
 def emul():
     em = ctypes.CDLL(os.path.join(ROOT, "iyokan_amd", "lib", "libiyk_emul.so"))
     em.emu_cmux_fft.argtypes = [ctypes.c_int, _u32p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_double), ctypes.c_uint64, _i32p,

@@ -128,3 +128,13 @@ def clock(p, orc, cells, trgsw, wren, wdata, only_cells=None):
     for (d, i), row in zip(before, blind_rotate_many(orc, tlwes)):
         new[d][i] = row
     return rdata, before, new
+
+
+def run_clocks(p, orc, cells, clocks):
+    """clock() for every (addr, wren, wdata, selectors, [wren, wdata] TLWEs) of memory_cases.ram_case (one bit plane), in order.
+    Returns [(rdata, chain outputs before the refresh, cells after the clock)]."""
+    trace = []
+    for _, _, _, trgsw, cts in clocks:
+        rdata, before, cells = clock(p, orc, cells, trgsw, cts[0], cts[1:2])
+        trace.append((rdata, before, cells))
+    return trace

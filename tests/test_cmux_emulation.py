@@ -137,3 +137,25 @@ def test_index_extraction(em, case, h):
 
         want0 = nt.sample_extract0([T[1][: p.N].astype(np.uint64), T[1][p.N :].astype(np.uint64)], p.N)
         assert np.array_equal(out, np.asarray(want0).astype(np.uint32))
+
+
+def test_degenerate_jobs_and_last_slot(em, request):
+    """The cmux_batch cases of tests/cmux_cases.py (the words test_gpu_cmux_edges.py runs on the GPU): in0 == in1, rot = 0, a job on
+    the store's last selector slot, a batch whose jobs all use it.  The closed forms (a zero difference returns T[in0]) hold for
+    the reference first, then for the emulation."""
+    import cmux_cases
+
+    for which in SETS:
+        keys = request.getfixturevalue("keys" + which)
+        p = keys.params
+        trgsw, T, batches = cmux_cases.cmux_cases(keys)
+        spec = cmux_ref.spectra(em, p, trgsw)
+        want, got = T.copy(), T.copy()
+        for n, jobs in enumerate(batches):
+            cmux_ref.run_jobs(p, want, trgsw, jobs)
+            got = cmux_ref.emu_run(em, p, got, spec, trgsw.shape[0], jobs)
+            if n == 0:
+                for out, same in cmux_cases.CMUX_IDENTITIES:
+                    assert np.array_equal(want[out], T[same]) and np.array_equal(got[out], T[same]), (which, out, same)
+        assert np.array_equal(got, want), which
+        assert not np.array_equal(got[20], T[4])   # the last slot's selector did something

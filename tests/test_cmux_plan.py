@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import cmux_ref
+import memory_cases
 from iyokan_amd import client, cmux
 
 ADDR_WIDTH, LOG2_WORD_BITS = 10, 3          # 8 TRLWEs x 1024 bits, 8-bit words: 1024 words
@@ -74,3 +75,40 @@ def test_rom_read_decrypts_with_margin(keys128, rom):
         assert err.max() < p.mu // 2, (addr, err.max())
         assert np.array_equal((ph > 0).astype(int), want), addr
     print(f"ROM read: worst phase error 2^{np.log2(max(worst, 1)):.2f}, bound mu/2 = 2^{np.log2(p.mu // 2):.0f}")
+
+
+@pytest.mark.parametrize("which", ["128", "80"])
+@pytest.mark.parametrize("aw,lw", memory_cases.ROM_SHAPES)
+def test_rom_shapes_decrypt_with_margin(request, which, aw, lw):
+    """Companion of test_rom_read_decrypts_with_margin at the shapes it does not run: no upper tree, a one-level tree, a two-level
+    one, 1-bit words (2 levels + 10 rotate steps, the deepest plan) and 1024-bit words (no rotate step); addresses 0, 1, last and one
+    from the middle, through the exact reference.  Measured worst |phase error| over the 4 addresses x word bits, bound mu/2 = 2^28:
+        shape      128-bit set   80-bit set
+        (3, 3)     2^20.1        2^20.3
+        (8, 3)     2^20.3        2^21.0
+        (9, 3)     2^20.6        2^20.9
+        (12, 0)    2^19.9        2^20.9
+        (2, 10)    2^20.1        2^20.8
+    At (2, 10) every coefficient index h in [0, N) of cmux_ref.sample_extract_index is checked by decryption: the phase of the
+    extracted TLWE under the lvl1 key is exactly coefficient h of the TRLWE's phase."""
+    keys = request.getfixturevalue("keys" + which)
+    p = keys.params
+    bits, data, addresses, trgsw = memory_cases.rom_case(keys, aw, lw)
+    wb = 1 << lw
+    assert data.shape[0] == cmux.rom_layout(aw, lw, p.N).data_rows
+    s1 = keys.s1.astype(np.int64)
+    worst = 0
+    for r, addr in enumerate(addresses):
+        row = cmux_ref.rom_read(p, data, trgsw[r], aw, lw)
+        ph = client.trlwe_phases(keys, row[None])[0][:wb].view(np.int32).astype(np.int64)
+        want = bits[addr * wb : (addr + 1) * wb].astype(np.int64)
+        err = np.abs(ph - np.where(want == 1, int(p.mu), -int(p.mu)))
+        worst = max(worst, int(err.max()))
+        assert err.max() < p.mu // 2, (addr, err.max())
+        assert np.array_equal((ph > 0).astype(np.int64), want), addr
+        if wb == p.N:
+            for h in range(p.N):
+                t = cmux_ref.sample_extract_index(row, h, p.N).astype(np.int64)
+                phase = (int(t[p.N]) - int(t[: p.N] @ s1)) & cmux_ref.M32
+                assert phase == int(ph[h]) & cmux_ref.M32, (addr, h)
+    print(f"ROM read ({aw}, {lw}), {which}-bit set: worst phase error 2^{np.log2(max(worst, 1)):.2f}, bound mu/2 = 2^{np.log2(p.mu // 2):.0f}")

@@ -5,6 +5,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import cmux_cases
 import cmux_ref
 import ram_ref
 from iyokan_amd import client
@@ -119,3 +120,72 @@ def test_bad_jobs_are_refused(em, case):
         Tc = T.copy()
         assert ram_ref.emu_chain_rc(em, p, Tc, spec, slots, [job]) == -1, job
         assert np.array_equal(Tc, T)
+
+
+# ---- the chosen cases of tests/cmux_cases.py: the words the GPU runs in test_gpu_cmux_edges.py ------------------------------------
+
+
+@pytest.fixture(scope="module", params=SETS)
+def chosen(request, em):
+    """The 128-slot selector store of cmux_cases and its spectra, once per parameter set."""
+    keys = request.getfixturevalue("keys" + request.param)
+    trgsw = cmux_cases.selectors(keys)
+    return keys, cmux_ref.spectra(em, keys.params, trgsw)
+
+
+def _run_chosen(em, chosen, case):
+    """The case through emu_cmux_chain, batch by batch, against ram_ref.run_chains.  Returns (T, jobs of all batches, result)."""
+    keys, spec = chosen
+    p = keys.params
+    trgsw, T, batches = case
+    want, got = T.copy(), T.copy()
+    for jobs in batches:
+        ram_ref.run_chains(p, want, trgsw, jobs)
+        got = ram_ref.emu_chain_run(em, p, got, spec, trgsw.shape[0], jobs)
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert bad.size == 0, f"rows that differ from the reference: {bad[:10]}"
+    written = {j[5] for jobs in batches for j in jobs}
+    untouched = [r for r in range(T.shape[0]) if r not in written]
+    assert np.array_equal(got[untouched], T[untouched])
+    return T, [j for jobs in batches for j in jobs], got
+
+
+@pytest.mark.parametrize("steps", cmux_cases.A_STEPS)
+def test_long_chains(em, chosen, steps):
+    """case A: 8 (the RAM benchmark's shape), 16, 31 and 32 steps, pattern bits up to 31, sel0 + j up to the store's last slot"""
+    keys, spec = chosen
+    p = keys.params
+    case = cmux_cases.case_a(keys, steps)
+    T, jobs, got = _run_chosen(em, chosen, case)
+    if steps == 32:   # the same chains through emu_cmux_fft as dependent CMUX jobs
+        step_jobs = [s for g, j in enumerate(jobs) for s in ram_ref.chain_as_cmux_jobs(j, cmux_cases.accumulator_row(jobs, g))]
+        unfused = cmux_ref.emu_run(em, p, T, spec, case[0].shape[0], step_jobs)
+        written = sorted({j[5] for j in jobs})
+        assert np.array_equal(unfused[written], got[written])
+
+
+def test_mixed_steps(em, chosen):
+    """case B: steps 1 .. 32 side by side, the top used bit of every pattern set"""
+    _run_chosen(em, chosen, cmux_cases.case_b(chosen[0]))
+
+
+def test_many_jobs(em, chosen):
+    """case C cut to 17 jobs (the emulation has no workgroups; the GPU runs all 301)"""
+    _run_chosen(em, chosen, cmux_cases.case_c(chosen[0], count=17))
+
+
+def test_degenerate_chains(em, chosen):
+    """case D: src == mem and chains on zero selectors.  The closed forms hold for the REFERENCE first, then for the emulation."""
+    keys, _ = chosen
+    trgsw, T, batches = cmux_cases.case_d(keys)
+    want = ram_ref.run_chains(keys.params, T.copy(), trgsw, batches[0])
+    for out, same in cmux_cases.D_IDENTITIES:
+        assert np.array_equal(want[out], T[same]), (out, same)
+    _, _, got = _run_chosen(em, chosen, (trgsw, T, batches))
+    for out, same in cmux_cases.D_IDENTITIES:
+        assert np.array_equal(got[out], T[same]), (out, same)
+
+
+def test_dependent_batches(em, chosen):
+    """case E: twelve batches, each on the rows the one before wrote"""
+    _run_chosen(em, chosen, cmux_cases.case_e(chosen[0]))

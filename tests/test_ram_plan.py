@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import cmux_ref
+import memory_cases
 import ram_ref
 from iyokan_amd import client, cmux
 
@@ -128,3 +129,32 @@ def test_exact_reference_clock(keys128, oracle128):
         assert client.decrypt_ram_trlwe(keys, fresh[None])[0] == want, i
     print(f"RAM clock: read tree phase error 2^{np.log2(max(read_err, 1)):.2f}, worst chain output 2^{np.log2(max(worst, 1)):.2f}, "
           f"bound mu/2 = 2^{np.log2(mu // 2):.0f}")
+
+
+@pytest.mark.parametrize("which", ["128", "80"])
+@pytest.mark.parametrize("aw", memory_cases.RAM_SHAPES)
+def test_small_and_wide_rams(request, which, aw):
+    """ram_ref.clock at 2 x 1 (addr_width = 1: a one-job read tree that writes the result row directly, one-step chains) and 16 x 1,
+    two clocks each: a write of the complement of the addressed bit, then a wren = 0 read of the same address.  rdata and every cell
+    decrypt; the chain outputs before the refresh stay below mu/2 = 2^28.  Measured worst |phase error| at coefficient 0 of the chain
+    outputs over both clocks: 2^23.7 at both shapes and both sets (2^23.8 at 16 x 1 on the 80-bit set) — the noise of MUXwoSE's two
+    blind rotations in the written row, which one or four more CMUXes hardly move."""
+    keys, orc = request.getfixturevalue("keys" + which), request.getfixturevalue("oracle" + which)
+    p = keys.params
+    mu = int(p.mu)
+    content, cells, clocks = memory_cases.ram_case(keys, aw)
+    words = [int(b) for b in content]
+    worst = 0
+    trace = ram_ref.run_clocks(p, orc, cells, clocks)
+    for (addr, wren, wdata, _, _), (rdata, before, new) in zip(clocks, trace):
+        assert [int(b) for b in client.decrypt_bits(keys, rdata)] == [words[addr]]
+        if wren:
+            words[addr] = wdata
+        for (_, i), row in before.items():
+            ph = int(client.trlwe_phases(keys, row[None])[0][:1].view(np.int32)[0])
+            err = abs(ph - (mu if words[i] else -mu))
+            worst = max(worst, err)
+            assert err < mu // 2, (i, err)
+        assert [int(b) for b in client.decrypt_ram_trlwe(keys, new[0])] == words
+    assert words[clocks[0][0]] == 1 - int(content[clocks[0][0]])   # the write landed and the second clock's wdata did not
+    print(f"RAM {1 << aw} x 1, {which}-bit set: worst chain output phase error 2^{np.log2(max(worst, 1)):.2f}, bound mu/2 = 2^{np.log2(mu // 2):.0f}")
