@@ -315,6 +315,48 @@ int iyk_hip_cmux_chain_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t t
 int iyk_hip_trlwe_add_batch(iyk_hip_stream* st, uint32_t* d_trlwe, uint64_t trlwe_slots, uint64_t count, const int32_t* a,
                             const int32_t* b, const int32_t* out, uint32_t b0_offset);
 
+/* ---- private key switch: lvl2 TLWEs (64-bit torus) -> TRLWE rows -> TRGSW selector slots ----------------------------------------
+ * The second half of circuit bootstrapping (TaskTFHEppCB / CBInv / CBWithInv, /root/reference/src/iyokan_tfhepp.hpp:194-236, 384-407,
+ * in front of every ROMUX / RAMUX / RAMCMUXs port, :738-802): the server makes the selector slots of the CMUX memories from
+ * ciphertexts instead of taking them from the holder of the secret key.  The first half (lvl0 -> lvl2 blind rotation) is not here yet;
+ * it will write the lvl2 store below.  Integer only: available on every path, exact, order-free (sums mod 2^32).
+ *
+ * The key, one object per GPU: u32 [k+1][n_in+1][t][2^basebit - 1][k+1][N] — row K[c][i][j][u] is a lvl1 TRLWE (a(X), then b(X)) whose
+ * phase b - a s1 is (u+1) 2^(32 - (j+1) basebit) sigma_i f_c(X) + noise, sigma_i = s2[i] (i < n_in), sigma_{n_in} = -1, f_1 = 1, f_0 = -s1(X)
+ * (TFHEpp's PrivKeySwitchKey<lvl21param>: n_in = 2048, t = 10, basebit = 3, 2.35 GB).  n_in, t, basebit are run-time values of the key.
+ * _create refuses (IYK_ERR_INVALID) n_in = 0, basebit outside 1..8, basebit * t > 63; an allocation failure is IYK_ERR_HIP, leaves no
+ * state behind and touches no stream.  _upload copies rows [first_row, first_row + row_count) of the host layout before it returns
+ * (so a caller never holds more than a window of the key) and orders the transfer on st.  _key_bytes: device bytes of the live keys of
+ * one GPU. */
+int iyk_hip_privks_key_create(int gpu_index, uint32_t n_in, uint32_t t, uint32_t basebit, void** out);
+int iyk_hip_privks_key_upload(iyk_hip_stream* st, void* key, uint64_t first_row, uint64_t row_count, const uint32_t* host_rows);
+int iyk_hip_privks_key_free(void* key);
+int iyk_hip_privks_key_bytes(int gpu_index, uint64_t* out);
+/* TLWE lvl2 store: u64 [slots][n_in+1], a[0 .. n_in-1] then b (TFHEpp::TLWE<lvl2param>) — what the lvl0 -> lvl2 blind rotation will
+ * write.  upload / download move a contiguous range, ordered on the stream; the host buffer must stay valid until the stream is idle. */
+int iyk_hip_tlwe2_alloc(int gpu_index, uint32_t n_in, uint64_t slots, uint64_t** d_tlwe2_out);
+int iyk_hip_tlwe2_free(int gpu_index, uint64_t* d_tlwe2);
+int iyk_hip_tlwe2_upload(iyk_hip_stream* st, uint64_t* d_tlwe2, uint32_t n_in, uint64_t tlwe2_slots, uint64_t first, uint64_t count,
+                         const uint64_t* host_tlwe2);
+int iyk_hip_tlwe2_download(iyk_hip_stream* st, const uint64_t* d_tlwe2, uint32_t n_in, uint64_t tlwe2_slots, uint64_t first,
+                           uint64_t count, uint64_t* host_tlwe2);
+/* `count` independent key switches, asynchronous on st.  Job g, with w_i the words of TLWE in[g] of a store of the key's n_in,
+ * wbar_i = w_i + 2^(63 - basebit t) and d_j(w) = (wbar >> (64 - (j+1) basebit)) & (2^basebit - 1):
+ *     T[out[g]] = - sum_{i <= n_in} sum_{j < t, d_j(w_i) != 0} K[c[g]][i][j][d_j(w_i) - 1]      (mod 2^32, all 2N words)
+ * a TRLWE of phase f_c (b - <a, s2>) / 2^32: from a lvl2 TLWE of bit * 2^(64 - (r+1) Bgbit), row c l + r of the bit's TRGSW as
+ * iyk_hip_trgsw_upload takes it.  Replaces TFHEpp::PrivKeySwitch<lvl21param> inside CircuitBootstrappingFFT.  The i range of a job is
+ * split over workgroups whose partial sums meet by integer atomics in a row zeroed first: word for word the same whatever the split.
+ * The three arrays are host arrays, copied before return.  Checked on every call, in O(count): every index against the size stated,
+ * c in [0, k], no two jobs with the same out — a violation is IYK_ERR_INVALID and nothing is launched. */
+int iyk_hip_privks_batch(iyk_hip_stream* st, const void* key, const uint64_t* d_tlwe2, uint64_t tlwe2_slots, uint64_t count,
+                         const int32_t* in, const int32_t* c, uint32_t* d_trlwe, uint64_t trlwe_slots, const int32_t* out);
+/* The device-resident twin of iyk_hip_trgsw_upload: selector out_slot[g] is made by the same transform from the (k+1) l torus-domain
+ * rows rows[g][0 .. (k+1) l - 1] of a TRLWE store, in row order c l + r (they are gathered into scratch of the stream first).
+ * Asynchronous on st, host arrays copied before return.  A duplicate out_slot or an index outside its store is IYK_ERR_INVALID and
+ * nothing is launched; IYK_ERR_STATE off the FFT path. */
+int iyk_hip_trgsw_from_rows(iyk_hip_stream* st, void* d_trgsw, uint64_t trgsw_slots, uint64_t count, const int32_t* out_slot,
+                            const uint32_t* d_trlwe, uint64_t trlwe_slots, const int32_t* rows /* [count][(k+1) l] */);
+
 /* Kernel-only time of the most recent iyk_hip_gate_batch on this stream, from HIP events
  * recorded on the stream around the blind-rotate and key-switch launches (milliseconds).
  * Blocks until those events have completed. */

@@ -36,6 +36,12 @@ def _lib():
         lib.iyk_client_encrypt_trlwe.argtypes = [ctypes.POINTER(IykParams), _u32p, ctypes.c_uint64, ctypes.c_int, _u32p,
                                                  ctypes.c_uint64, _u32p]
         lib.iyk_client_trlwe_phases.argtypes = [ctypes.POINTER(IykParams), _u32p, _u32p, ctypes.c_uint64, _u32p]
+        u64, _u64p = ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)
+        lib.iyk_client_keygen_lvl2.argtypes = [ctypes.c_uint32, u64, ctypes.c_int, _u32p]
+        lib.iyk_client_encrypt_tlwe2.argtypes = [ctypes.c_uint32, _u32p, u64, ctypes.c_int, ctypes.c_double, _u64p, u64, _u64p]
+        lib.iyk_client_tlwe2_phases.argtypes = [ctypes.c_uint32, _u32p, _u64p, u64, _u64p]
+        lib.iyk_client_privks_key_rows.argtypes = [ctypes.POINTER(IykParams), _u32p, ctypes.c_uint32, _u32p, ctypes.c_uint32,
+                                                   ctypes.c_uint32, u64, u64, u64, ctypes.c_int, ctypes.c_int, _u32p]
         _LIB = lib
     return _LIB
 
@@ -153,3 +159,71 @@ def trivial(params: IykParams, bit: int) -> np.ndarray:
     out = np.zeros(params.n + 1, dtype=np.uint32)
     _lib().iyk_client_trivial(ctypes.byref(params), int(bit), _p32(out))
     return out
+
+
+# ---- lvl2 (64-bit torus) and the private key-switching key: the client side of circuit bootstrapping's second half ----------------
+_u64p = ctypes.POINTER(ctypes.c_uint64)
+MAX_THREADS = 16   # row generation never starts more threads than this, whatever the machine has
+
+
+def _threads():
+    try:
+        return max(1, min(MAX_THREADS, len(os.sched_getaffinity(0))))
+    except AttributeError:
+        return 1
+
+
+def keygen_lvl2(n_in, seed=None) -> np.ndarray:
+    """A binary lvl2 secret key s2: u32 [n_in], one word per bit (TFHEpp's key.lvl2 has n_in = 2048)."""
+    s2 = np.zeros(int(n_in), dtype=np.uint32)
+    _lib().iyk_client_keygen_lvl2(int(n_in), 0 if seed is None else int(seed), int(seed is not None), _p32(s2))
+    return s2
+
+
+def encrypt_tlwe2(s2, msgs_u64, alpha, seed=None) -> np.ndarray:
+    """TLWE lvl2 of 64-bit torus messages -> u64 [count][n_in + 1]: a, then b = msg + <a, s2> + Gaussian noise of deviation alpha."""
+    s2 = np.ascontiguousarray(s2, dtype=np.uint32)
+    msgs = np.ascontiguousarray(np.asarray(msgs_u64, dtype=np.uint64).ravel())
+    out = np.zeros((msgs.size, s2.size + 1), dtype=np.uint64)
+    _lib().iyk_client_encrypt_tlwe2(s2.size, _p32(s2), 0 if seed is None else int(seed), int(seed is not None), float(alpha),
+                                    msgs.ctypes.data_as(_u64p), msgs.size, out.ctypes.data_as(_u64p))
+    return out
+
+
+def tlwe2_phases(s2, ct) -> np.ndarray:
+    """b - <a, s2> of TLWE lvl2 rows -> u64 [count]."""
+    s2 = np.ascontiguousarray(s2, dtype=np.uint32)
+    ct = np.ascontiguousarray(ct, dtype=np.uint64).reshape(-1, s2.size + 1)
+    out = np.zeros(ct.shape[0], dtype=np.uint64)
+    _lib().iyk_client_tlwe2_phases(s2.size, _p32(s2), ct.ctypes.data_as(_u64p), ct.shape[0], out.ctypes.data_as(_u64p))
+    return out
+
+
+def privks_key_total_rows(params, n_in, t, basebit):
+    return (params.k + 1) * (int(n_in) + 1) * int(t) * ((1 << int(basebit)) - 1)
+
+
+def privks_key_rows(keys: KeySet, s2, t, basebit, first_row=0, row_count=None, seed=None, nthreads=None) -> np.ndarray:
+    """Rows [first_row, first_row + row_count) of the private key-switching key lvl2 -> lvl1, host layout
+    u32 [k+1][n_in+1][t][2^basebit-1][k+1][N] flattened over its first four axes -> (row_count, 2N).  Row (c, i, j, u) is a TRLWE of
+    zero (noise alpha1) plus sigma_i (u+1) 2^(32 - (j+1) basebit) at coefficient 0 of polynomial c, sigma_i = s2[i], sigma_{n_in} = -1.
+    Any window gives the same words as the whole key (an int seed), so a full-size key (2.35 GB) is made and uploaded in chunks."""
+    s2 = np.ascontiguousarray(s2, dtype=np.uint32)
+    p = keys.params
+    total = privks_key_total_rows(p, s2.size, t, basebit)
+    row_count = total - first_row if row_count is None else int(row_count)
+    out = np.zeros((row_count, 2 * p.N), dtype=np.uint32)
+    rc = _lib().iyk_client_privks_key_rows(ctypes.byref(p), _p32(keys.s1), s2.size, _p32(s2), int(t), int(basebit), int(first_row),
+                                           row_count, 0 if seed is None else int(seed), int(seed is not None),
+                                           _threads() if nthreads is None else int(nthreads), _p32(out))
+    if rc != 0:
+        raise ValueError(f"iyk_client_privks_key_rows refused its arguments ({rc})")
+    return out
+
+
+def encrypt_cb_digits(s2, bits, params, alpha, seed=None) -> np.ndarray:
+    """What the lvl0 -> lvl2 rotation of circuit bootstrapping outputs, made by the key holder instead: per bit the l TLWE lvl2 of
+    bit * 2^(64 - (r+1) Bgbit), r < l -> u64 [len(bits) * l][n_in + 1], TLWE bit * l + r = gadget digit r of that bit."""
+    bits = np.asarray(bits, dtype=np.uint64).ravel()
+    msgs = np.array([[int(b) << (64 - (r + 1) * params.Bgbit) for r in range(params.l)] for b in bits], dtype=np.uint64)
+    return encrypt_tlwe2(s2, msgs.ravel(), alpha, seed)

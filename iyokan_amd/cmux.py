@@ -60,6 +60,31 @@ def rom_read_plan(addr_width, log2_word_bits, N):
     return launches   # empty for a one-word ROM: nothing to select
 
 
+def selectors_from_tlwe2(stream, key, tlwe2, first, addr_width, trlwe_scratch, trgsw, first_slot=0):
+    """The selectors of a whole address from ciphertexts, on the device: TLWE lvl2 slot first + bit l + r of `tlwe2` holds gadget digit r
+    of address bit `bit` (bit * 2^(64 - (r+1) Bgbit): client.encrypt_cb_digits, later the lvl0 -> lvl2 rotation).  ONE privks_batch of
+    addr_width (k+1) l key switches into rows 0 .. of `trlwe_scratch` (row (bit (k+1) + c) l + r), then ONE trgsw_from_rows into
+    selector slots first_slot .. first_slot + addr_width - 1 of `trgsw`.  Replaces the second half of the reference's TaskTFHEppCB in
+    front of a ROM / RAM port (/root/reference/src/iyokan_tfhepp.hpp:194-236).  Asynchronous on the stream."""
+    from . import hip
+
+    p = hip.current_params()
+    l, k1 = int(p.l), int(p.k) + 1
+    per = k1 * l
+    if trlwe_scratch.slots < addr_width * per:
+        raise ValueError(f"{addr_width * per} scratch rows needed, the store has {trlwe_scratch.slots}")
+    in_, c, out = [], [], []
+    for bit in range(addr_width):
+        for cc in range(k1):
+            for r in range(l):
+                in_.append(first + bit * l + r)
+                c.append(cc)
+                out.append(bit * per + cc * l + r)
+    stream.privks_batch(key, tlwe2, in_, c, trlwe_scratch, out)
+    stream.trgsw_from_rows(trgsw, np.arange(first_slot, first_slot + addr_width), trlwe_scratch,
+                           np.arange(addr_width * per).reshape(addr_width, per))
+
+
 class Rom:
     """A ROM of TRLWE rows on one GPU.  read() runs rom_read_plan for R independent reads at once: the jobs of all reads at one
     level go into ONE cmux_batch, each read with its own scratch rows and its own addr_width selectors; then bit i of every read's
@@ -102,15 +127,21 @@ class Rom:
             out.append(tuple(cols))
         return out
 
-    def read(self, addr_trgsw, arena, out_slots):
+    def read(self, addr_trgsw, arena, out_slots, resident=False):
         """addr_trgsw: u32 [R][addr_width][(k+1) l][k+1][N] (client.encrypt_trgsw of every read's address bits, bit 0 first);
-        out_slots: [R][word_bits] arena slots.  Asynchronous on the stream."""
-        sel = np.ascontiguousarray(addr_trgsw, dtype=np.uint32).reshape(-1, self.addr_width, self.trgsw.words)
-        reads = sel.shape[0]
-        out_slots = np.asarray(out_slots, dtype=np.int32).reshape(reads, self.word_bits)
+        out_slots: [R][word_bits] arena slots.  Asynchronous on the stream.  resident=True: the selectors are in self.trgsw already
+        (slot read * addr_width + bit, e.g. from selectors_from_tlwe2 on this stream): addr_trgsw is ignored and nothing is uploaded."""
+        if resident:
+            out_slots = np.asarray(out_slots, dtype=np.int32).reshape(-1, self.word_bits)
+            reads = out_slots.shape[0]
+        else:
+            sel = np.ascontiguousarray(addr_trgsw, dtype=np.uint32).reshape(-1, self.addr_width, self.trgsw.words)
+            reads = sel.shape[0]
+            out_slots = np.asarray(out_slots, dtype=np.int32).reshape(reads, self.word_bits)
         if reads > self.max_reads:
             raise ValueError(f"{reads} reads, sized for {self.max_reads}")
-        self.trgsw.upload(self.stream, 0, sel)
+        if not resident:
+            self.trgsw.upload(self.stream, 0, sel)
         for args in self.launches(reads):
             self.stream.cmux_batch(self.trgsw, self.trlwe, *args)
         rows = np.repeat([self.row(r, self.layout.result) for r in range(reads)], self.word_bits)
@@ -208,16 +239,18 @@ class Ram:
         C = self.cells_per_plane
         return [j for d in range(self.data_width) for j in ram_write_jobs(self.addr_width, self.mux_rows(d)[0], d * C)]
 
-    def clock(self, addr_trgsw, arena, wren_slot, wdata_slots, rdata_slots, fused=True):
+    def clock(self, addr_trgsw, arena, wren_slot, wdata_slots, rdata_slots, fused=True, resident=False):
         """One clock of the reference's RAM network, asynchronous on the stream.  addr_trgsw: u32 [addr_width][(k+1) l][k+1][N]
         (client.encrypt_trgsw of the address bits, bit 0 first); arena holds the TLWEs of wren (one slot) and wdata (data_width
         slots) and receives rdata (data_width slots, the addressed word BEFORE the write).  fused=False sends the write-back as
-        addr_width cmux_batch launches instead of one cmux_chain_batch: the same words."""
+        addr_width cmux_batch launches instead of one cmux_chain_batch: the same words.  resident=True: the addr_width selectors are in
+        self.trgsw already (e.g. from selectors_from_tlwe2 on this stream): addr_trgsw is ignored and nothing is uploaded."""
         st, w, C = self.stream, self.data_width, self.cells_per_plane
         wdata_slots, rdata_slots = np.asarray(wdata_slots, dtype=np.int32).ravel(), np.asarray(rdata_slots, dtype=np.int32).ravel()
         if len(wdata_slots) != w or len(rdata_slots) != w:
             raise ValueError(f"expected {w} wdata and {w} rdata slots")
-        self.trgsw.upload(st, 0, np.ascontiguousarray(addr_trgsw, dtype=np.uint32).reshape(self.addr_width, self.trgsw.words))
+        if not resident:
+            self.trgsw.upload(st, 0, np.ascontiguousarray(addr_trgsw, dtype=np.uint32).reshape(self.addr_width, self.trgsw.words))
         # 1, 2: RAMUX, SEI(0) + key switch -> rdata
         for args in self.read_launches():
             st.cmux_batch(self.trgsw, self.trlwe, *args)

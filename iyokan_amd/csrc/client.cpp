@@ -19,13 +19,18 @@
 //   TLWE lvl0      u32[n+1]                      a[0..n-1], b = a[n]
 //   BK (torus)     u32[n][(k+1)l][k+1][N]        row r = c*l + j: TRLWE(0) + s0[i]*2^(32-(j+1)Bgbit) on poly c, coeff 0
 //   KSK            u32[kN][t][2^basebit-1][n+1]  TLWE0( s1[i] * v * 2^(32-(j+1)basebit) ), v = idx+1
+//   TLWE lvl2      u64[n_in+1]                   a[0..n_in-1], b = a[n_in]: 64-bit torus (the output level of circuit bootstrapping's rotation)
+//   private KSK    u32[k+1][n_in+1][t][2^basebit-1][k+1][N]   row (c, i, j, u): TRLWE(0) + sigma_i (u+1) 2^(32-(j+1)basebit) on poly c,
+//                                                coeff 0; sigma_i = s2[i], sigma_{n_in} = -1 (phase: f_c = 1 for c = 1, -s1(X) for c = 0)
 #include <sys/random.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <thread>
 #include <vector>
 
 #include "../../include/iyokan_hip_params.h"
@@ -249,6 +254,81 @@ int iyk_client_trivial(const iyk_params* p, int bit, uint32_t* out)
 {
     std::memset(out, 0, sizeof(uint32_t) * (p->n + 1));
     out[p->n] = bit ? p->mu : 0u - p->mu;
+    return 0;
+}
+
+// ---- lvl2 (64-bit torus) and the private key-switching key: the client side of circuit bootstrapping's second half ----------------
+
+// binary lvl2 key, one u32 per bit
+int iyk_client_keygen_lvl2(uint32_t n_in, uint64_t seed, int deterministic, uint32_t* s2)
+{
+    Rng rng(seed, deterministic);
+    for (uint32_t i = 0; i < n_in; ++i) s2[i] = rng.u32() & 1u;
+    return 0;
+}
+
+// TLWE lvl2 of 64-bit torus messages: b = msg + <a, s2> + e, e Gaussian of standard deviation alpha (in units of the torus)
+int iyk_client_encrypt_tlwe2(uint32_t n_in, const uint32_t* s2, uint64_t seed, int deterministic, double alpha, const uint64_t* msgs,
+                             uint64_t count, uint64_t* out)
+{
+    Rng rng(seed, deterministic);
+    for (uint64_t g = 0; g < count; ++g) {
+        uint64_t* ct = out + g * ((uint64_t)n_in + 1);
+        double d = rng.gauss(alpha);
+        d -= std::rint(d);                                                  // [-1/2, 1/2]
+        uint64_t b = msgs[g] + ((uint64_t)(int64_t)std::ldexp(d, 63) << 1);   // * 2^64 without leaving int64
+        for (uint32_t i = 0; i < n_in; ++i) {
+            ct[i] = rng.next();
+            if (s2[i]) b += ct[i];
+        }
+        ct[n_in] = b;
+    }
+    return 0;
+}
+
+int iyk_client_tlwe2_phases(uint32_t n_in, const uint32_t* s2, const uint64_t* ct, uint64_t count, uint64_t* phases)
+{
+    for (uint64_t g = 0; g < count; ++g) {
+        const uint64_t* c = ct + g * ((uint64_t)n_in + 1);
+        uint64_t ph = c[n_in];
+        for (uint32_t i = 0; i < n_in; ++i)
+            if (s2[i]) ph -= c[i];
+        phases[g] = ph;
+    }
+    return 0;
+}
+
+// Rows [first_row, first_row + row_count) of the private key-switching key, host layout (row index = ((c (n_in+1) + i) t + j) nb + u,
+// nb = 2^basebit - 1).  Every row draws from a generator of its own — seeded from (seed, row index), or keyed from the OS — so a window
+// holds the same words however the key is cut into windows and whatever nthreads is.  Noise: alpha1.
+int iyk_client_privks_key_rows(const iyk_params* p, const uint32_t* s1, uint32_t n_in, const uint32_t* s2, uint32_t t, uint32_t basebit,
+                               uint64_t first_row, uint64_t row_count, uint64_t seed, int deterministic, int nthreads, uint32_t* out)
+{
+    if (!p || p->k != 1 || basebit < 1 || basebit > 8 || t == 0 || (uint64_t)basebit * t > 63 || n_in == 0) return -1;
+    const uint64_t nb = (1u << basebit) - 1, n1 = (uint64_t)n_in + 1, total = (p->k + 1) * n1 * t * nb;
+    if (first_row > total || row_count > total - first_row) return -1;
+    const uint32_t N = p->N;
+    auto work = [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t q = lo; q < hi; ++q) {
+            const uint64_t R = first_row + q;
+            const uint32_t u = (uint32_t)(R % nb), j = (uint32_t)(R / nb % t), i = (uint32_t)(R / nb / t % n1), c = (uint32_t)(R / nb / t / n1);
+            Rng rng(seed ^ (0xD1342543DE82EF95ull * (R + 1)), deterministic);
+            uint32_t* row = out + q * 2 * N;
+            trlwe_encrypt_zero(p, s1, rng, row, row + N);
+            const uint32_t sh = (j + 1) * basebit;                              // digits below the 32-bit torus carry no message
+            const uint32_t m = sh <= 32 ? (uint32_t)(((uint64_t)(u + 1) << (32 - sh)) & 0xFFFFFFFFu) : 0u;
+            if (i == n_in) row[c * N] -= m;
+            else if (s2[i]) row[c * N] += m;
+        }
+    };
+    const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)nthreads, 16, (int64_t)row_count}));
+    if (nt == 1) {
+        work(0, row_count);
+        return 0;
+    }
+    std::vector<std::thread> pool;
+    for (int k = 0; k < nt; ++k) pool.emplace_back(work, row_count * k / nt, row_count * (k + 1) / nt);
+    for (auto& th : pool) th.join();
     return 0;
 }
 

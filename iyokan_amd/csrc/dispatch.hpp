@@ -119,5 +119,25 @@ inline KsPlan ks_plan(int kind, int shared_max, int shared_wg, int njobs, int T,
     return plan(KS_FORM_KIND0, KS_KIND0_GATES, 64, 512);
 }
 
+// ---- private key switch (privks.hpp) --------------------------------------------------------------------------------------------
+
+constexpr int PRIVKS_WG_PER_CU = 4;   // workgroups of 256 lanes a launch aims to have per CU: 16 waves, each with up to PRIVKS_UNROLL rows in flight
+
+struct PrivksPlan {
+    int splits;        // workgroups per job: split s takes i in [s * i_per_split, min((s + 1) * i_per_split, n_words))
+    int i_per_split;   // >= 1; (splits - 1) * i_per_split < n_words <= splits * i_per_split: no split is empty, every i has one owner
+};
+// A job streams the rows of n_words = n_in + 1 input words.  A batch is a handful of jobs (address bits x l x (k+1)), so the i range of
+// every job is cut until the launch has ~PRIVKS_WG_PER_CU workgroups per CU, never finer than one word per workgroup.  The launch is
+// 1-D: workgroup b is split b % splits of job b / splits.
+inline PrivksPlan privks_plan(int njobs, int n_words, int cus)
+{
+    const long want = (long)PRIVKS_WG_PER_CU * std::max(1, cus);
+    long s = (want + njobs - 1) / std::max(1, njobs);
+    s = std::min<long>(std::max<long>(s, 1), n_words);
+    const int per = (int)((n_words + s - 1) / s);
+    return PrivksPlan{(n_words + per - 1) / per, per};
+}
+
 }  // namespace dispatch
 }  // namespace iyk

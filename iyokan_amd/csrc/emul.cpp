@@ -18,6 +18,7 @@
 #include "cmux_fft.hpp"
 #include "fft256.hpp"
 #include "dispatch.hpp"
+#include "privks.hpp"
 
 using namespace iyk;
 
@@ -1123,5 +1124,19 @@ int iyk_emul_blind_rotate(const iyk_params* p, const uint32_t* lin, const uint64
     else if (p->l == 2 && p->Bgbit == 10) blind_rotate<2, 10>(p, lin, bk_ntt, tlwe1);
     else return -1;
     return 0;
+}
+/* privks_plan: splits and words per split of a private key-switch launch */
+void iyk_emul_privks_plan(int njobs, int n_words, int cus, int out[2])
+{
+    const dispatch::PrivksPlan k = dispatch::privks_plan(njobs, n_words, cus);
+    out[0] = k.splits, out[1] = k.i_per_split;
+}
+/* privks.hpp's digits of `count` 64-bit words as privks_kernel takes them: digits[count][t] */
+void iyk_emul_privks_digits(const uint64_t* w, int count, uint32_t t, uint32_t basebit, uint32_t* digits)
+{
+    for (int g = 0; g < count; ++g) {
+        const u64 wbar = privks_round(w[g], t, basebit);
+        for (uint32_t j = 0; j < t; ++j) digits[(size_t)g * t + j] = privks_digit(wbar, j, basebit);
+    }
 }
 }

@@ -41,6 +41,7 @@
 #define IYK_BUILD_ID_SUFFIX ""
 #endif
 #include "cmux_fft.hpp"
+#include "privks.hpp"
 
 using namespace iyk;
 using namespace iyk::dispatch;
@@ -90,6 +91,7 @@ struct Device {
     unsigned long long* fft_err = nullptr;  // IYK_HIP_DEBUG: largest |z - rint(z)| seen by the FFT kernel (bits of a double)
     iyk_level_cost cost{};         // what a level of r rotations costs on this GPU (iyk_hip_level_cost_table); read / written under G.mu
     struct GateCoalescer* co = nullptr;   // lazily created by iyk_hip_gate_host (one per GPU); freed by iyk_hip_cleanup
+    uint64_t privks_bytes = 0;     // device memory of the live private key-switch keys of this GPU (iyk_hip_privks_key_*): __atomic adds
     int max_passes = 0;            // cost.max_passes as the dispatch reads it: __atomic loads / stores, lock-free (a calibration may run
                                    // beside a batch; a plain int keeps Device copyable)
     void release()
@@ -157,6 +159,7 @@ struct Global {
     uint64_t field_key_bytes = 0;
     uint64_t ks_lut_bytes = 0;   // the pre-added key-switch rows, once built (ensure_ks_lut)
     std::mutex field_mu;
+    uint64_t generation = 0;     // counts iyk_hip_init: a private key-switch key freed after a re-initialisation leaves the new counters alone
 } G;
 
 }  // namespace
@@ -179,6 +182,8 @@ struct iyk_hip_stream {
     hipEvent_t stage_free[STAGE_RING] = {};  // work reading slot k done
     hipEvent_t xfer = nullptr, xfer2 = nullptr;  // cross-stream hand-offs of iyk_hip_arena_sync_slots
     // blind-rotation outputs (TLWE lvl1), one row per rotation job
+    u32* d_sel = nullptr;   // iyk_hip_trgsw_from_rows: the gathered torus rows of the selectors of one call, sel_cap selectors
+    size_t sel_cap = 0;
     u32* d_rot = nullptr;
     u32* d_abar = nullptr;  // mod-switched rotation inputs, one row of ABAR_STRIDE words per job
     size_t rot_cap = 0;
@@ -602,6 +607,7 @@ void destroy_stream_resources(iyk_hip_stream* st)
     if (st->d_stage) (void)hipFree(st->d_stage);
     if (st->d_rot) (void)hipFree(st->d_rot);
     if (st->d_abar) (void)hipFree(st->d_abar);
+    if (st->d_sel) (void)hipFree(st->d_sel);
     if (st->d_scratch) (void)hipFree(st->d_scratch);
     if (st->h_gate) (void)hipHostFree(st->h_gate);
     for (hipEvent_t e : st->stage_free)
@@ -1209,6 +1215,7 @@ int iyk_hip_init(int ngpu, const int* device_ids, const iyk_params* params, cons
                   G.bk_fft_bytes;
     if (use_fft) G.bk_torus_host.assign(bk_torus, bk_torus + bk_words);
     else G.bk_torus_host.clear();
+    ++G.generation;
     G.init.store(true);
     return IYK_OK;
     IYK_API_END
@@ -2274,6 +2281,224 @@ int iyk_hip_sample_extract_index_keyswitch_batch(iyk_hip_stream* st, const uint3
                        (const int32_t*)(st->d_stage + soff + idx_off), (const int32_t*)(st->d_stage + soff + idx_off + idx_bytes), st->d_rot);
     HIP_TRY(hipGetLastError());
     if ((rc = launch_keyswitch(st, d_arena, (const KsJob*)(st->d_stage + soff), (int)count))) return rc;
+    return release_stage(st);
+    IYK_API_END
+}
+
+/* ---- private key switch: lvl2 TLWEs -> TRLWE rows -> TRGSW selector slots ------------------------------------------------- */
+
+namespace {
+
+struct PrivksKey {
+    int gpu = 0;
+    u32 n_in = 0, t = 0, basebit = 0;
+    uint64_t rows = 0;        // (k+1) (n_in+1) t (2^basebit - 1) rows of 2N words
+    uint64_t bytes = 0;
+    uint64_t generation = 0;  // G.generation at create
+    u32* d = nullptr;
+};
+constexpr uint64_t PRIVKS_UPLOAD_CHUNK = 256;   // key rows per staging slot (2 MiB)
+constexpr u32 PRIVKS_MAX_N_IN = 1u << 16;
+
+int ensure_sel(iyk_hip_stream* st, size_t selectors, size_t words_per_selector)
+{
+    if (selectors <= st->sel_cap) return IYK_OK;
+    HIP_TRY(hipStreamSynchronize(st->s));   // work of an earlier call may still read the smaller buffer
+    if (st->d_sel) HIP_TRY(hipFree(st->d_sel));
+    st->d_sel = nullptr;
+    st->sel_cap = 0;
+    const size_t cap = selectors + selectors / 2 + 2;
+    HIP_TRY(hipMalloc((void**)&st->d_sel, cap * words_per_selector * sizeof(u32)));
+    st->sel_cap = cap;
+    return IYK_OK;
+}
+
+}  // namespace
+
+int iyk_hip_privks_key_create(int gpu_index, uint32_t n_in, uint32_t t, uint32_t basebit, void** out)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    if (!out) return fail(IYK_ERR_INVALID, "null out");
+    if (n_in == 0 || n_in > PRIVKS_MAX_N_IN) return fail(IYK_ERR_INVALID, "n_in outside [1, 65536]");
+    if (basebit < 1 || basebit > 8) return fail(IYK_ERR_INVALID, "basebit outside [1, 8]");
+    if (t == 0 || (uint64_t)basebit * t > 63) return fail(IYK_ERR_INVALID, "basebit * t outside [1, 63]");
+    int rc = set_device(gpu_index);
+    if (rc) return rc;
+    const uint64_t rows = (uint64_t)(G.p.k + 1) * ((uint64_t)n_in + 1) * t * ((1u << basebit) - 1u);
+    const uint64_t bytes = rows * 2 * NTT_N * sizeof(u32);
+    u32* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();   // an allocation failure is not sticky: leave no pending error behind
+        return fail(IYK_ERR_HIP, std::string("hipMalloc of the private key-switch key (") + std::to_string(bytes) + " bytes): " + hipGetErrorString(e));
+    }
+    PrivksKey* key = new (std::nothrow) PrivksKey();
+    if (!key) {
+        (void)hipFree(d);
+        return fail(IYK_ERR_NOMEM, "out of host memory");
+    }
+    key->gpu = gpu_index, key->n_in = n_in, key->t = t, key->basebit = basebit;
+    key->rows = rows, key->bytes = bytes, key->generation = G.generation, key->d = d;
+    __atomic_fetch_add(&G.devs[gpu_index].privks_bytes, bytes, __ATOMIC_RELAXED);
+    *out = key;
+    return IYK_OK;
+    IYK_API_END
+}
+
+int iyk_hip_privks_key_free(void* key_)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    PrivksKey* key = (PrivksKey*)key_;
+    if (!key) return IYK_OK;
+    int rc = set_device(key->gpu);
+    if (rc) return rc;
+    HIP_TRY(hipFree(key->d));
+    if (key->generation == G.generation) __atomic_fetch_sub(&G.devs[key->gpu].privks_bytes, key->bytes, __ATOMIC_RELAXED);
+    delete key;
+    return IYK_OK;
+    IYK_API_END
+}
+
+int iyk_hip_privks_key_bytes(int gpu_index, uint64_t* out)
+{
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    if (!out) return fail(IYK_ERR_INVALID, "null out");
+    if (gpu_index < 0 || gpu_index >= (int)G.devs.size()) return fail(IYK_ERR_INVALID, "gpu_index out of range");
+    *out = __atomic_load_n(&G.devs[gpu_index].privks_bytes, __ATOMIC_RELAXED);
+    return IYK_OK;
+}
+
+int iyk_hip_privks_key_upload(iyk_hip_stream* st, void* key_, uint64_t first_row, uint64_t row_count, const uint32_t* host_rows)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    PrivksKey* key = (PrivksKey*)key_;
+    if (!st || !key || !host_rows) return fail(IYK_ERR_INVALID, "null argument");
+    if (st->gpu != key->gpu) return fail(IYK_ERR_INVALID, "the stream and the key are on different GPUs");
+    if (first_row > key->rows || row_count > key->rows - first_row) return fail(IYK_ERR_INVALID, "row range outside the key");
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    const size_t words = 2 * NTT_N;
+    for (uint64_t done = 0; done < row_count; done += PRIVKS_UPLOAD_CHUNK) {
+        const uint64_t c = std::min<uint64_t>(PRIVKS_UPLOAD_CHUNK, row_count - done);
+        const size_t bytes = (size_t)c * words * sizeof(u32);
+        size_t soff = 0;
+        if ((rc = acquire_stage(st, bytes, &soff))) return rc;
+        std::memcpy(st->h_stage + soff, host_rows + (size_t)done * words, bytes);   // the caller's rows are free on return
+        HIP_TRY(hipMemcpyAsync(key->d + (size_t)(first_row + done) * words, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+        if ((rc = release_stage(st))) return rc;
+    }
+    return IYK_OK;
+    IYK_API_END
+}
+
+int iyk_hip_tlwe2_alloc(int gpu_index, uint32_t n_in, uint64_t slots, uint64_t** out)
+{
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    if (!out || slots == 0 || slots > (1ull << 28) || n_in == 0 || n_in > PRIVKS_MAX_N_IN) return fail(IYK_ERR_INVALID, "bad argument");
+    int rc = set_device(gpu_index);
+    if (rc) return rc;
+    HIP_TRY(hipMalloc((void**)out, slots * ((uint64_t)n_in + 1) * sizeof(u64)));
+    return IYK_OK;
+}
+
+int iyk_hip_tlwe2_free(int gpu_index, uint64_t* d_tlwe2) { return iyk_hip_arena_free(gpu_index, (uint32_t*)d_tlwe2); }
+
+int iyk_hip_tlwe2_upload(iyk_hip_stream* st, uint64_t* d_tlwe2, uint32_t n_in, uint64_t tlwe2_slots, uint64_t first, uint64_t count,
+                         const uint64_t* host_tlwe2)
+{
+    if (n_in == 0 || n_in > PRIVKS_MAX_N_IN) return fail(IYK_ERR_INVALID, "n_in outside [1, 65536]");
+    return row_copy(st, d_tlwe2, host_tlwe2, 2 * ((size_t)n_in + 1), tlwe2_slots, first, count, true, hipMemcpyHostToDevice);
+}
+
+int iyk_hip_tlwe2_download(iyk_hip_stream* st, const uint64_t* d_tlwe2, uint32_t n_in, uint64_t tlwe2_slots, uint64_t first,
+                           uint64_t count, uint64_t* host_tlwe2)
+{
+    if (n_in == 0 || n_in > PRIVKS_MAX_N_IN) return fail(IYK_ERR_INVALID, "n_in outside [1, 65536]");
+    return row_copy(st, host_tlwe2, d_tlwe2, 2 * ((size_t)n_in + 1), tlwe2_slots, first, count, false, hipMemcpyDeviceToHost);
+}
+
+int iyk_hip_privks_batch(iyk_hip_stream* st, const void* key_, const uint64_t* d_tlwe2, uint64_t tlwe2_slots, uint64_t count,
+                         const int32_t* in, const int32_t* c, uint32_t* d_trlwe, uint64_t trlwe_slots, const int32_t* out)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    const PrivksKey* key = (const PrivksKey*)key_;
+    if (!st || !key || !d_tlwe2 || !in || !c || !d_trlwe || !out) return fail(IYK_ERR_INVALID, "null argument");
+    if (st->gpu != key->gpu) return fail(IYK_ERR_INVALID, "the stream and the key are on different GPUs");
+    if (count == 0) return IYK_OK;
+    if (count > (1u << 20)) return fail(IYK_ERR_INVALID, "batch too large");
+    if (tlwe2_slots > (1ull << 28) || trlwe_slots > (1ull << 28)) return fail(IYK_ERR_INVALID, "store larger than an allocation can be");
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    std::vector<PrivksJob> jobs(count);
+    std::unordered_map<int32_t, uint64_t> writer;   // out row -> its job
+    writer.reserve(count * 2);
+    for (uint64_t g = 0; g < count; ++g) {
+        if (!slot_ok(in[g], tlwe2_slots)) return fail(IYK_ERR_INVALID, "TLWE index outside the lvl2 store");
+        if (c[g] < 0 || c[g] > (int32_t)G.p.k) return fail(IYK_ERR_INVALID, "c outside [0, k]");
+        if (!slot_ok(out[g], trlwe_slots)) return fail(IYK_ERR_INVALID, "TRLWE index outside the buffer");
+        if (!writer.emplace(out[g], g).second) return fail(IYK_ERR_INVALID, "two jobs of one batch write the same TRLWE row");
+        jobs[g] = PrivksJob{in[g], c[g], out[g]};
+    }
+    const size_t bytes = jobs.size() * sizeof(PrivksJob);
+    size_t soff = 0;
+    if ((rc = acquire_stage(st, bytes, &soff))) return rc;
+    std::memcpy(st->h_stage + soff, jobs.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+    const PrivksJob* d_jobs = (const PrivksJob*)(st->d_stage + soff);
+    const PrivksPlan plan = privks_plan((int)count, (int)key->n_in + 1, G.devs[st->gpu].cus);
+    hipLaunchKernelGGL(privks_zero_kernel, dim3((unsigned)count), dim3(256), 0, st->s, d_jobs, d_trlwe);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(privks_kernel, dim3((unsigned)(count * (uint64_t)plan.splits)), dim3(256), 0, st->s, d_jobs, plan.splits,
+                       plan.i_per_split, (const u64*)d_tlwe2, key->n_in + 1, key->t, key->basebit, (const u32*)key->d, d_trlwe);
+    HIP_TRY(hipGetLastError());
+    return release_stage(st);
+    IYK_API_END
+}
+
+int iyk_hip_trgsw_from_rows(iyk_hip_stream* st, void* d_trgsw, uint64_t trgsw_slots, uint64_t count, const int32_t* out_slot,
+                            const uint32_t* d_trlwe, uint64_t trlwe_slots, const int32_t* rows)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_trgsw_from_rows")) return rc;
+    if (!st || !d_trgsw || !out_slot || !d_trlwe || !rows) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    if (trgsw_slots > (1ull << 24) || trlwe_slots > (1ull << 28)) return fail(IYK_ERR_INVALID, "store larger than an allocation can be");
+    if (count > trgsw_slots) return fail(IYK_ERR_INVALID, "more selectors than the store has slots");
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    const size_t per = (size_t)(G.p.k + 1) * G.p.l, polys = trgsw_polys(), words = polys * NTT_N;   // rows, polynomials, words of a selector
+    std::unordered_map<int32_t, uint64_t> writer;
+    writer.reserve(count * 2);
+    for (uint64_t g = 0; g < count; ++g) {
+        if (!slot_ok(out_slot[g], trgsw_slots)) return fail(IYK_ERR_INVALID, "selector index outside the selector store");
+        if (!writer.emplace(out_slot[g], g).second) return fail(IYK_ERR_INVALID, "two selectors of one call go to the same slot");
+        for (size_t r = 0; r < per; ++r)
+            if (!slot_ok(rows[g * per + r], trlwe_slots)) return fail(IYK_ERR_INVALID, "TRLWE index outside the buffer");
+    }
+    const Device& D = G.devs[st->gpu];
+    const size_t bytes = (size_t)count * per * sizeof(int32_t);
+    size_t soff = 0;
+    if ((rc = ensure_sel(st, count, words))) return rc;
+    if ((rc = acquire_stage(st, bytes, &soff))) return rc;
+    std::memcpy(st->h_stage + soff, rows, bytes);
+    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+    hipLaunchKernelGGL(trlwe_gather_rows_kernel, dim3((unsigned)(count * per)), dim3(256), 0, st->s, d_trlwe,
+                       (const int32_t*)(st->d_stage + soff), st->d_sel);
+    HIP_TRY(hipGetLastError());
+    for (uint64_t g = 0; g < count;) {   // one transform launch per run of consecutive destination slots
+        uint64_t e = g + 1;
+        while (e < count && out_slot[e] == out_slot[e - 1] + 1) ++e;
+        const size_t c = e - g;
+        fft::cplx* dst = (fft::cplx*)d_trgsw + (size_t)out_slot[g] * polys * 2 * fft::M;
+        hipLaunchKernelGGL(bk_fft_kernel, dim3((unsigned)(c * polys * 2)), dim3(64), 0, st->s, (const u32*)(st->d_sel + (size_t)g * words), dst,
+                           &D.fftc->c, c * polys);
+        HIP_TRY(hipGetLastError());
+        g = e;
+    }
     return release_stage(st);
     IYK_API_END
 }

@@ -17,6 +17,7 @@ from .params import IykParams, OPS
 _LIB = None
 _u32p = ctypes.POINTER(ctypes.c_uint32)
 _i32p = ctypes.POINTER(ctypes.c_int32)
+_u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libiyokan_hip.so")
@@ -37,6 +38,9 @@ EXPORTS = [
     "iyk_hip_build_id", "iyk_hip_host_alloc", "iyk_hip_host_free", "iyk_hip_init_profile",
     "iyk_hip_trgsw_alloc", "iyk_hip_trgsw_free", "iyk_hip_trgsw_upload", "iyk_hip_cmux_batch",
     "iyk_hip_sample_extract_index_keyswitch_batch", "iyk_hip_cmux_chain_batch", "iyk_hip_trlwe_add_batch",
+    "iyk_hip_privks_key_create", "iyk_hip_privks_key_upload", "iyk_hip_privks_key_free", "iyk_hip_privks_key_bytes",
+    "iyk_hip_tlwe2_alloc", "iyk_hip_tlwe2_free", "iyk_hip_tlwe2_upload", "iyk_hip_tlwe2_download", "iyk_hip_privks_batch",
+    "iyk_hip_trgsw_from_rows",
 ]
 
 
@@ -92,6 +96,17 @@ def lib():
         L.iyk_hip_cmux_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p, _i32p]
         L.iyk_hip_cmux_chain_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _u32p, _i32p, _i32p, _i32p]
         L.iyk_hip_trlwe_add_batch.argtypes = [_vp, _vp, u64, u64, _i32p, _i32p, _i32p, ctypes.c_uint32]
+        u32 = ctypes.c_uint32
+        L.iyk_hip_privks_key_create.argtypes = [ctypes.c_int, u32, u32, u32, ctypes.POINTER(_vp)]
+        L.iyk_hip_privks_key_upload.argtypes = [_vp, _vp, u64, u64, _u32p]
+        L.iyk_hip_privks_key_free.argtypes = [_vp]
+        L.iyk_hip_privks_key_bytes.argtypes = [ctypes.c_int, ctypes.POINTER(u64)]
+        L.iyk_hip_tlwe2_alloc.argtypes = [ctypes.c_int, u32, u64, ctypes.POINTER(_vp)]
+        L.iyk_hip_tlwe2_free.argtypes = [ctypes.c_int, _vp]
+        L.iyk_hip_tlwe2_upload.argtypes = [_vp, _vp, u32, u64, u64, u64, _u64p]
+        L.iyk_hip_tlwe2_download.argtypes = [_vp, _vp, u32, u64, u64, u64, _u64p]
+        L.iyk_hip_privks_batch.argtypes = [_vp, _vp, _vp, u64, u64, _i32p, _i32p, _vp, u64, _i32p]
+        L.iyk_hip_trgsw_from_rows.argtypes = [_vp, _vp, u64, u64, _i32p, _vp, u64, _i32p]
         L.iyk_hip_last_batch_timing.argtypes = [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.iyk_hip_resident_key_bytes.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
         L.iyk_hip_level_cost_ms.restype = ctypes.c_double
@@ -310,6 +325,67 @@ class Trgsw:
         self.ptr = None
 
 
+class PrivKsKey:
+    """Device-resident private key-switching key lvl2 -> lvl1 of one GPU: u32 [k+1][n_in+1][t][2^basebit-1][2N] (client.privks_key_rows),
+    uploaded in windows of rows."""
+
+    def __init__(self, n_in, t, basebit, gpu_index=0):
+        self.n_in, self.t, self.basebit, self.gpu_index = int(n_in), int(t), int(basebit), gpu_index
+        p = current_params()
+        self.words = 2 * p.N
+        self.rows = (p.k + 1) * (self.n_in + 1) * self.t * ((1 << self.basebit) - 1)
+        h = _vp()
+        _check(lib().iyk_hip_privks_key_create(gpu_index, self.n_in, self.t, self.basebit, ctypes.byref(h)), "iyk_hip_privks_key_create")
+        self.h = h
+
+    def upload(self, stream, first_row, host_rows):
+        """Rows first_row .. of the host layout; copied before return, ordered on the stream."""
+        host = np.ascontiguousarray(host_rows, dtype=np.uint32).reshape(-1, self.words)
+        _check(lib().iyk_hip_privks_key_upload(stream.h, self.h, int(first_row), host.shape[0], host.ctypes.data_as(_u32p)),
+               "iyk_hip_privks_key_upload")
+
+    def free(self):
+        if self.h:
+            _check(lib().iyk_hip_privks_key_free(self.h), "iyk_hip_privks_key_free")
+        self.h = None
+
+
+def privks_key_bytes(gpu=0):
+    """Device bytes of the live private key-switching keys of GPU `gpu`."""
+    v = ctypes.c_uint64()
+    _check(lib().iyk_hip_privks_key_bytes(int(gpu), ctypes.byref(v)), "iyk_hip_privks_key_bytes")
+    return v.value
+
+
+class Tlwe2:
+    """Device-resident TLWE lvl2 ciphertexts, u64 [slots][n_in + 1]: the inputs of Stream.privks_batch."""
+
+    def __init__(self, n_in, slots, gpu_index=0):
+        self.n_in, self.slots, self.gpu_index = int(n_in), int(slots), gpu_index
+        self.words = self.n_in + 1
+        ptr = _vp()
+        _check(lib().iyk_hip_tlwe2_alloc(gpu_index, self.n_in, self.slots, ctypes.byref(ptr)), "iyk_hip_tlwe2_alloc")
+        self.ptr = ptr.value
+
+    def upload(self, stream, first, host):
+        host = np.ascontiguousarray(host, dtype=np.uint64).reshape(-1, self.words)
+        _check(lib().iyk_hip_tlwe2_upload(stream.h, self.ptr, self.n_in, self.slots, first, host.shape[0], host.ctypes.data_as(_u64p)),
+               "iyk_hip_tlwe2_upload")
+        stream.sync()  # host buffer is pageable: finish before it can be garbage collected
+
+    def download(self, stream, first, count):
+        out = np.zeros((count, self.words), dtype=np.uint64)
+        _check(lib().iyk_hip_tlwe2_download(stream.h, self.ptr, self.n_in, self.slots, first, count, out.ctypes.data_as(_u64p)),
+               "iyk_hip_tlwe2_download")
+        stream.sync()
+        return out
+
+    def free(self):
+        if self.ptr:
+            _check(lib().iyk_hip_tlwe2_free(self.gpu_index, self.ptr), "iyk_hip_tlwe2_free")
+        self.ptr = None
+
+
 class Stream:
     """CUFHEStream equivalent (/root/reference/src/iyokan_cufhe.hpp:8-27)."""
 
@@ -476,6 +552,29 @@ class Stream:
         p = lambda x: x.ctypes.data_as(_i32p)
         _check(lib().iyk_hip_trlwe_add_batch(self.h, trlwe.ptr, trlwe.slots, len(a), p(a), p(b), p(out),
                                              ctypes.c_uint32(int(b0_offset) & 0xFFFFFFFF)), "iyk_hip_trlwe_add_batch")
+
+    def privks_batch(self, key, tlwe2, in_, c, trlwe, out):
+        """len(in_) private key switches, asynchronous: row out[g] of a Trlwe store = R_{c[g]} of TLWE in_[g] of a Tlwe2 store under a
+        PrivKsKey — a TRLWE of phase f_c (b - <a, s2>) / 2^32, f_1 = 1, f_0 = -s1(X).  No two jobs may write the same row."""
+        in_, c, out = map(_i32, (in_, c, out))
+        assert len(in_) == len(c) == len(out)
+        if tlwe2.n_in != key.n_in:
+            raise ValueError(f"the store holds TLWEs of n_in = {tlwe2.n_in}, the key switches n_in = {key.n_in}")
+        p = lambda a: a.ctypes.data_as(_i32p)
+        _check(lib().iyk_hip_privks_batch(self.h, key.h, tlwe2.ptr, tlwe2.slots, len(in_), p(in_), p(c), trlwe.ptr, trlwe.slots, p(out)),
+               "iyk_hip_privks_batch")
+
+    def trgsw_from_rows(self, trgsw, out_slot, trlwe, rows):
+        """Selector out_slot[g] of a Trgsw store from the (k+1) l torus-domain rows rows[g] of a Trlwe store (row order c l + r), on the
+        device: the twin of Trgsw.upload for rows that never were on the host.  Asynchronous."""
+        out_slot = _i32(out_slot).ravel()
+        rows = _i32(rows).reshape(len(out_slot), -1)
+        p = current_params()
+        if rows.shape[1] != (p.k + 1) * p.l:
+            raise ValueError(f"expected {(p.k + 1) * p.l} rows per selector, got {rows.shape[1]}")
+        q = lambda a: a.ctypes.data_as(_i32p)
+        _check(lib().iyk_hip_trgsw_from_rows(self.h, trgsw.ptr, trgsw.slots, len(out_slot), q(out_slot), trlwe.ptr, trlwe.slots, q(rows)),
+               "iyk_hip_trgsw_from_rows")
 
     def last_batch_timing(self):
         """(blind_rotate_ms, keyswitch_ms) of the most recent batch, from HIP events on this stream."""
