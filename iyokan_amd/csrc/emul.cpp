@@ -567,6 +567,30 @@ void fft_inverse_wave(fft::cplx (*a)[8], fft::cplx* xb)
     ALL_LANES fft::inv_p3(a[lane], C.u, &C.t1[0][lane]);
 }
 
+// kernels_fft.hpp::fft_inverse2: the lo and hi halves of one output polynomial through ONE exchange buffer, in the kernel's issue
+// order (every hand-off of A before the same hand-off of B), the lane's T2 and T1 columns fetched once and used by both halves
+void fft_inverse2_wave(fft::cplx (*a)[8], fft::cplx (*b)[8], fft::cplx* xb)
+{
+    const fft::Consts& C = fft_consts();
+    static thread_local fft::cplx w[64][7], tw[64][8];
+    ALL_LANES fft::inv_t2_load(w[lane], &C.t2t[0][lane & 7]);
+    ALL_LANES fft::inv_p1(a[lane], w[lane]);
+    ALL_LANES fft::x2_put_c(lane, a[lane], xb);
+    ALL_LANES fft::x2_get_b(lane, a[lane], xb);
+    ALL_LANES fft::inv_p1(b[lane], w[lane]);
+    ALL_LANES fft::x2_put_c(lane, b[lane], xb);
+    ALL_LANES fft::x2_get_b(lane, b[lane], xb);
+    ALL_LANES fft::inv_p2(a[lane]);
+    ALL_LANES fft::x1_put_b(lane, a[lane], xb);
+    ALL_LANES fft::x1_get_a(lane, a[lane], xb);
+    ALL_LANES fft::inv_p2(b[lane]);
+    ALL_LANES fft::x1_put_b(lane, b[lane], xb);
+    ALL_LANES fft::x1_get_a(lane, b[lane], xb);
+    ALL_LANES fft::inv_t1_load(tw[lane], &C.t1[0][lane]);
+    ALL_LANES fft::inv_p3(a[lane], C.u, tw[lane]);
+    ALL_LANES fft::inv_p3(b[lane], C.u, tw[lane]);
+}
+
 template <class G>
 void blind_rotate_fft(const iyk_params* p, const u32* lin, const fft::cplx* bk_fft, u32* tlwe1)
 {
@@ -597,18 +621,12 @@ void blind_rotate_fft(const iyk_params* p, const u32* lin, const fft::cplx* bk_f
             }
         }
         for (int cc = 0; cc < 2; ++cc) {
-            fft_inverse_wave(S[cc][0], xb);
+            fft_inverse2_wave(S[cc][0], S[cc][1], xb);
             ALL_LANES
             {
-                const double e = fft::round_err8(S[cc][0][lane]);
-                if (e > g_fft_worst) g_fft_worst = e;
+                const double e0 = fft::round_err8(S[cc][0][lane]), e1 = fft::round_err8(S[cc][1][lane]);
+                g_fft_worst = std::max(g_fft_worst, std::max(e0, e1));
                 fft::round16(S[cc][0][lane], lo[lane]);
-            }
-            fft_inverse_wave(S[cc][1], xb);
-            ALL_LANES
-            {
-                const double e = fft::round_err8(S[cc][1][lane]);
-                if (e > g_fft_worst) g_fft_worst = e;
             }
             ALL_LANES fft::acc_update16(lane, S[cc][1][lane], lo[lane], acc.data() + cc * NTT_N);
         }
@@ -648,8 +666,7 @@ void cmux_fft(const CmuxJob& j, const fft::cplx* trgsw, u32* T)
         }
     }
     for (int cc = 0; cc < 2; ++cc) {
-        fft_inverse_wave(S[cc][0], xb);
-        fft_inverse_wave(S[cc][1], xb);
+        fft_inverse2_wave(S[cc][0], S[cc][1], xb);
         ALL_LANES
         {
             const double e0 = fft::round_err8(S[cc][0][lane]), e1 = fft::round_err8(S[cc][1][lane]);
@@ -694,8 +711,7 @@ void cmux_chain(const CmuxChainJob& j, const fft::cplx* trgsw, u32* T)
             }
         }
         for (int cc = 0; cc < 2; ++cc) {
-            fft_inverse_wave(S[cc][0], xb);
-            fft_inverse_wave(S[cc][1], xb);
+            fft_inverse2_wave(S[cc][0], S[cc][1], xb);
             ALL_LANES
             {
                 const double e0 = fft::round_err8(S[cc][0][lane]), e1 = fft::round_err8(S[cc][1][lane]);
@@ -1030,6 +1046,34 @@ double iyk_emul_fft256_selftest(unsigned seed)
         }
     }
     return worst / big;
+}
+/* The paired inverse (fft_inverse2_wave: twiddle columns fetched once, both halves through one exchange buffer) against two
+ * single inverses (fft_inverse1_wave) on the same two random spectra (integers of 16 bits times 2^scale_bits, the size of a
+ * step's sums).  Returns the number of output doubles whose BIT PATTERNS differ (0: the same arithmetic in the same order). */
+int iyk_emul_fft_inverse2_selftest(unsigned seed, int scale_bits)
+{
+    static thread_local fft::cplx a[64][8], b[64][8], ra[64][8], rb[64][8];
+    std::vector<fft::cplx> xb(fft::XCHG_BYTES / sizeof(fft::cplx));
+    u64 st = 0xA0761D6478BD642Full ^ seed;
+    const double scale = std::ldexp(1.0, scale_bits);
+    auto rnd = [&]() {
+        st = st * 6364136223846793005ull + 1442695040888963407ull;
+        return ((double)(int32_t)(st >> 40) / 256.0 - 32768.0) * scale;
+    };
+    ALL_LANES for (int q = 0; q < 8; ++q) a[lane][q] = ra[lane][q] = {rnd(), rnd()};
+    ALL_LANES for (int q = 0; q < 8; ++q) b[lane][q] = rb[lane][q] = {rnd(), rnd()};
+    fft_inverse2_wave(a, b, xb.data());
+    fft_inverse1_wave(ra, xb.data());
+    fft_inverse1_wave(rb, xb.data());
+    int bad = 0;
+    ALL_LANES for (int q = 0; q < 8; ++q)
+    {
+        bad += std::memcmp(&a[lane][q].re, &ra[lane][q].re, 8) != 0;
+        bad += std::memcmp(&a[lane][q].im, &ra[lane][q].im, 8) != 0;
+        bad += std::memcmp(&b[lane][q].re, &rb[lane][q].re, 8) != 0;
+        bad += std::memcmp(&b[lane][q].im, &rb[lane][q].im, 8) != 0;
+    }
+    return bad;
 }
 /* The Linzer-Feig forward network (round 5) against a direct long-double evaluation A[k] = sum_j z[j] psi^(j (4 k + 1)) and
  * against the round-4 network on the same random input (integers of 16 bits).  which = 0: largest |LF - direct| relative to

@@ -325,6 +325,31 @@ IYK_HD void inv_p3(cplx (&a)[8], const Twist& u, const cplx* t1_lane)
     dft8<true>(a);
     twist8<true>(a, u);
 }
+// The same two parts with the lane's twiddle columns in registers: a pair of transforms that runs in one lane (the lo and hi
+// halves of an output polynomial, kernels_fft.hpp::fft_inverse2) fetches them once.  w[j0 - 1] = t2_lane[8 j0], tw[k0] = t1_lane[64 k0].
+IYK_HD void inv_t2_load(cplx (&w)[7], const cplx* t2_lane)
+{
+#pragma unroll
+    for (int j0 = 1; j0 < 8; ++j0) w[j0 - 1] = t2_lane[8 * j0];
+}
+IYK_HD void inv_t1_load(cplx (&tw)[8], const cplx* t1_lane)
+{
+#pragma unroll
+    for (int k0 = 0; k0 < 8; ++k0) tw[k0] = t1_lane[64 * k0];
+}
+IYK_HD void inv_p1(cplx (&a)[8], const cplx (&w)[7])
+{
+    dft8<true>(a);
+#pragma unroll
+    for (int j0 = 1; j0 < 8; ++j0) a[j0] = cmulc(a[j0], w[j0 - 1]);
+}
+IYK_HD void inv_p3(cplx (&a)[8], const Twist& u, const cplx (&tw)[8])
+{
+#pragma unroll
+    for (int k0 = 0; k0 < 8; ++k0) a[k0] = cmulc(a[k0], tw[k0]);
+    dft8<true>(a);
+    twist8<true>(a, u);
+}
 
 // rint(x) mod 2^32 for |x| < 2^51 by the magic-constant addition (one instruction): the low word of x + 1.5 * 2^52
 static constexpr double MAGIC = 6755399441055744.0;

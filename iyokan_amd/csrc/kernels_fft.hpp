@@ -88,6 +88,23 @@ __device__ __forceinline__ void twiddle_and_store(fft::cplx (&a)[8], const fft::
     }
 }
 
+// The same with the pass's values already in registers (tw[e - 1] belongs to a[e]): the second transform of a pair, and the
+// first once the pair's column has been fetched — 4 VALU, 1 LDS store per product.
+template <class Store>
+__device__ __forceinline__ void twiddle_and_store_conj(fft::cplx (&a)[8], const fft::cplx (&tw)[7], Store store)
+{
+#pragma unroll
+    for (int e = 1; e < 8; ++e) {
+        a[e] = fft::cmulc(a[e], tw[e - 1]);
+        store(e);
+    }
+#pragma unroll
+    for (int e = 1; e < 8; ++e) {
+        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+    }
+}
+
 // Wait until the LDS word at byte address `flag` is >= `want` (a counter only ever raised by the partner wave).  One assembly
 // block: as a C++ loop around an atomic load it became an inner loop that made the register allocator spill ~60 VGPRs around
 // it (4x slower); plain LDS accesses suffice — LDS is coherent within the workgroup, a wave's DS operations execute in order.
@@ -196,13 +213,19 @@ __device__ __forceinline__ void fft_forward_lf(int lane, fft::cplx (&a)[8], cons
 __device__ __forceinline__ void fft_inverse2(int lane, fft::cplx (&a)[8], fft::cplx (&b)[8], const fft::Twist& u,
                                              const fft::cplx* t1_lane, const fft::cplx* t2, fft::cplx* xb)
 {
+    // Both halves belong to the same lane and multiply by the same conjugated T2 column (7 values) and T1 column (8): each column
+    // is fetched ONCE per pair — 15 reads of 16 bytes per pair less than a fetch per half — into registers the inverse phase has
+    // (the dead u[16] and the forward's a[8]).  T2 is requested ahead of A's DFT8 and lands under it; T1 behind B's last exchange
+    // reads: LDS returns in order, so the wait for the data is the wait for the twiddles.  The exchange stores and reads keep their
+    // issue order: the single-buffer pipelining rests on it.
+    fft::cplx w2[7];
+    fft::inv_t2_load(w2, t2);
+    __builtin_amdgcn_sched_barrier(0);
     auto p1 = [&](fft::cplx (&x)[8]) {
-        const fft::cplx ta = t2[8], tb = t2[16];
-        __builtin_amdgcn_sched_barrier(0);
         fft::dft8<true>(x);
         xb[fft::x2_rbase(lane)] = x[0];
         __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-        twiddle_and_store<1, true>(x, t2, 8, ta, tb, [&](int j0) { xb[fft::x2_rbase(lane) + j0] = x[j0]; });
+        twiddle_and_store_conj(x, w2, [&](int j0) { xb[fft::x2_rbase(lane) + j0] = x[j0]; });
         lds_sync();
         fft::x2_get_b(lane, x, xb);
         lds_sync();
@@ -214,24 +237,18 @@ __device__ __forceinline__ void fft_inverse2(int lane, fft::cplx (&a)[8], fft::c
         fft::x1_get_a(lane, x, xb);
         lds_sync();
     };
-    auto p3 = [&](fft::cplx (&x)[8]) {   // the inverse phase has the registers (the dead u[16] and x[8]) for all of T1 at once
-        fft::cplx tw[8];
-#pragma unroll
-        for (int k0 = 0; k0 < 8; ++k0) tw[k0] = t1_lane[64 * k0];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int k0 = 0; k0 < 8; ++k0) x[k0] = fft::cmulc(x[k0], tw[k0]);
-        fft::dft8<true>(x);
-        fft::twist8<true>(x, u);
-    };
     p1(a);   // at FFT_PRIO_INV1, set by the caller
     p1(b);
     set_prio<FFT_PRIO_INV2>();
     p2(a);
     p2(b);
     set_prio<FFT_PRIO_INV3>();
-    p3(a);
-    p3(b);
+    fft::cplx tw[8];
+    fft::inv_t1_load(tw, t1_lane);
+    __builtin_amdgcn_sched_barrier(0);
+    fft::inv_p3(a, u, tw);
+    __builtin_amdgcn_sched_barrier(0);
+    fft::inv_p3(b, u, tw);
 }
 
 // One inverse transform (narrow-frontier kernel: one spectrum per wave); `after_p1` runs once the first exchange is under way
