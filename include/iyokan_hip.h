@@ -318,8 +318,8 @@ int iyk_hip_trlwe_add_batch(iyk_hip_stream* st, uint32_t* d_trlwe, uint64_t trlw
 /* ---- private key switch: lvl2 TLWEs (64-bit torus) -> TRLWE rows -> TRGSW selector slots ----------------------------------------
  * The second half of circuit bootstrapping (TaskTFHEppCB / CBInv / CBWithInv, /root/reference/src/iyokan_tfhepp.hpp:194-236, 384-407,
  * in front of every ROMUX / RAMUX / RAMCMUXs port, :738-802): the server makes the selector slots of the CMUX memories from
- * ciphertexts instead of taking them from the holder of the secret key.  The first half (lvl0 -> lvl2 blind rotation) is not here yet;
- * it will write the lvl2 store below.  Integer only: available on every path, exact, order-free (sums mod 2^32).
+ * ciphertexts instead of taking them from the holder of the secret key.  The first half (lvl0 -> lvl2 blind rotation) is
+ * iyk_hip_cb_rotate_batch further down; it writes the lvl2 store below.  Integer only: available on every path, exact, order-free (sums mod 2^32).
  *
  * The key, one object per GPU: u32 [k+1][n_in+1][t][2^basebit - 1][k+1][N] — row K[c][i][j][u] is a lvl1 TRLWE (a(X), then b(X)) whose
  * phase b - a s1 is (u+1) 2^(32 - (j+1) basebit) sigma_i f_c(X) + noise, sigma_i = s2[i] (i < n_in), sigma_{n_in} = -1, f_1 = 1, f_0 = -s1(X)
@@ -356,6 +356,38 @@ int iyk_hip_privks_batch(iyk_hip_stream* st, const void* key, const uint64_t* d_
  * nothing is launched; IYK_ERR_STATE off the FFT path. */
 int iyk_hip_trgsw_from_rows(iyk_hip_stream* st, void* d_trgsw, uint64_t trgsw_slots, uint64_t count, const int32_t* out_slot,
                             const uint32_t* d_trlwe, uint64_t trlwe_slots, const int32_t* rows /* [count][(k+1) l] */);
+
+/* ---- circuit bootstrapping, first half: lvl0 -> lvl2 blind rotation (N2 = 2048, k = 1, 64-bit torus) -----------------------------
+ * TFHEpp's GateBootstrappingTLWE2TLWEFFTvariableMu followed by + mu, once per gadget digit of an address bit, inside
+ * CircuitBootstrappingFFT<lvl02param, lvl21param> (TaskTFHEppCB / CBInv / CBWithInv).  Job g = {in, sign, off, mu, out} on a lvl0 TLWE
+ * store u32 [tlwe0_slots][key.n + 1] (the arena, when key.n is the initialised n) and a lvl2 store of n_in = 2048:
+ *     lin = sign * W0[in] + (0, .., 0, off);  abar_i = (lin_i + 2^19) >> 20;  acc = X^(2 N2 - (lin_n >> 20)) * (0, mu (1 + .. + X^(N2-1)));
+ *     acc += BK2_i [.] ((X^abar_i - 1) acc) for i < n;  W2[out] = SampleExtractIndex(acc, 0) + (0, .., 0, mu)
+ * a lvl2 TLWE of 2 mu where the phase of lin is positive, of 0 where it is negative.  mu_r = 2^(63 - (r+1) Bgbit), r < l, gives the TLWEs
+ * iyk_hip_privks_batch takes, slot order bit * l + r.  sign = -1: the reference's CircuitBootstrappingFFTInv.
+ * Exact: every output word is the schoolbook negacyclic product mod 2^64 (integer field, key words split in two 32-bit halves: csrc/cb_rotate.hpp).
+ * Integer only: available on every path.
+ *
+ * The key, one object per GPU: the torus-domain lvl2 TRGSW of every lvl0 key bit, u64 [n][(k+1) l2][k+1][N2] on the host (row c l2 + j:
+ * a lvl2 TRLWE of zero plus s0[i] 2^(64 - (j+1) Bgbit2) at coefficient 0 of polynomial c), is uploaded in windows of steps through the
+ * stream's page-locked ring and transformed on the stream into u64 [n][2 halves][(k+1) l2][k+1][N2] (333 MB at n = 636).  1 <= n <= 2047;
+ * (l2, Bgbit2) = (4, 9) is the one instantiated pair, anything else is IYK_ERR_INVALID.  create allocates and does nothing else; a failed
+ * allocation is IYK_ERR_HIP and leaves nothing behind.  upload: host words copied before return, asynchronous on st; the FIRST upload of
+ * a key also sends the transform's tables (32 KiB) ahead of its window, so an upload on another stream must be ordered after it; a stream of another
+ * replica than the key's is IYK_ERR_INVALID.  bytes: device bytes of the live keys of one GPU (0 again after iyk_hip_cleanup + iyk_hip_init;
+ * a key of the earlier initialisation may still be freed and leaves the new count alone). */
+int iyk_hip_bk2_key_create(int gpu_index, uint32_t n, uint32_t l2, uint32_t Bgbit2, void** out);
+int iyk_hip_bk2_key_upload(iyk_hip_stream* st, void* key, uint64_t first_step, uint64_t step_count,
+                           const uint64_t* host_trgsw /* u64 [step_count][(k+1) l2][k+1][N2], torus domain */);
+int iyk_hip_bk2_key_free(void* key);
+int iyk_hip_bk2_key_bytes(int gpu_index, uint64_t* out);
+/* count rotations, asynchronous on st, host arrays copied before return.  One workgroup per rotation; a batch wider than the GPU has
+ * compute units runs in rounds inside the one launch.  Checked in O(count): every index inside its store, sign in {+1, -1}, no two jobs
+ * with one out — a violation is IYK_ERR_INVALID and nothing is launched.  The kernel's time is what iyk_hip_last_batch_timing reports
+ * (keyswitch_ms = 0). */
+int iyk_hip_cb_rotate_batch(iyk_hip_stream* st, const void* key, const uint32_t* d_tlwe0, uint64_t tlwe0_slots, uint64_t count,
+                            const int32_t* in, const int32_t* sign, const uint32_t* off, const uint64_t* mu, uint64_t* d_tlwe2,
+                            uint64_t tlwe2_slots, const int32_t* out);
 
 /* Kernel-only time of the most recent iyk_hip_gate_batch on this stream, from HIP events
  * recorded on the stream around the blind-rotate and key-switch launches (milliseconds).

@@ -42,6 +42,8 @@ def _lib():
         lib.iyk_client_tlwe2_phases.argtypes = [ctypes.c_uint32, _u32p, _u64p, u64, _u64p]
         lib.iyk_client_privks_key_rows.argtypes = [ctypes.POINTER(IykParams), _u32p, ctypes.c_uint32, _u32p, ctypes.c_uint32,
                                                    ctypes.c_uint32, u64, u64, u64, ctypes.c_int, ctypes.c_int, _u32p]
+        lib.iyk_client_bk2_rows.argtypes = [ctypes.c_uint32, _u32p, ctypes.c_uint32, _u32p, ctypes.c_uint32, ctypes.c_uint32,
+                                            ctypes.c_double, u64, u64, u64, ctypes.c_int, ctypes.c_int, _u64p]
         _LIB = lib
     return _LIB
 
@@ -227,3 +229,20 @@ def encrypt_cb_digits(s2, bits, params, alpha, seed=None) -> np.ndarray:
     bits = np.asarray(bits, dtype=np.uint64).ravel()
     msgs = np.array([[int(b) << (64 - (r + 1) * params.Bgbit) for r in range(params.l)] for b in bits], dtype=np.uint64)
     return encrypt_tlwe2(s2, msgs.ravel(), alpha, seed)
+
+
+def bk2_rows(keys: KeySet, s2, l2, Bgbit2, alpha2, first_step=0, step_count=None, seed=None, nthreads=None) -> np.ndarray:
+    """Steps [first_step, first_step + step_count) of the lvl2 bootstrapping key of the lvl0 -> lvl2 rotation, torus domain:
+    u64 [step_count][(k+1) l2][k+1][N2], N2 = len(s2).  Row c l2 + j of step i is a lvl2 TRLWE of zero (noise alpha2) under the ring key s2
+    plus s0[i] 2^(64 - (j+1) Bgbit2) at coefficient 0 of polynomial c.  The lvl2 TLWE key the rotation's outputs decrypt under is s2 as
+    tlwe2_phases takes it.  Any window gives the same words as the whole key (an int seed); at most MAX_THREADS threads."""
+    s2 = np.ascontiguousarray(s2, dtype=np.uint32)
+    s0 = np.ascontiguousarray(keys.s0, dtype=np.uint32)
+    step_count = s0.size - first_step if step_count is None else int(step_count)
+    out = np.zeros((max(step_count, 0), 2 * int(l2), 2, s2.size), dtype=np.uint64)
+    rc = _lib().iyk_client_bk2_rows(s0.size, _p32(s0), s2.size, _p32(s2), int(l2), int(Bgbit2), float(alpha2), int(first_step), step_count,
+                                    0 if seed is None else int(seed), int(seed is not None),
+                                    _threads() if nthreads is None else int(nthreads), out.ctypes.data_as(_u64p))
+    if rc != 0:
+        raise ValueError(f"iyk_client_bk2_rows refused its arguments ({rc})")
+    return out

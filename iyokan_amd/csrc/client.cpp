@@ -20,6 +20,7 @@
 //   BK (torus)     u32[n][(k+1)l][k+1][N]        row r = c*l + j: TRLWE(0) + s0[i]*2^(32-(j+1)Bgbit) on poly c, coeff 0
 //   KSK            u32[kN][t][2^basebit-1][n+1]  TLWE0( s1[i] * v * 2^(32-(j+1)basebit) ), v = idx+1
 //   TLWE lvl2      u64[n_in+1]                   a[0..n_in-1], b = a[n_in]: 64-bit torus (the output level of circuit bootstrapping's rotation)
+//   BK lvl2 (torus) u64[n][(k+1)l2][k+1][N2]     row r = c*l2 + j: TRLWE2(0) + s0[i]*2^(64-(j+1)Bgbit2) on poly c, coeff 0 (iyk_client_bk2_rows)
 //   private KSK    u32[k+1][n_in+1][t][2^basebit-1][k+1][N]   row (c, i, j, u): TRLWE(0) + sigma_i (u+1) 2^(32-(j+1)basebit) on poly c,
 //                                                coeff 0; sigma_i = s2[i], sigma_{n_in} = -1 (phase: f_c = 1 for c = 1, -s1(X) for c = 0)
 #include <sys/random.h>
@@ -328,6 +329,49 @@ int iyk_client_privks_key_rows(const iyk_params* p, const uint32_t* s1, uint32_t
     }
     std::vector<std::thread> pool;
     for (int k = 0; k < nt; ++k) pool.emplace_back(work, row_count * k / nt, row_count * (k + 1) / nt);
+    for (auto& th : pool) th.join();
+    return 0;
+}
+
+// Steps [first_step, first_step + step_count) of the lvl2 bootstrapping key of circuit bootstrapping's rotation: u64 [n][(k+1) l2][k+1][N2],
+// N2 = 2048 = the size of s2 (the ring key whose coefficients are the lvl2 TLWE key of iyk_client_tlwe2_phases).  Row (i, r = c l2 + j) is a
+// lvl2 TRLWE of zero (noise alpha2) plus s0[i] 2^(64 - (j+1) Bgbit2) at coefficient 0 of polynomial c: TFHEpp's bkgen<lvl02param> in the
+// torus domain.  Every row draws from a generator of its own — seeded from (seed, row index), or keyed from the OS — so a window holds the
+// same words however the key is cut and whatever nthreads is.
+int iyk_client_bk2_rows(uint32_t n, const uint32_t* s0, uint32_t N2, const uint32_t* s2, uint32_t l2, uint32_t Bgbit2, double alpha2,
+                        uint64_t first_step, uint64_t step_count, uint64_t seed, int deterministic, int nthreads, uint64_t* out)
+{
+    if (!s0 || !s2 || !out || n == 0 || N2 == 0 || l2 == 0 || Bgbit2 == 0 || (uint64_t)l2 * Bgbit2 > 63) return -1;
+    if (first_step > n || step_count > n - first_step) return -1;
+    const uint64_t rows = 2ull * l2, total = step_count * rows;
+    auto work = [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t q = lo; q < hi; ++q) {
+            const uint64_t R = first_step * rows + q, i = R / rows, r = R % rows;
+            Rng rng(seed ^ (0xA0761D6478BD642Full * (R + 1)), deterministic);
+            uint64_t* a = out + q * 2 * N2;
+            uint64_t* b = a + N2;
+            for (uint32_t x = 0; x < N2; ++x) {
+                a[x] = rng.next();
+                double d = rng.gauss(alpha2);
+                d -= std::rint(d);
+                b[x] = (uint64_t)(int64_t)std::ldexp(d, 63) << 1;
+            }
+            for (uint32_t t = 0; t < N2; ++t) {
+                if (!s2[t]) continue;
+                for (uint32_t x = 0; x < N2 - t; ++x) b[x + t] += a[x];
+                for (uint32_t x = N2 - t; x < N2; ++x) b[x + t - N2] -= a[x];
+            }
+            const uint64_t c = r / l2, j = r % l2;
+            if (s0[i]) out[q * 2 * N2 + c * N2] += 1ull << (64 - (j + 1) * Bgbit2);
+        }
+    };
+    const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)nthreads, 16, (int64_t)total}));
+    if (nt == 1) {
+        work(0, total);
+        return 0;
+    }
+    std::vector<std::thread> pool;
+    for (int k = 0; k < nt; ++k) pool.emplace_back(work, total * k / nt, total * (k + 1) / nt);
     for (auto& th : pool) th.join();
     return 0;
 }

@@ -19,6 +19,7 @@
 #include "fft256.hpp"
 #include "dispatch.hpp"
 #include "privks.hpp"
+#include "cb_rotate.hpp"
 
 using namespace iyk;
 
@@ -1182,5 +1183,128 @@ void iyk_emul_privks_digits(const uint64_t* w, int count, uint32_t t, uint32_t b
         const u64 wbar = privks_round(w[g], t, basebit);
         for (uint32_t j = 0; j < t; ++j) digits[(size_t)g * t + j] = privks_digit(wbar, j, basebit);
     }
+}
+}
+
+/* ---- cb_rotate.hpp: the lvl0 -> lvl2 rotation's transform and one job, lane by lane ---------------------------------------------- */
+namespace {
+struct CbTables {
+    std::vector<u64> tw;   // twf then twi
+    CbTables() : tw(2 * CB_N) { cb_make_tables(tw.data(), tw.data() + CB_N); }
+};
+const CbTables& cb_tables()
+{
+    static CbTables t;
+    return t;
+}
+// forward transform of field elements x[j] (natural) -> X[k] (natural), through one slot of the exchange buffer
+void cb_forward(const u64* in, u64* out)
+{
+    const u64* twf = cb_tables().tw.data();
+    std::vector<u64> bp(CB_PSTRIDE);
+    for (int j1 = 0; j1 < 64; ++j1) {
+        u64 x[32];
+        for (int j2 = 0; j2 < 32; ++j2) x[j2] = gl_mul_pow2(in[j1 + 64 * j2], LOG_ZETA * j2);
+        cb_pass1_fwd(j1, x, twf, bp.data());
+    }
+    std::vector<std::array<u64, 64>> X(32);
+    for (int k2 = 0; k2 < 32; ++k2) cb_pass2_fwd_read(k2, bp.data(), reinterpret_cast<u64(&)[64]>(*X[k2].data()));
+    for (int k2 = 0; k2 < 32; ++k2) cb_pass2_fwd_write(k2, reinterpret_cast<const u64(&)[64]>(*X[k2].data()), out);
+}
+void cb_inverse(const u64* in, u64* out)
+{
+    const u64* twi = cb_tables().tw.data() + CB_N;
+    std::vector<u64> bp(in, in + CB_N);
+    bp.resize(CB_PSTRIDE);
+    std::vector<std::array<u64, 64>> X(32);
+    for (int k2 = 0; k2 < 32; ++k2) cb_pass1_inv_read(k2, bp.data(), twi, reinterpret_cast<u64(&)[64]>(*X[k2].data()));
+    for (int k2 = 0; k2 < 32; ++k2) cb_pass1_inv_write(k2, reinterpret_cast<const u64(&)[64]>(*X[k2].data()), bp.data());
+    for (int j1 = 0; j1 < 64; ++j1) {
+        u64 y[32];
+        cb_pass2_inv(j1, bp.data(), y);
+        for (int p = 0; p < 32; ++p) out[j1 + 64 * brv5(p)] = y[p];
+    }
+}
+
+// lane-by-lane run of cb_rotate_kernel for one job: the same phase functions in the same order, one loop over the 256 lanes wherever
+// the kernel has a barrier
+template <int L2, int BGBIT2>
+void cb_rotate(u32 n, const u32* w, const CbJob& jb, const u64* bk, u64* out)
+{
+    const u64* twf = cb_tables().tw.data();
+    const u64* twi = twf + CB_N;
+    std::vector<u64> acc(2 * CB_N), buf(4 * CB_PSTRIDE);
+    std::vector<u32> abar(CB_N);
+    struct Lane {
+        u64 x[64], accum[32];
+    };
+    std::vector<Lane> R(CB_LANES);
+#define CB_LANES_ALL for (int lane = 0; lane < CB_LANES; ++lane)
+#define CB_LANES_HALF for (int lane = 0; lane < 128; ++lane)
+    CB_LANES_ALL cb_prologue(lane, jb, w, n, abar.data(), acc.data());
+    for (u32 i = 0; i < n; ++i) {
+        const u32 ab = abar[i];
+        const u64* bk_step = bk + (size_t)i * CB_STEP_WORDS;
+        CB_LANES_ALL for (int q = 0; q < 32; ++q) R[lane].accum[q] = 0;
+        for (int h = 0; h < 2; ++h) {
+            CB_LANES_ALL cb_fwd1<L2, BGBIT2>(lane, h, ab, acc.data(), twf, buf.data());
+            CB_LANES_HALF cb_pass2_fwd_read(lane & 31, buf.data() + (lane >> 5) * CB_PSTRIDE, R[lane].x);
+            CB_LANES_HALF cb_pass2_fwd_write(lane & 31, R[lane].x, buf.data() + (lane >> 5) * CB_PSTRIDE);
+            CB_LANES_ALL cb_mac<L2>(lane, h, buf.data(), bk_step, R[lane].accum);
+        }
+        CB_LANES_ALL cb_inv_write(lane, R[lane].accum, buf.data());
+        CB_LANES_HALF cb_pass1_inv_read(lane & 31, buf.data() + (lane >> 5) * CB_PSTRIDE, twi, R[lane].x);
+        CB_LANES_HALF cb_pass1_inv_write(lane & 31, R[lane].x, buf.data() + (lane >> 5) * CB_PSTRIDE);
+        CB_LANES_ALL cb_inv2(lane, buf.data(), acc.data());
+    }
+    for (int j = 0; j <= CB_N; ++j) out[j] = cb_extract_word(acc.data(), j, jb.mu);
+#undef CB_LANES_ALL
+#undef CB_LANES_HALF
+}
+}  // namespace
+
+extern "C" {
+/* ntt64_dif on 64 field elements, result in natural order; inverse != 0: the root 2^-3 (unscaled) */
+void iyk_emul_ntt64(const uint64_t* in, int inverse, uint64_t* out)
+{
+    u64 x[64];
+    for (int j = 0; j < 64; ++j) x[j] = in[j];
+    if (inverse) ntt64_dif<192 - LOG_ZETA>(x);
+    else ntt64_dif<LOG_ZETA>(x);
+    for (int p = 0; p < 64; ++p) out[brv6(p)] = x[p];
+}
+/* the N2 = 2048 negacyclic transform on canonical field elements, natural order on both sides; psi_out: the root it is built on */
+void iyk_emul_cb_ntt(const uint64_t* in, int inverse, uint64_t* out, uint64_t* psi_out)
+{
+    if (inverse) cb_inverse(in, out);
+    else cb_forward(in, out);
+    if (psi_out) *psi_out = cb_find_psi();
+}
+/* signed gadget digits of `count` words: digits[count][l2] */
+int iyk_emul_cb_digits(const uint64_t* x, int count, uint32_t l2, uint32_t Bgbit2, int32_t* digits)
+{
+    if (l2 != 4 || Bgbit2 != 9) return -1;
+    for (int g = 0; g < count; ++g)
+        for (int lvl = 0; lvl < 4; ++lvl) digits[g * 4 + lvl] = (int32_t)cb_digit_u<4, 9>(x[g], lvl) - (int32_t)CbConsts<4, 9>::half_bg;
+    return 0;
+}
+/* bk2_ntt_kernel on the CPU: torus u64 [steps][8][2][N2] -> u64 [steps][2 halves][8][2][N2] */
+void iyk_emul_bk2_ntt(uint64_t steps, const uint64_t* torus, uint64_t* dst)
+{
+    std::vector<u64> half(CB_N);
+    for (uint64_t poly = 0; poly < steps * CB_ROWS * 2; ++poly)
+        for (int hf = 0; hf < 2; ++hf) {
+            const uint64_t step = poly / (CB_ROWS * 2), rc = poly % (CB_ROWS * 2);
+            for (int j = 0; j < CB_N; ++j) half[j] = hf ? torus[poly * CB_N + j] >> 32 : (u64)(u32)torus[poly * CB_N + j];
+            cb_forward(half.data(), dst + step * CB_STEP_WORDS + ((size_t)hf * CB_ROWS * 2 + rc) * CB_N);
+        }
+}
+/* one job of cb_rotate_kernel: w = the n + 1 words of the lvl0 TLWE, out = u64 [N2 + 1] */
+int iyk_emul_cb_rotate(uint32_t n, uint32_t l2, uint32_t Bgbit2, const uint32_t* w, int32_t sign, uint32_t off, uint64_t mu,
+                       const uint64_t* bk_ntt, uint64_t* out)
+{
+    if (l2 != 4 || Bgbit2 != 9 || n == 0 || n > CB_MAX_N0 || (sign != 1 && sign != -1)) return -1;
+    cb_rotate<4, 9>(n, w, CbJob{0, sign, off, 0, mu}, bk_ntt, out);
+    return 0;
 }
 }

@@ -42,6 +42,7 @@
 #endif
 #include "cmux_fft.hpp"
 #include "privks.hpp"
+#include "cb_rotate.hpp"
 
 using namespace iyk;
 using namespace iyk::dispatch;
@@ -92,6 +93,7 @@ struct Device {
     iyk_level_cost cost{};         // what a level of r rotations costs on this GPU (iyk_hip_level_cost_table); read / written under G.mu
     struct GateCoalescer* co = nullptr;   // lazily created by iyk_hip_gate_host (one per GPU); freed by iyk_hip_cleanup
     uint64_t privks_bytes = 0;     // device memory of the live private key-switch keys of this GPU (iyk_hip_privks_key_*): __atomic adds
+    uint64_t bk2_bytes = 0;        // device memory of the live lvl2 bootstrapping keys of this GPU (iyk_hip_bk2_key_*): __atomic adds
     int max_passes = 0;            // cost.max_passes as the dispatch reads it: __atomic loads / stores, lock-free (a calibration may run
                                    // beside a batch; a plain int keeps Device copyable)
     void release()
@@ -553,6 +555,7 @@ int set_kernel_attrs(const iyk_params& p, bool use_fp, int split)
         return set_fp_attrs<DC>();
     });
     if (rc) return rc;
+    if ((rc = set_lds(cb_rotate_kernel<4, 9>, CB_LDS_BYTES))) return rc;   // lvl2 rotation of circuit bootstrapping: every path
     return with_ks_set(p.t, [&](auto t, auto nc) {
         constexpr int T = decltype(t)::value, NC = decltype(nc)::value;
         if constexpr (NC != 0)
@@ -2498,6 +2501,153 @@ int iyk_hip_trgsw_from_rows(iyk_hip_stream* st, void* d_trgsw, uint64_t trgsw_sl
                            &D.fftc->c, c * polys);
         HIP_TRY(hipGetLastError());
         g = e;
+    }
+    return release_stage(st);
+    IYK_API_END
+}
+
+/* ---- circuit bootstrapping, first half: lvl0 -> lvl2 blind rotation (cb_rotate.hpp) ------------------------------------------- */
+
+namespace {
+
+struct Bk2Key {
+    int gpu = 0;
+    u32 n = 0, l2 = 0, Bgbit2 = 0;
+    uint64_t bytes = 0;
+    uint64_t generation = 0;  // G.generation at create
+    u64* d = nullptr;         // u64 [n][2 halves][(k+1) l2][k+1][N2], NTT domain; then the transform's tables (twf, twi: 2 x N2 words)
+    u64* tw = nullptr;        // d + n * CB_STEP_WORDS
+    std::atomic<bool> tables_sent{false};   // the first upload sends the tables, on its stream, ahead of its window
+};
+constexpr uint64_t BK2_UPLOAD_CHUNK = 8;   // key steps per staging slot (2 MiB of torus words)
+
+}  // namespace
+
+int iyk_hip_bk2_key_create(int gpu_index, uint32_t n, uint32_t l2, uint32_t Bgbit2, void** out)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    if (!out) return fail(IYK_ERR_INVALID, "null out");
+    if (n == 0 || n > CB_MAX_N0) return fail(IYK_ERR_INVALID, "n outside [1, 2047]");
+    if (l2 != 4 || Bgbit2 != 9) return fail(IYK_ERR_INVALID, "the lvl2 rotation is built for l2 = 4, Bgbit2 = 9");
+    int rc = set_device(gpu_index);
+    if (rc) return rc;
+    const uint64_t bytes = ((uint64_t)n * CB_STEP_WORDS + 2 * CB_N) * sizeof(u64);
+    u64* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();   // an allocation failure is not sticky: leave no pending error behind
+        return fail(IYK_ERR_HIP, std::string("hipMalloc of the lvl2 bootstrapping key (") + std::to_string(bytes) + " bytes): " + hipGetErrorString(e));
+    }
+    Bk2Key* key = new (std::nothrow) Bk2Key();
+    if (!key) {
+        (void)hipFree(d);
+        return fail(IYK_ERR_NOMEM, "out of host memory");
+    }
+    key->gpu = gpu_index, key->n = n, key->l2 = l2, key->Bgbit2 = Bgbit2;
+    key->bytes = bytes, key->generation = G.generation, key->d = d, key->tw = d + (size_t)n * CB_STEP_WORDS;
+    __atomic_fetch_add(&G.devs[gpu_index].bk2_bytes, bytes, __ATOMIC_RELAXED);
+    *out = key;
+    return IYK_OK;
+    IYK_API_END
+}
+
+int iyk_hip_bk2_key_free(void* key_)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    Bk2Key* key = (Bk2Key*)key_;
+    if (!key) return IYK_OK;
+    int rc = set_device(key->gpu);
+    if (rc) return rc;
+    HIP_TRY(hipFree(key->d));
+    if (key->generation == G.generation) __atomic_fetch_sub(&G.devs[key->gpu].bk2_bytes, key->bytes, __ATOMIC_RELAXED);
+    delete key;
+    return IYK_OK;
+    IYK_API_END
+}
+
+int iyk_hip_bk2_key_bytes(int gpu_index, uint64_t* out)
+{
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    if (!out) return fail(IYK_ERR_INVALID, "null out");
+    if (gpu_index < 0 || gpu_index >= (int)G.devs.size()) return fail(IYK_ERR_INVALID, "gpu_index out of range");
+    *out = __atomic_load_n(&G.devs[gpu_index].bk2_bytes, __ATOMIC_RELAXED);
+    return IYK_OK;
+}
+
+int iyk_hip_bk2_key_upload(iyk_hip_stream* st, void* key_, uint64_t first_step, uint64_t step_count, const uint64_t* host_trgsw)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    Bk2Key* key = (Bk2Key*)key_;
+    if (!st || !key || !host_trgsw) return fail(IYK_ERR_INVALID, "null argument");
+    if (st->gpu != key->gpu) return fail(IYK_ERR_INVALID, "the stream and the key are on different GPUs");
+    if (first_step > key->n || step_count > key->n - first_step) return fail(IYK_ERR_INVALID, "step range outside the key");
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    if (!key->tables_sent.exchange(true)) {   // once per key, by its first upload (create only allocates)
+        const size_t bytes = 2 * CB_N * sizeof(u64);
+        size_t soff = 0;
+        if ((rc = acquire_stage(st, bytes, &soff))) return rc;
+        cb_make_tables((u64*)(st->h_stage + soff), (u64*)(st->h_stage + soff) + CB_N);
+        HIP_TRY(hipMemcpyAsync(key->tw, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+        if ((rc = release_stage(st))) return rc;
+    }
+    for (uint64_t done = 0; done < step_count; done += BK2_UPLOAD_CHUNK) {
+        const uint64_t c = std::min<uint64_t>(BK2_UPLOAD_CHUNK, step_count - done);
+        const size_t bytes = (size_t)c * CB_TORUS_STEP_WORDS * sizeof(u64);
+        size_t soff = 0;
+        if ((rc = acquire_stage(st, bytes, &soff))) return rc;
+        std::memcpy(st->h_stage + soff, host_trgsw + (size_t)done * CB_TORUS_STEP_WORDS, bytes);   // the caller's window is free on return
+        HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+        hipLaunchKernelGGL(bk2_ntt_kernel, dim3((unsigned)(c * CB_ROWS * 2 * 2)), dim3(64), 0, st->s, (const u64*)(st->d_stage + soff),
+                           key->d + (size_t)(first_step + done) * CB_STEP_WORDS, (const u64*)key->tw);
+        HIP_TRY(hipGetLastError());
+        if ((rc = release_stage(st))) return rc;
+    }
+    return IYK_OK;
+    IYK_API_END
+}
+
+int iyk_hip_cb_rotate_batch(iyk_hip_stream* st, const void* key_, const uint32_t* d_tlwe0, uint64_t tlwe0_slots, uint64_t count,
+                            const int32_t* in, const int32_t* sign, const uint32_t* off, const uint64_t* mu, uint64_t* d_tlwe2,
+                            uint64_t tlwe2_slots, const int32_t* out)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    const Bk2Key* key = (const Bk2Key*)key_;
+    if (!st || !key || !d_tlwe0 || !in || !sign || !off || !mu || !d_tlwe2 || !out) return fail(IYK_ERR_INVALID, "null argument");
+    if (st->gpu != key->gpu) return fail(IYK_ERR_INVALID, "the stream and the key are on different GPUs");
+    if (count == 0) return IYK_OK;
+    if (count > (1u << 20)) return fail(IYK_ERR_INVALID, "batch too large");
+    if (tlwe0_slots > (1ull << 28) || tlwe2_slots > (1ull << 28)) return fail(IYK_ERR_INVALID, "store larger than an allocation can be");
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    std::vector<CbJob> jobs(count);
+    std::unordered_map<int32_t, uint64_t> writer;   // out slot -> its job
+    writer.reserve(count * 2);
+    for (uint64_t g = 0; g < count; ++g) {
+        if (!slot_ok(in[g], tlwe0_slots)) return fail(IYK_ERR_INVALID, "TLWE index outside the lvl0 store");
+        if (sign[g] != 1 && sign[g] != -1) return fail(IYK_ERR_INVALID, "sign outside {+1, -1}");
+        if (!slot_ok(out[g], tlwe2_slots)) return fail(IYK_ERR_INVALID, "TLWE index outside the lvl2 store");
+        if (!writer.emplace(out[g], g).second) return fail(IYK_ERR_INVALID, "two jobs of one batch write the same lvl2 TLWE");
+        jobs[g] = CbJob{in[g], sign[g], off[g], out[g], mu[g]};
+    }
+    const size_t bytes = jobs.size() * sizeof(CbJob);
+    size_t soff = 0;
+    if ((rc = acquire_stage(st, bytes, &soff))) return rc;
+    std::memcpy(st->h_stage + soff, jobs.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+    const unsigned grid = (unsigned)std::min<uint64_t>(count, (uint64_t)G.devs[st->gpu].cus);   // wider batches run in rounds
+    const bool timed = !st->log_on && st->ev_br0 && st->ev_br1;
+    if (timed) HIP_TRY(hipEventRecord(st->ev_br0, st->s));
+    hipLaunchKernelGGL((cb_rotate_kernel<4, 9>), dim3(grid), dim3(CB_LANES), CB_LDS_BYTES, st->s, (const CbJob*)(st->d_stage + soff), (int)count,
+                       d_tlwe0, key->n, (const u64*)key->d, (const u64*)key->tw, d_tlwe2);
+    HIP_TRY(hipGetLastError());
+    if (timed) {
+        HIP_TRY(hipEventRecord(st->ev_br1, st->s));
+        st->timing_valid = true, st->timing_has_ks = false;
     }
     return release_stage(st);
     IYK_API_END

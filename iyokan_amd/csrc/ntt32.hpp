@@ -74,6 +74,32 @@ IYK_HD void ntt32_dit(u64 (&a)[32])
     }
 }
 
+IYK_HD constexpr int brv6(int x)
+{
+    return ((x & 1) << 5) | ((x & 2) << 3) | ((x & 4) << 1) | ((x & 8) >> 1) | ((x & 16) >> 3) | ((x & 32) >> 5);
+}
+
+// Cyclic 64-point NTT, natural-order input, bit-reversed output (position p holds index brv6(p)): the long pass of the
+// N = 2048 = 32 x 64 transform (cb_rotate.hpp).  Root = 2^LOGW, which must have order 64: LOGW = 3 forward, 189 inverse.
+template <unsigned LOGW>
+IYK_HD void ntt64_dif(u64 (&a)[64])
+{
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+        const int len = 32 >> s;
+#pragma unroll
+        for (int blk = 0; blk < 64; blk += 2 * len) {
+#pragma unroll
+            for (int j = 0; j < len; ++j) {
+                const unsigned sh = (unsigned)(((u64)LOGW << s) * (u64)j % 192u);
+                u64 u = a[blk + j], v = a[blk + j + len];
+                a[blk + j] = gl_add(u, v);
+                a[blk + j + len] = gl_mul_pow2(gl_sub(u, v), sh);
+            }
+        }
+    }
+}
+
 // forward pass 1: x[j2] natural.  On return position p holds
 //   Y[k2 = brv5(p)] = tw_row[k2] * sum_j2 x[j2] zeta^(j2(2k2+1)),  tw_row = tw_fwd[j1]
 IYK_HD void ntt_fwd_pass1(u64 (&x)[32], const u64* tw_row)

@@ -41,6 +41,7 @@ EXPORTS = [
     "iyk_hip_privks_key_create", "iyk_hip_privks_key_upload", "iyk_hip_privks_key_free", "iyk_hip_privks_key_bytes",
     "iyk_hip_tlwe2_alloc", "iyk_hip_tlwe2_free", "iyk_hip_tlwe2_upload", "iyk_hip_tlwe2_download", "iyk_hip_privks_batch",
     "iyk_hip_trgsw_from_rows",
+    "iyk_hip_bk2_key_create", "iyk_hip_bk2_key_upload", "iyk_hip_bk2_key_free", "iyk_hip_bk2_key_bytes", "iyk_hip_cb_rotate_batch",
 ]
 
 
@@ -106,6 +107,11 @@ def lib():
         L.iyk_hip_tlwe2_upload.argtypes = [_vp, _vp, u32, u64, u64, u64, _u64p]
         L.iyk_hip_tlwe2_download.argtypes = [_vp, _vp, u32, u64, u64, u64, _u64p]
         L.iyk_hip_privks_batch.argtypes = [_vp, _vp, _vp, u64, u64, _i32p, _i32p, _vp, u64, _i32p]
+        L.iyk_hip_bk2_key_create.argtypes = [ctypes.c_int, u32, u32, u32, ctypes.POINTER(_vp)]
+        L.iyk_hip_bk2_key_upload.argtypes = [_vp, _vp, u64, u64, _u64p]
+        L.iyk_hip_bk2_key_free.argtypes = [_vp]
+        L.iyk_hip_bk2_key_bytes.argtypes = [ctypes.c_int, ctypes.POINTER(u64)]
+        L.iyk_hip_cb_rotate_batch.argtypes = [_vp, _vp, _vp, u64, u64, _i32p, _i32p, _u32p, _u64p, _vp, u64, _i32p]
         L.iyk_hip_trgsw_from_rows.argtypes = [_vp, _vp, u64, u64, _i32p, _vp, u64, _i32p]
         L.iyk_hip_last_batch_timing.argtypes = [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.iyk_hip_resident_key_bytes.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
@@ -357,6 +363,37 @@ def privks_key_bytes(gpu=0):
     return v.value
 
 
+class Bk2Key:
+    """Device-resident lvl2 bootstrapping key of one GPU (the lvl0 -> lvl2 rotation of circuit bootstrapping, Stream.cb_rotate_batch):
+    the torus-domain rows u64 [n][(k+1) l2][k+1][N2] of client.bk2_rows, uploaded in windows of steps and transformed on the stream."""
+    N2 = 2048
+
+    def __init__(self, n, l2=4, Bgbit2=9, gpu_index=0):
+        self.n, self.l2, self.Bgbit2, self.gpu_index = int(n), int(l2), int(Bgbit2), gpu_index
+        self.step_words = 2 * self.l2 * 2 * self.N2
+        h = _vp()
+        _check(lib().iyk_hip_bk2_key_create(gpu_index, self.n, self.l2, self.Bgbit2, ctypes.byref(h)), "iyk_hip_bk2_key_create")
+        self.h = h
+
+    def upload(self, stream, first_step, host_steps):
+        """Steps first_step .. of the host layout; copied before return, transformed on the stream."""
+        host = np.ascontiguousarray(host_steps, dtype=np.uint64).reshape(-1, self.step_words)
+        _check(lib().iyk_hip_bk2_key_upload(stream.h, self.h, int(first_step), host.shape[0], host.ctypes.data_as(_u64p)),
+               "iyk_hip_bk2_key_upload")
+
+    def free(self):
+        if self.h:
+            _check(lib().iyk_hip_bk2_key_free(self.h), "iyk_hip_bk2_key_free")
+        self.h = None
+
+
+def bk2_key_bytes(gpu=0):
+    """Device bytes of the live lvl2 bootstrapping keys of GPU `gpu`."""
+    v = ctypes.c_uint64()
+    _check(lib().iyk_hip_bk2_key_bytes(int(gpu), ctypes.byref(v)), "iyk_hip_bk2_key_bytes")
+    return v.value
+
+
 class Tlwe2:
     """Device-resident TLWE lvl2 ciphertexts, u64 [slots][n_in + 1]: the inputs of Stream.privks_batch."""
 
@@ -563,6 +600,20 @@ class Stream:
         p = lambda a: a.ctypes.data_as(_i32p)
         _check(lib().iyk_hip_privks_batch(self.h, key.h, tlwe2.ptr, tlwe2.slots, len(in_), p(in_), p(c), trlwe.ptr, trlwe.slots, p(out)),
                "iyk_hip_privks_batch")
+
+    def cb_rotate_batch(self, key, arena, in_, sign, off, mu, tlwe2, out):
+        """len(in_) lvl0 -> lvl2 blind rotations, asynchronous: slot out[g] of a Tlwe2 store of n_in = 2048 = a lvl2 TLWE of 2 mu[g] where
+        the phase of sign[g] * arena[in_[g]] + (0, off[g]) is positive, of 0 where it is negative, under a Bk2Key.  `arena` holds TLWEs
+        of key.n + 1 words (the arena, or Arena.from_torch of a (slots, key.n + 1) tensor).  No two jobs may write the same slot."""
+        in_, sign, out = map(_i32, (in_, sign, out))
+        off = np.ascontiguousarray(np.asarray(off, dtype=np.uint64) & np.uint64(0xFFFFFFFF), dtype=np.uint32)
+        mu = np.ascontiguousarray(mu, dtype=np.uint64)
+        assert len(in_) == len(sign) == len(off) == len(mu) == len(out)
+        if tlwe2.n_in != key.N2:
+            raise ValueError(f"the store holds TLWEs of n_in = {tlwe2.n_in}, the rotation writes n_in = {key.N2}")
+        p = lambda a: a.ctypes.data_as(_i32p)
+        _check(lib().iyk_hip_cb_rotate_batch(self.h, key.h, arena.ptr, arena.slots, len(in_), p(in_), p(sign), off.ctypes.data_as(_u32p),
+                                             mu.ctypes.data_as(_u64p), tlwe2.ptr, tlwe2.slots, p(out)), "iyk_hip_cb_rotate_batch")
 
     def trgsw_from_rows(self, trgsw, out_slot, trlwe, rows):
         """Selector out_slot[g] of a Trgsw store from the (k+1) l torus-domain rows rows[g] of a Trlwe store (row order c l + r), on the
