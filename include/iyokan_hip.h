@@ -389,6 +389,22 @@ int iyk_hip_cb_rotate_batch(iyk_hip_stream* st, const void* key, const uint32_t*
                             const int32_t* in, const int32_t* sign, const uint32_t* off, const uint64_t* mu, uint64_t* d_tlwe2,
                             uint64_t tlwe2_slots, const int32_t* out);
 
+/* The whole circuit bootstrapping of `bits` address bits as ONE checked call: the three calls above with the slot and row order of
+ * cmux.selectors_from_tlwe0.  Bit b is TLWE in[b] of the lvl0 store, taken with sign[b] (-1: the selector of the negated bit); its l
+ * rotations (mu_r = 2^(63 - (r+1) Bgbit), off = 0) go to lvl2 slots tlwe2_first + b l + r, its (k+1) l key switches to rows
+ * (b (k+1) + c) l + r of the TRLWE scratch store, its selector to slot trgsw_first + b.  Checked before the first launch: everything the
+ * three calls check, and what only their combination can — both keys and the stream of one replica, the lvl2 key's n = the initialised n
+ * (the lvl0 store is the arena: rows of n + 1 words), the lvl2 store's n_in = 2048 = the
+ * private key's n_in, bits * l lvl2 slots from tlwe2_first, at least bits (k+1) l scratch rows, bits selector slots from trgsw_first.  A
+ * violation is IYK_ERR_INVALID (IYK_ERR_STATE off the FFT path): nothing is launched and no store changes.  The stream's selector scratch
+ * and staging slot are grown to what the three calls need before the first launch as well.  Then the launches of
+ * iyk_hip_cb_rotate_batch, iyk_hip_privks_batch and iyk_hip_trgsw_from_rows, in that order, asynchronous on st; host arrays are copied
+ * before return. */
+int iyk_hip_circuit_bootstrap_batch(iyk_hip_stream* st, const void* bk2_key, const void* privks_key, const uint32_t* d_tlwe0,
+                                    uint64_t tlwe0_slots, const int32_t* in, const int32_t* sign, uint64_t* d_tlwe2, uint32_t tlwe2_n_in,
+                                    uint64_t tlwe2_slots, uint64_t tlwe2_first, uint32_t* d_trlwe, uint64_t trlwe_slots, void* d_trgsw,
+                                    uint64_t trgsw_slots, uint64_t trgsw_first, uint64_t bits);
+
 /* Kernel-only time of the most recent iyk_hip_gate_batch on this stream, from HIP events
  * recorded on the stream around the blind-rotate and key-switch launches (milliseconds).
  * Blocks until those events have completed. */

@@ -267,17 +267,35 @@ class Ram:
         slots) and receives rdata (data_width slots, the addressed word BEFORE the write).  fused=False sends the write-back as
         addr_width cmux_batch launches instead of one cmux_chain_batch: the same words.  resident=True: the addr_width selectors are in
         self.trgsw already (e.g. from selectors_from_tlwe2 on this stream): addr_trgsw is ignored and nothing is uploaded."""
-        st, w, C = self.stream, self.data_width, self.cells_per_plane
-        wdata_slots, rdata_slots = np.asarray(wdata_slots, dtype=np.int32).ravel(), np.asarray(rdata_slots, dtype=np.int32).ravel()
-        if len(wdata_slots) != w or len(rdata_slots) != w:
-            raise ValueError(f"expected {w} wdata and {w} rdata slots")
+        self._slots(wdata_slots, rdata_slots)   # both refused before anything is uploaded or enqueued
         if not resident:
-            self.trgsw.upload(st, 0, np.ascontiguousarray(addr_trgsw, dtype=np.uint32).reshape(self.addr_width, self.trgsw.words))
+            self.trgsw.upload(self.stream, 0, np.ascontiguousarray(addr_trgsw, dtype=np.uint32).reshape(self.addr_width, self.trgsw.words))
+        self.read_port(arena, rdata_slots)
+        self.write_port(arena, wren_slot, wdata_slots, rdata_slots, fused)
+
+    def _slots(self, *lists):
+        out = [np.asarray(s, dtype=np.int32).ravel() for s in lists]
+        if any(len(s) != self.data_width for s in out):
+            raise ValueError(f"expected {self.data_width} wdata and {self.data_width} rdata slots")
+        return out
+
+    def read_port(self, arena, rdata_slots):
+        """The read half of a clock (steps 1, 2: RAMUX, SEI(0) + key switch -> rdata) with the selectors that are resident in
+        self.trgsw.  Inside a netlist rdata feeds the logic that computes wren / wdata of the same clock, so the two halves are
+        enqueued apart: read_port, the gates, write_port.  Together they enqueue what clock(resident=True) enqueues."""
+        st, w = self.stream, self.data_width
+        rdata_slots, = self._slots(rdata_slots)
         # 1, 2: RAMUX, SEI(0) + key switch -> rdata
         for args in self.read_launches():
             st.cmux_batch(self.trgsw, self.trlwe, *args)
         result = [self.row(d, self.layout.result) for d in range(w)]
         st.sample_extract_index_keyswitch_batch(self.trlwe, result, np.zeros(w, dtype=np.int32), rdata_slots, arena)
+
+    def write_port(self, arena, wren_slot, wdata_slots, rdata_slots, fused=True):
+        """The write half of a clock (steps 3 - 6: MUXwoSE, the chain of every cell, extraction, refresh) with the same resident
+        selectors; rdata_slots still hold what read_port put there."""
+        st, w = self.stream, self.data_width
+        wdata_slots, rdata_slots = self._slots(wdata_slots, rdata_slots)
         # 3: HomMUXwoSE: BlindRotate(wren + wdata - mu) + BlindRotate(-wren + rdata - mu), + mu at coefficient 0 of b
         m1, m0 = zip(*(self.mux_rows(d) for d in range(w)))
         minus_mu = np.full(2 * w, (-self.mu) & 0xFFFFFFFF, dtype=np.uint32)

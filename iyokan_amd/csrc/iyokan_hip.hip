@@ -2653,6 +2653,69 @@ int iyk_hip_cb_rotate_batch(iyk_hip_stream* st, const void* key_, const uint32_t
     IYK_API_END
 }
 
+/* ---- circuit bootstrapping, whole: address bits in the arena -> TRGSW selector slots ------------------------------------------ */
+
+int iyk_hip_circuit_bootstrap_batch(iyk_hip_stream* st, const void* bk2_key, const void* privks_key, const uint32_t* d_tlwe0,
+                                    uint64_t tlwe0_slots, const int32_t* in, const int32_t* sign, uint64_t* d_tlwe2, uint32_t tlwe2_n_in,
+                                    uint64_t tlwe2_slots, uint64_t tlwe2_first, uint32_t* d_trlwe, uint64_t trlwe_slots, void* d_trgsw,
+                                    uint64_t trgsw_slots, uint64_t trgsw_first, uint64_t bits)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_circuit_bootstrap_batch")) return rc;
+    const Bk2Key* bk2 = (const Bk2Key*)bk2_key;
+    const PrivksKey* pk = (const PrivksKey*)privks_key;
+    if (!st || !bk2 || !pk || !d_tlwe0 || !in || !sign || !d_tlwe2 || !d_trlwe || !d_trgsw) return fail(IYK_ERR_INVALID, "null argument");
+    // everything the three calls below check, and what only their combination can: all of it before the first launch
+    if (st->gpu != bk2->gpu || st->gpu != pk->gpu) return fail(IYK_ERR_INVALID, "the stream and the key are on different GPUs");
+    if (bits == 0) return IYK_OK;
+    const uint64_t l = G.p.l, per = (uint64_t)(G.p.k + 1) * l;
+    if (bits > (1u << 20) / per) return fail(IYK_ERR_INVALID, "batch too large");
+    if (tlwe0_slots > (1ull << 28) || tlwe2_slots > (1ull << 28) || trlwe_slots > (1ull << 28) || trgsw_slots > (1ull << 24))
+        return fail(IYK_ERR_INVALID, "store larger than an allocation can be");
+    if (bk2->n != G.p.n) return fail(IYK_ERR_INVALID, "the lvl2 bootstrapping key's n is not the initialised n of the lvl0 store's rows");
+    if (tlwe2_n_in != (uint32_t)CB_N) return fail(IYK_ERR_INVALID, "the lvl2 store's n_in is not the 2048 the rotation writes");
+    if (tlwe2_n_in != pk->n_in) return fail(IYK_ERR_INVALID, "the lvl2 store's n_in is not the private key-switching key's");
+    if (tlwe2_first > tlwe2_slots || bits * l > tlwe2_slots - tlwe2_first) return fail(IYK_ERR_INVALID, "bits * l lvl2 slots from the first do not fit the lvl2 store");
+    if (trlwe_slots < bits * per) return fail(IYK_ERR_INVALID, "the TRLWE scratch store has fewer than bits (k+1) l rows");
+    if (trgsw_first > trgsw_slots || bits > trgsw_slots - trgsw_first) return fail(IYK_ERR_INVALID, "selector slots outside the selector store");
+    for (uint64_t b = 0; b < bits; ++b) {
+        if (!slot_ok(in[b], tlwe0_slots)) return fail(IYK_ERR_INVALID, "TLWE index outside the lvl0 store");
+        if (sign[b] != 1 && sign[b] != -1) return fail(IYK_ERR_INVALID, "sign outside {+1, -1}");
+    }
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    // the two buffers the calls below could have to grow, grown here: the selector scratch and the staging ring's slot (the largest of
+    // the three job lists).  What can still fail after the first launch is the HIP runtime itself (a copy, a launch, an event).
+    if ((rc = ensure_sel(st, bits, trgsw_polys() * NTT_N))) return rc;
+    if ((rc = ensure_stage(st, std::max({(size_t)(bits * l) * sizeof(CbJob), (size_t)(bits * per) * sizeof(PrivksJob),
+                                         (size_t)(bits * per) * sizeof(int32_t)}))))
+        return rc;
+    // slot and row order of cmux.selectors_from_tlwe0: lvl2 slot first + bit l + r, scratch row (bit (k+1) + c) l + r
+    std::vector<int32_t> r_in(bits * l), r_sign(bits * l), r_out(bits * l), p_in(bits * per), p_c(bits * per), rows(bits * per), sel(bits);
+    std::vector<uint32_t> r_off(bits * l, 0u);
+    std::vector<uint64_t> r_mu(bits * l);
+    for (uint64_t b = 0; b < bits; ++b) {
+        sel[b] = (int32_t)(trgsw_first + b);
+        for (uint64_t r = 0; r < l; ++r) {
+            r_in[b * l + r] = in[b], r_sign[b * l + r] = sign[b];
+            r_mu[b * l + r] = 1ull << (63 - (r + 1) * G.p.Bgbit);
+            r_out[b * l + r] = (int32_t)(tlwe2_first + b * l + r);
+        }
+        for (uint64_t c = 0; c <= G.p.k; ++c)
+            for (uint64_t r = 0; r < l; ++r) {
+                const uint64_t row = b * per + c * l + r;
+                p_in[row] = (int32_t)(tlwe2_first + b * l + r), p_c[row] = (int32_t)c, rows[row] = (int32_t)row;
+            }
+    }
+    if ((rc = iyk_hip_cb_rotate_batch(st, bk2, d_tlwe0, tlwe0_slots, bits * l, r_in.data(), r_sign.data(), r_off.data(), r_mu.data(), d_tlwe2,
+                                      tlwe2_slots, r_out.data())))
+        return rc;
+    if ((rc = iyk_hip_privks_batch(st, pk, d_tlwe2, tlwe2_slots, bits * per, p_in.data(), p_c.data(), d_trlwe, trlwe_slots, rows.data())))
+        return rc;
+    return iyk_hip_trgsw_from_rows(st, d_trgsw, trgsw_slots, bits, sel.data(), d_trlwe, trlwe_slots, rows.data());
+    IYK_API_END
+}
+
 /* ---- measurement ------------------------------------------------------------------------- */
 
 int iyk_hip_last_batch_timing(iyk_hip_stream* st, float* blind_rotate_ms, float* keyswitch_ms)

@@ -529,14 +529,39 @@ def two_lane_bound(nl, table, lane_cus, penalties=(PENALTY_LOADED,), levels=None
     return best
 
 
+def stage_netlist(nl, stages, s):
+    """The netlist of ONE stage of a system with CMUX memory ports (system.assign_stages), node numbers kept: every gate of another
+    stage becomes a source, so the levels of this netlist hold the gates of stage `s` alone and the slack-moving planners see no
+    path that crosses a port."""
+    from .netlist import Netlist
+
+    sub = Netlist()
+    for i, k in enumerate(nl.kinds):
+        keep = k in ("INPUT", "DFF", "OUTPUT") or stages[i] == s
+        sub.kinds.append(k if keep else "INPUT")
+        sub.ins.append(list(nl.ins[i]) if keep else [])
+    return sub
+
+
 class FrontierPlan:
     """Slot assignment + per-level, per-rank gate descriptor arrays.  `balance` (default): gates with slack are placed in
     the level where the kernels' step-shaped cost is lowest (plan_levels; `cost` = make_level_cost(hip.rotation_round()) on
-    a GPU other than the 256-CU MI355X the default describes); False: every gate at its earliest level."""
+    a GPU other than the 256-CU MI355X the default describes); False: every gate at its earliest level.  `stages` (node -> stage,
+    System.stages): the plan is made stage by stage, each from stage_netlist — stage_levels[s] is the range of self.levels that
+    stage s owns (possibly empty), and a memory port of stage s runs after it (FrontierExecutor.run(after_stage))."""
 
-    def __init__(self, nl, world=1, balance=True, cost=mi355x_level_cost, spread=True):
+    def __init__(self, nl, world=1, balance=True, cost=mi355x_level_cost, spread=True, stages=None):
         self.nl, self.world = nl, world
-        levels = plan_levels(nl, world, cost, spread) if balance else nl.levelise()
+        if stages is None:
+            levels = plan_levels(nl, world, cost, spread) if balance else nl.levelise()
+            self.stage_levels = [range(len(levels))]
+        else:
+            levels, self.stage_levels = [], []
+            for s in range(1 + max(stages)):
+                sub = stage_netlist(nl, stages, s)
+                lv = [x for x in (plan_levels(sub, world, cost, spread) if balance else sub.levelise()) if x]
+                self.stage_levels.append(range(len(levels), len(levels) + len(lv)))
+                levels += lv
         n = nl.num_nodes
         slot = [-1] * n
         nslots = 0
@@ -703,11 +728,19 @@ class FrontierExecutor:
         return self.be.read(self.plan.slot[node])
 
     # ---- one combinational evaluation -------------------------------------------------------
-    def run(self):
+    def run(self, after_stage=None):
+        """after_stage(s): called once the levels of stage s are enqueued (a staged plan's memory ports), on the same stream."""
+        if after_stage is None:
+            return self._run_levels(self.plan.levels)
+        for s, rng in enumerate(self.plan.stage_levels):
+            self._run_levels(self.plan.levels[rng.start:rng.stop])
+            after_stage(s)
+
+    def _run_levels(self, levels):
         be, w = self.be, self.world
         ctx = be.torch.cuda.stream(be.torch_stream) if hasattr(be, "torch_stream") else _null()
         with ctx:
-            for L in self.plan.levels:
+            for L in levels:
                 be.gate_batch(*L["ew_desc"])
                 if L["B"] == 0:
                     continue

@@ -42,6 +42,7 @@ EXPORTS = [
     "iyk_hip_tlwe2_alloc", "iyk_hip_tlwe2_free", "iyk_hip_tlwe2_upload", "iyk_hip_tlwe2_download", "iyk_hip_privks_batch",
     "iyk_hip_trgsw_from_rows",
     "iyk_hip_bk2_key_create", "iyk_hip_bk2_key_upload", "iyk_hip_bk2_key_free", "iyk_hip_bk2_key_bytes", "iyk_hip_cb_rotate_batch",
+    "iyk_hip_circuit_bootstrap_batch",
 ]
 
 
@@ -113,6 +114,7 @@ def lib():
         L.iyk_hip_bk2_key_bytes.argtypes = [ctypes.c_int, ctypes.POINTER(u64)]
         L.iyk_hip_cb_rotate_batch.argtypes = [_vp, _vp, _vp, u64, u64, _i32p, _i32p, _u32p, _u64p, _vp, u64, _i32p]
         L.iyk_hip_trgsw_from_rows.argtypes = [_vp, _vp, u64, u64, _i32p, _vp, u64, _i32p]
+        L.iyk_hip_circuit_bootstrap_batch.argtypes = [_vp, _vp, _vp, _vp, u64, _i32p, _i32p, _vp, u32, u64, u64, _vp, u64, _vp, u64, u64, u64]
         L.iyk_hip_last_batch_timing.argtypes = [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.iyk_hip_resident_key_bytes.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
         L.iyk_hip_level_cost_ms.restype = ctypes.c_double
@@ -626,6 +628,19 @@ class Stream:
         q = lambda a: a.ctypes.data_as(_i32p)
         _check(lib().iyk_hip_trgsw_from_rows(self.h, trgsw.ptr, trgsw.slots, len(out_slot), q(out_slot), trlwe.ptr, trlwe.slots, q(rows)),
                "iyk_hip_trgsw_from_rows")
+
+    def circuit_bootstrap_batch(self, bk2, privks_key, arena, in_, sign, tlwe2, first, trlwe_scratch, trgsw, first_slot=0):
+        """The selectors of len(in_) address bits from their lvl0 TLWEs (arena slot in_[bit], sign[bit] = -1: of the negated bit) into
+        slots first_slot .. of a Trgsw store, as ONE checked call: what cmux.selectors_from_tlwe0 composes of cb_rotate_batch, privks_batch
+        and trgsw_from_rows, with the same lvl2 slots (first + bit l + r) and scratch rows.  Every argument of all three is checked
+        before the first launch; a refusal (IykHipError) launches nothing and changes no store.  Asynchronous."""
+        in_, sign = _i32(in_).ravel(), _i32(sign).ravel()
+        if len(in_) != len(sign):
+            raise ValueError(f"{len(in_)} input slots, {len(sign)} signs")
+        p = lambda a: a.ctypes.data_as(_i32p)
+        _check(lib().iyk_hip_circuit_bootstrap_batch(self.h, bk2.h, privks_key.h, arena.ptr, arena.slots, p(in_), p(sign), tlwe2.ptr,
+                                                     tlwe2.n_in, tlwe2.slots, int(first), trlwe_scratch.ptr, trlwe_scratch.slots, trgsw.ptr,
+                                                     trgsw.slots, int(first_slot), len(in_)), "iyk_hip_circuit_bootstrap_batch")
 
     def last_batch_timing(self):
         """(blind_rotate_ms, keyswitch_ms) of the most recent batch, from HIP events on this stream."""

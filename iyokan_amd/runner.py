@@ -14,6 +14,11 @@ GPU backend, /root/reference/src/iyokan_cufhe.cpp:754-832):
 
 The engine behind it is anything with `set_nodes / get_nodes / run / tick` working on BITS: `PlainEngine` (numpy evaluator) or `CipherEngine` (a `FrontierExecutor` whose
 values are TLWE ciphertexts, wrapped with an encrypt / decrypt pair — the GPU path).
+
+A system with CMUX memory ports (load_blueprint(cmux_memories=True)) needs an engine that also has `load_rom / load_ram / ram_image`
+and runs its plan in stages: `CmuxCipherEngine` (cmux.Rom / cmux.Ram behind circuit bootstrapping, on the GPU) or `StagedBitsEngine`
+(the same staging on bits, the memories evaluated in the clear).  The memories clock during the reset cycle like everything else
+and the request's cycle-0 RAM image overwrites them afterwards, as the reference's go() does.
 """
 import numpy as np
 
@@ -71,6 +76,190 @@ class CipherEngine:
         self.ex.tick()
 
 
+class StagedPorts:
+    """run / tick of an engine whose FrontierExecutor has a staged plan and whose memories are ports (system.MemPort): in run(),
+    after the levels of stage s every port of stage s turns its address slots into read data (_port_read) on the executor's one
+    stream; in tick(), every RAM is written back (_port_write) BEFORE the DFF latch / commit copies — wren / wdata may be DFF
+    outputs, which the commit overwrites.  The write uses the address the read saw (the resident selectors)."""
+
+    def _reads(self, s):
+        for pt in self.ports:
+            if pt.stage == s:
+                self._port_read(pt)
+
+    def run(self):
+        self.ex.run(after_stage=self._reads)
+
+    def tick(self):
+        for pt in self.ports:
+            if pt.kind == "ram":
+                self._port_write(pt)
+        self.ex.tick()
+
+
+def _staged_executor(system, backend_of, balance=True, spread=True, cost=None):
+    from . import frontier
+
+    kw = {} if cost is None else {"cost": cost}
+    plan = frontier.FrontierPlan(system.nl, 1, balance, spread=spread, stages=system.stages, **kw)
+    return frontier.FrontierExecutor(plan, backend_of(plan.num_slots))
+
+
+class StagedBitsEngine(StagedPorts):
+    """The bits-only twin of CmuxCipherEngine: the staged plan of `system` on a PlainBitBackend, every memory port an array of bits
+    read and written in the clear.  What it checks is the ORDER — stages, read before write, write before commit."""
+
+    def __init__(self, system, balance=True, spread=True):
+        from . import frontier
+
+        self.ex = _staged_executor(system, frontier.PlainBitBackend, balance, spread)
+        self.nl, self.ports = system.nl, list(system.ports)
+        self.mem = {pt.name: [0] * (pt.data_width << pt.addr_width) for pt in self.ports}
+        self._addr = {}
+
+    def set_nodes(self, nids, bits):
+        if len(nids):
+            slot = self.ex.plan.slot
+            self.ex.be.write_many([slot[i] for i in nids], [int(b) for b in bits])
+
+    def get_nodes(self, nids):
+        slot = self.ex.plan.slot
+        return self.ex.be.read_many([slot[i] for i in nids])
+
+    def _port_read(self, pt):
+        slot, be = self.ex.plan.slot, self.ex.be
+        addr = sum(b << i for i, b in enumerate(be.read_many([slot[a] for a in pt.addr])))
+        self._addr[pt.name] = addr
+        word = self.mem[pt.name][addr * pt.data_width:(addr + 1) * pt.data_width]
+        be.write_many([slot[r] for r in pt.rdata], word)
+
+    def _port_write(self, pt):
+        slot, be = self.ex.plan.slot, self.ex.be
+        if pt.name in self._addr and be.read(slot[pt.wren[0]]):
+            addr = self._addr[pt.name]
+            self.mem[pt.name][addr * pt.data_width:(addr + 1) * pt.data_width] = be.read_many([slot[w] for w in pt.wdata])
+
+    def _load(self, name, image):
+        if image is not None:
+            cells = self.mem[name]
+            if len(image) > len(cells):
+                raise ValueError(f"Invalid request packet: the image of {name!r} is longer than the memory")
+            cells[:len(image)] = [int(b) for b in image]
+
+    def load_rom(self, name, request):
+        self._load(name, request.rom.get(name))
+
+    def load_ram(self, name, request):
+        image = request.ram.get(name)
+        if image is not None and len(image) != len(self.mem[name]):
+            raise ValueError("Invalid request packet: wrong length of RAM")
+        self._load(name, image)
+
+    def ram_image(self, name):
+        return list(self.mem[name])
+
+
+class CmuxCipherEngine(StagedPorts, CipherEngine):
+    """CipherEngine for a system with CMUX memory ports, on one GPU.  Per port a cmux.Rom / cmux.Ram on the executor's stream; shared
+    by all ports the lvl2 bootstrapping key `bk2`, the private key-switching key `privks_key`, one Tlwe2 store and one TRLWE scratch
+    store sized for the widest address.  A port's read is ONE Stream.circuit_bootstrap_batch from its address slots into its own
+    selector slots, then Rom.read(resident=True) / Ram.read_port into the rdata nodes' slots; nothing synchronises with the host.
+    `packet`: the encrypted request (TFHEPacket) whose TRLWE forms `rom` / `ram` fill the memories; `decrypt_ram(rows) -> bits`
+    (client.decrypt_ram_trlwe of the caller's keys) reads the result packet's RAM images out of Ram.cells().
+    The 80-bit set is refused unless words_only=True: there the restatement of the circuit bootstrapping itself misreads ROM bits
+    (DESIGN.md section 6d), so only words may be compared, never decryptions."""
+
+    def __init__(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packet=None, decrypt_ram=None, words_only=False):
+        from . import cmux, hip
+        from .params import params_80bit
+
+        p = hip.current_params()
+        p80 = params_80bit()
+        if (p.n, p.l, p.Bgbit) == (p80.n, p80.l, p80.Bgbit) and not words_only:
+            raise ValueError("CMUX memories behind circuit bootstrapping misread bits at the 80-bit set (DESIGN.md 6d): "
+                             "pass words_only=True and compare words, not decryptions")
+        if executor.world != 1:
+            raise ValueError("staged systems run on one GPU")
+        if not system.ports or len(executor.plan.stage_levels) != system.num_stages:
+            raise ValueError("the executor's plan is not the staged plan of this system (FrontierPlan(stages=system.stages))")
+        if bk2.n != p.n:
+            raise ValueError(f"the lvl2 bootstrapping key rotates TLWEs of n = {bk2.n}, the arena holds n = {p.n}")
+        CipherEngine.__init__(self, executor, encrypt, decrypt, zero_row)
+        be = executor.be
+        self.stream, self.arena, self.ports = be.stream, be._arena, list(system.ports)
+        self.bk2, self.privks_key, self.packet, self.decrypt_ram = bk2, privks_key, packet, decrypt_ram
+        N, l, per = int(p.N), int(p.l), int(p.trgsw_rows)
+        widest = max(pt.addr_width for pt in self.ports)
+        self.tlwe2 = hip.Tlwe2(hip.Bk2Key.N2, widest * l, self.stream.gpu_index)
+        self.scratch = hip.Trlwe(widest * per, self.stream.gpu_index)
+        self.mem = {}
+        for pt in self.ports:
+            if pt.kind == "rom":
+                log2w = pt.data_width.bit_length() - 1
+                if 1 << log2w != pt.data_width or pt.data_width > N:
+                    raise ValueError(f"ROM {pt.name!r}: a word of {pt.data_width} bits is no power of two up to N")
+                rows = cmux.rom_layout(pt.addr_width, log2w, N).data_rows
+                self.mem[pt.name] = cmux.Rom(self.stream, np.zeros((rows, 2 * N), dtype=np.uint32), pt.addr_width, log2w)
+            else:
+                zero = np.zeros((pt.data_width << pt.addr_width, 2 * N), dtype=np.uint32)
+                zero[:, N] = (-int(p.mu)) & 0xFFFFFFFF          # trivial TRLWEs of bit 0, as the DFFs start as trivial 0
+                self.mem[pt.name] = cmux.Ram(self.stream, zero, pt.addr_width, pt.data_width)
+
+    def _slots(self, nodes):
+        slot = self.ex.plan.slot
+        return np.array([slot[i] for i in nodes], dtype=np.int32)
+
+    def _port_read(self, pt):
+        mem = self.mem[pt.name]
+        self.stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, self._slots(pt.addr), [1] * pt.addr_width, self.tlwe2,
+                                            0, self.scratch, mem.trgsw, 0)
+        if pt.kind == "rom":
+            mem.read(None, self.arena, self._slots(pt.rdata).reshape(1, -1), resident=True)
+        else:
+            mem.read_port(self.arena, self._slots(pt.rdata))
+
+    def _port_write(self, pt):
+        self.mem[pt.name].write_port(self.arena, int(self._slots(pt.wren)[0]), self._slots(pt.wdata), self._slots(pt.rdata))
+
+    def _rows(self, table, name):
+        if self.packet is None:
+            raise ValueError("CmuxCipherEngine needs the encrypted request (packet=TFHEPacket) for its memory images")
+        return getattr(self.packet, table).get(name)
+
+    def load_rom(self, name, request):
+        rows, rom = self._rows("rom", name), self.mem[name]
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 2 * rom.N)
+            if rows.shape[0] > rom.layout.data_rows:
+                raise ValueError(f"Invalid request packet: the image of {name!r} is longer than the memory")
+            rom.trlwe.upload(self.stream, 0, rows)
+
+    def load_ram(self, name, request):
+        rows, ram = self._rows("ram", name), self.mem[name]
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 2 * ram.N)
+            if rows.shape[0] != ram.ncells:
+                raise ValueError("Invalid request packet: wrong length of RAM")
+            # the packet's order is address * width + bit, the store's one plane of 2^addr_width cells per bit
+            ram.trlwe.upload(self.stream, 0, rows.reshape(ram.cells_per_plane, ram.data_width, -1).transpose(1, 0, 2))
+
+    def ram_rows(self, name):
+        """The cells of a RAM in the packet's order, u32 [2^addr_width * width][2N] (synchronises the stream)."""
+        cells = self.mem[name].cells()
+        return np.ascontiguousarray(cells.transpose(1, 0, 2)).reshape(-1, cells.shape[2])
+
+    def ram_image(self, name):
+        if self.decrypt_ram is None:
+            raise ValueError("CmuxCipherEngine needs decrypt_ram to read a RAM image")
+        return [int(b) for b in self.decrypt_ram(self.ram_rows(name))]
+
+    def free(self):
+        for m in self.mem.values():
+            m.free()
+        self.tlwe2.free()
+        self.scratch.free()
+
+
 def _at_width(system, nl, name):
     widths = getattr(system, "at_widths", None)
     if widths and name in widths:
@@ -84,7 +273,10 @@ def run_packet(system, request, cycles=None, engine=None, skip_reset=False, on_c
     nl = getattr(system, "nl", system)
     roms = getattr(system, "rom", {})
     rams = getattr(system, "ram", {})
+    ports = getattr(system, "ports", [])
     if engine is None:
+        if ports:
+            raise ValueError("a system with CMUX memory ports needs a staged engine (StagedBitsEngine / CmuxCipherEngine)")
         engine = PlainEngine(nl)
     if cycles is None:
         cycles = request.cycles if request.cycles is not None else -1
@@ -100,6 +292,9 @@ def run_packet(system, request, cycles=None, engine=None, skip_reset=False, on_c
         if image is not None:
             order = sorted(cells)
             engine.set_nodes([cells[i] for i in order], [image[i] if i < len(image) else 0 for i in order])
+    for pt in ports:
+        if pt.kind == "rom":
+            engine.load_rom(pt.name, request)
 
     if "reset" in request.bits:
         raise ValueError("@reset cannot be set by user's input")
@@ -127,6 +322,9 @@ def run_packet(system, request, cycles=None, engine=None, skip_reset=False, on_c
                     raise ValueError("Invalid request packet: wrong length of RAM")
                 order = sorted(cells)
                 engine.set_nodes([cells[i] for i in order], [image[i] for i in order])
+            for pt in ports:
+                if pt.kind == "ram":
+                    engine.load_ram(pt.name, request)
         nids, vals = [], []
         for (port, bit), nid in nl.inputs.items():
             stream = request.bits.get(port)
@@ -157,4 +355,7 @@ def result_packet(system, engine, cycles):
     for name, cells in getattr(system, "ram", {}).items():
         order = sorted(cells)
         res.ram[name] = [int(v) for v in engine.get_nodes([cells[i] for i in order])]
+    for pt in getattr(system, "ports", []):
+        if pt.kind == "ram":
+            res.ram[pt.name] = [int(v) for v in engine.ram_image(pt.name)]
     return res

@@ -7,10 +7,12 @@ Covers the subset of Iyokan's TOML blueprint that the CAHP-with-MUX-memories sys
   [[builtin]] type = "mux-rom" (in_addr_width, out_rdata_width)       -> makeROMWithMUX  (:2517-2593)
               type = "mux-ram" (in_addr_width, in_wdata_width = out_rdata_width) -> makeRAMWithMUX (:2595-2762):
                        the precompiled 8/16/16 netlist when its JSON is at hand, else the generated DMUX/MUX form
-              type = "rom" / "ram": the reference keeps these in CMUX memories evaluated by TFHEpp on the CPU
-                       (out of scope); they have the same ports and the same observable
-                       behaviour as the MUX forms (the reference's fixtures are shared between the two), so
-                       here they are LOWERED to the MUX forms and run on the gate path
+              type = "rom" / "ram": the reference keeps these in CMUX memories evaluated by TFHEpp on the CPU; they have
+                       the same ports and the same observable behaviour as the MUX forms (the reference's fixtures are
+                       shared between the two).  load_blueprint(cmux_memories=False), the default, LOWERS them to the
+                       MUX forms on the gate path; cmux_memories=True keeps each as a memory PORT (MemPort) for
+                       cmux.Rom / cmux.Ram behind circuit bootstrapping (runner.CmuxCipherEngine): address, wren and
+                       wdata bits end at sink nodes, rdata bits start at source nodes, and every node gets a STAGE
   [connect]   "dst/port[a:b]" = "src/port[a:b]"   internal edge (dst input <- src output)
               "dst/port"      = "@name[a:b]"      system input  @name drives dst's input port
               "@name[a:b]"    = "src/port[a:b]"   system output @name reads src's output port
@@ -22,6 +24,7 @@ DAG per clock.  ROM cells are INPUT-like nodes (`nl.rom[index]`), RAM cells DFFs
 """
 import os
 import re
+from collections import namedtuple
 
 import tomli
 
@@ -109,10 +112,73 @@ def make_ram_with_mux(in_addr_width, data_width):
     return nl
 
 
+# One CMUX memory of a system (load_blueprint(cmux_memories=True)).  addr / wren / wdata: the sink nodes its inputs end at (bit 0
+# first; wren and wdata are empty for a ROM); rdata: the source nodes (kind INPUT, so they own arena slots) its read data starts at;
+# stage: the highest stage among the address drivers — rdata and everything downstream of it sit one stage later.
+MemPort = namedtuple("MemPort", "kind name addr_width data_width addr wren wdata rdata stage")
+
+
+def make_memory_port(kind, in_addr_width, data_width):
+    """The netlist side of a CMUX memory: nothing but its pins.  Inputs are INPUT nodes (aliases of their drivers once connected),
+    rdata bits INPUT nodes that the memory itself writes."""
+    nl = N.Netlist()
+    for i in range(in_addr_width):
+        nl.inputs[("addr", i)] = nl.add("INPUT")
+    if kind == "ram":
+        nl.inputs[("wren", 0)] = nl.add("INPUT")
+        for i in range(data_width):
+            nl.inputs[("wdata", i)] = nl.add("INPUT")
+    for i in range(data_width):
+        nl.outputs[("rdata", i)] = nl.add("INPUT")
+    return nl
+
+
+def assign_stages(nl, ports):
+    """(stage of every node, the ports with their stage filled in).  Sources are stage 0, a gate has the highest stage among its
+    inputs, a port the highest among its address nodes, its rdata nodes one more.  A port whose address depends on its own rdata,
+    directly or through other ports, is a combinational loop: ValueError naming it."""
+    n = nl.num_nodes
+    nl._topo()                                              # a loop among the gates alone is the netlist's own error
+    deps = [[] for _ in range(n)]
+    indeg = [0] * n
+    for i in range(n):
+        if nl.kinds[i] == "DFF":
+            continue                                        # a DFF's input belongs to the next clock
+        for j in nl.ins[i]:
+            deps[j].append(i)
+            indeg[i] += 1
+    owner = {}
+    for k, pt in enumerate(ports):
+        for r in pt.rdata:
+            owner[r] = k
+            for a in pt.addr:
+                deps[a].append(r)
+                indeg[r] += 1
+    stage = [0] * n
+    stack = [i for i in range(n) if indeg[i] == 0]
+    done = 0
+    while stack:
+        i = stack.pop()
+        done += 1
+        if i in owner:
+            stage[i] = 1 + max(stage[a] for a in ports[owner[i]].addr)
+        elif nl.kinds[i] != "DFF" and nl.ins[i]:
+            stage[i] = max(stage[j] for j in nl.ins[i])
+        for d in deps[i]:
+            indeg[d] -= 1
+            if indeg[d] == 0:
+                stack.append(d)
+    if done != n:
+        stuck = sorted({ports[k].name for r, k in owner.items() if indeg[r] > 0})
+        raise ValueError("combinational loop: the address of memory port " + ", ".join(repr(s_) for s_ in stuck)
+                         + " depends on its own rdata")
+    return stage, [pt._replace(stage=max(stage[a] for a in pt.addr)) for pt in ports]
+
+
 class System:
     """Merged netlist + where the blueprint's named things ended up."""
 
-    def __init__(self, nl, at_inputs, at_outputs, rom, ram, at_widths=None, ram_shapes=None, rom_shapes=None):
+    def __init__(self, nl, at_inputs, at_outputs, rom, ram, at_widths=None, ram_shapes=None, rom_shapes=None, ports=None, stages=None):
         self.nl = nl
         self.at_inputs = at_inputs      # (name, bit) -> node id (INPUT)
         self.at_outputs = at_outputs    # (name, bit) -> node id
@@ -121,6 +187,9 @@ class System:
         self.at_widths = at_widths or {}    # @port name -> declared width (incl. TOGND bits)
         self.ram_shapes = ram_shapes or {}  # builtin name -> (addr width, data width)
         self.rom_shapes = rom_shapes or {}
+        self.ports = ports or []            # CMUX memories (MemPort), empty unless load_blueprint(cmux_memories=True) found some
+        self.stages = stages                # node id -> stage when there are ports, else None
+        self.num_stages = 1 + max(stages) if stages else 1
 
     def at_width(self, table, name):
         if name in self.at_widths:
@@ -128,7 +197,9 @@ class System:
         return 1 + max(b for (p, b) in table if p == name)
 
 
-def load_blueprint(path, mux_ram_dir=None):
+def load_blueprint(path, mux_ram_dir=None, cmux_memories=False):
+    """cmux_memories=True: "rom" / "ram" builtins stay memories (System.ports, System.stages) instead of being lowered to the MUX
+    forms; "mux-rom" / "mux-ram" are MUX memories either way."""
     base = os.path.dirname(os.path.abspath(path))
     with open(path, "rb") as f:
         bp = tomli.load(f)
@@ -141,9 +212,14 @@ def load_blueprint(path, mux_ram_dir=None):
             parts[fdesc["name"]] = N.load_iyokanl1_json(p)
         else:
             raise ValueError(f"Invalid file type: {fdesc['type']}")
-    ram_shapes, rom_shapes = {}, {}
+    ram_shapes, rom_shapes, port_shapes = {}, {}, {}
     for b in bp.get("builtin", []):
-        if b["type"] in ("mux-rom", "rom"):
+        if cmux_memories and b["type"] in ("rom", "ram"):
+            if b["type"] == "ram" and b["in_wdata_width"] != b["out_rdata_width"]:
+                raise ValueError("Invalid RAM size; RAM with different write/read data widths is not implemented")
+            parts[b["name"]] = make_memory_port(b["type"], b["in_addr_width"], b["out_rdata_width"])
+            port_shapes[b["name"]] = (b["type"], b["in_addr_width"], b["out_rdata_width"])
+        elif b["type"] in ("mux-rom", "rom"):
             parts[b["name"]] = make_rom_with_mux(b["in_addr_width"], b["out_rdata_width"])
             rom_shapes[b["name"]] = (b["in_addr_width"], b["out_rdata_width"])
         elif b["type"] in ("mux-ram", "ram"):
@@ -229,4 +305,13 @@ def load_blueprint(path, mux_ram_dir=None):
     for name, cells in ram.items():
         nl.ram.update({(name, idx): nid for idx, nid in cells.items()})
     nl.validate()
-    return System(nl, at_inputs, at_outputs, rom, ram, at_widths, ram_shapes, rom_shapes)
+    if not port_shapes:
+        return System(nl, at_inputs, at_outputs, rom, ram, at_widths, ram_shapes, rom_shapes)
+    ports = []
+    for name, (kind, aw, dw) in port_shapes.items():
+        pins = lambda table, port, width: [table[(port, i)] + offset[name] for i in range(width)]
+        pi, po = parts[name].inputs, parts[name].outputs
+        ports.append(MemPort(kind, name, aw, dw, pins(pi, "addr", aw), pins(pi, "wren", 1) if kind == "ram" else [],
+                             pins(pi, "wdata", dw) if kind == "ram" else [], pins(po, "rdata", dw), 0))
+    stages, ports = assign_stages(nl, ports)
+    return System(nl, at_inputs, at_outputs, rom, ram, at_widths, ram_shapes, rom_shapes, ports, stages)

@@ -1,0 +1,161 @@
+"""Time per clock of a blueprint with rom / ram builtins, once as CMUX memories behind circuit bootstrapping (runner.CmuxCipherEngine) and
+once lowered to the MUX form on the gate path (runner.CipherEngine), on the same GPU in one process.  Two systems: the small ROM + RAM
+system of tests/cmux_system_cases.py and the 8-bit-address RAM of tests/golden/reftest/config-toml/ram-addr8bit.toml.
+
+Keys have the real shapes (bk2 at n = 636; the private key-switching key n_in = 2048, t = 10, basebit = 3, 2.35 GB) and uniform content:
+the kernels' time does not depend on the words.  Wall time per clock is tick() + run() over --clocks clocks between two stream
+synchronisations.  The split is taken in a second pass that synchronises after every part of a port (rotation, private key switch +
+selector assembly, read tree + extraction, write-back + refresh) and after the gate levels, so its parts add up to more than the wall time.
+
+    python tools/cmux_system_measure.py [--clocks 3] > profiles/cmux_system_ab.txt"""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import cmux_system_cases as cases  # noqa: E402
+from iyokan_amd import client, cmux, hip, runner  # noqa: E402
+from iyokan_amd.frontier import FrontierExecutor, FrontierPlan, HipBackend  # noqa: E402
+from iyokan_amd.params import params_128bit  # noqa: E402
+from iyokan_amd.system import load_blueprint  # noqa: E402
+
+
+class SplitEngine(runner.CmuxCipherEngine):
+    """the same launches, the circuit bootstrapping as its three calls, a synchronisation and a clock reading after every part"""
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.ms = {"rotation": 0.0, "private key switch + selectors": 0.0, "read tree + extraction": 0.0, "write-back + refresh": 0.0, "gates": 0.0}
+        self._t = None
+
+    def _lap(self, what):
+        self.stream.sync()
+        now = time.perf_counter()
+        self.ms[what] += (now - self._t) * 1e3
+        self._t = now
+
+    def run(self):
+        self.stream.sync()
+        self._t = time.perf_counter()
+        super().run()
+        self._lap("gates")
+
+    def tick(self):
+        self.stream.sync()
+        self._t = time.perf_counter()
+        super().tick()
+        self._lap("gates")
+
+    def _port_read(self, pt):
+        self._lap("gates")
+        p = hip.current_params()
+        l, mem, slots = int(p.l), self.mem[pt.name], self._slots(pt.addr)
+        in_ = np.repeat(slots, l)
+        mu = np.tile(np.array([1 << (63 - (r + 1) * int(p.Bgbit)) for r in range(l)], dtype=np.uint64), len(slots))
+        self.stream.cb_rotate_batch(self.bk2, self.arena, in_, [1] * len(in_), [0] * len(in_), mu, self.tlwe2, np.arange(len(in_)))
+        self._lap("rotation")
+        cmux.selectors_from_tlwe2(self.stream, self.privks_key, self.tlwe2, 0, pt.addr_width, self.scratch, mem.trgsw, 0)
+        self._lap("private key switch + selectors")
+        if pt.kind == "rom":
+            mem.read(None, self.arena, self._slots(pt.rdata).reshape(1, -1), resident=True)
+        else:
+            mem.read_port(self.arena, self._slots(pt.rdata))
+        self._lap("read tree + extraction")
+
+    def _port_write(self, pt):
+        self._lap("gates")
+        super()._port_write(pt)
+        self._lap("write-back + refresh")
+
+
+def engine(keys, sysm, kind, bk2=None, pk=None):
+    import torch
+
+    plan = FrontierPlan(sysm.nl, 1, stages=sysm.stages)
+    be = HipBackend(plan.num_slots, keys.params, torch.device("cuda", 0))
+    enc, dec, zero = (lambda bits: client.encrypt_bits(keys, bits, seed=5)), (lambda rows: client.decrypt_bits(keys, rows)), client.trivial(keys.params, 0)
+    ex = FrontierExecutor(plan, be)
+    if kind == "mux":
+        return runner.CipherEngine(ex, enc, dec, zero), be, plan
+    cls = SplitEngine if kind == "split" else runner.CmuxCipherEngine
+    return cls(sysm, ex, enc, dec, zero, bk2, pk), be, plan
+
+
+def clocks(eng, be, sysm, n):
+    rng = np.random.default_rng(1)
+    nids = list(sysm.nl.inputs.values())
+    eng.set_nodes(nids, rng.integers(0, 2, size=len(nids)))
+    eng.run()
+    eng.tick()
+    eng.run()                                                                       # one clock to warm up
+    be.sync()
+    t = time.perf_counter()
+    for _ in range(n):
+        eng.tick()
+        eng.run()
+    be.sync()
+    return (time.perf_counter() - t) * 1e3 / max(n, 1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clocks", type=int, default=3)
+    args = ap.parse_args()
+    keys = client.keygen(params_128bit(), seed=1)
+    hip.initialize(keys, device_ids=(0,))
+    st = hip.Stream(0)
+    rng = np.random.default_rng(2)
+    bk2 = hip.Bk2Key(keys.params.n)
+    for first in range(0, bk2.n, 100):
+        count = min(100, bk2.n - first)
+        bk2.upload(st, first, rng.integers(0, 1 << 63, size=(count, bk2.step_words), dtype=np.uint64))
+    pk = hip.PrivKsKey(2048, 10, 3)
+    window = rng.integers(0, 1 << 32, size=(8192, pk.words), dtype=np.uint64).astype(np.uint32)
+    for first in range(0, pk.rows, 8192):
+        pk.upload(st, first, window[:min(8192, pk.rows - first)])
+    st.sync()
+    print(f"build {hip.build_id()}; {args.clocks} clocks per figure; 128-bit set; bk2 n = {bk2.n}, private key n_in = 2048, t = 10, basebit = 3")
+    tmp = tempfile.mkdtemp()
+    systems = [("small: ROM 3-bit address x 4 bits, RAM 2-bit address x 2 bits, 12 gates", cases.write_blueprint(tmp)),
+               ("ram-addr8bit: RAM 8-bit address x 8 bits", os.path.join(ROOT, "tests", "golden", "reftest", "config-toml", "ram-addr8bit.toml"))]
+    for title, path in systems:
+        print(f"\n== {title}")
+        lowered, ported = load_blueprint(path), load_blueprint(path, cmux_memories=True)
+        eng, be, plan = engine(keys, lowered, "mux")
+        ms = clocks(eng, be, lowered, args.clocks)
+        print(f"lowered MUX form : {ms:9.2f} ms per clock   ({lowered.nl.rotations()} rotations, {len(plan.levels)} levels)")
+        be.close()
+        eng, be, plan = engine(keys, ported, "cmux", bk2, pk)
+        ms = clocks(eng, be, ported, args.clocks)
+        rot = sum(pt.addr_width for pt in ported.ports) * int(keys.params.l)
+        print(f"CMUX memories    : {ms:9.2f} ms per clock   ({ported.nl.rotations()} gate rotations, {len(plan.levels)} levels, "
+              f"{len(ported.ports)} ports, {rot} lvl2 rotations in {len(ported.ports)} batches)")
+        eng.free()
+        be.close()
+        eng, be, _ = engine(keys, ported, "split", bk2, pk)
+        clocks(eng, be, ported, 0)
+        for k in eng.ms:
+            eng.ms[k] = 0.0
+        n = max(1, args.clocks - 1)
+        for _ in range(n):
+            eng.tick()
+            eng.run()
+        for k, v in eng.ms.items():
+            print(f"    {k:32s} {v / n:9.2f} ms per clock (synchronised after every part)")
+        eng.free()
+        be.close()
+    bk2.free()
+    pk.free()
+    st.destroy()
+    hip.cleanup()
+
+
+if __name__ == "__main__":
+    main()
