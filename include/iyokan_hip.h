@@ -433,7 +433,15 @@ int iyk_hip_timing_log_end(iyk_hip_stream* st, uint64_t* batches, double* blind_
  * 2, the default for wider batches since round 6 — the one that takes the digits in pairs and selects a PRE-ADDED row by
  * address (a table of 16 sums per digit pair, built on the GPU from the resident key-switching key by the first wide batch:
  * + 136 MB per GPU, counted by iyk_hip_resident_key_bytes from then on); all three subtract the same rows mod 2^32, so
- * they agree word for word. */
+ * they agree word for word.  IYK_HIP_KS_KERNEL = 3 forces, at any batch size, the key switch as an integer matrix product on the
+ * matrix cores (one-hot digits x the key's rows in four signed base-256 planes, v_mfma_i32_32x32x32_i8: nothing is rounded, the
+ * words are the same again; no initialisation launch, no atomics).  Unset, batches of KS_MATRIX_MIN_JOBS (csrc/dispatch.hpp:
+ * 4 608) gates or more run it, batches of 4 097 gates up to there the table of 2, narrower ones the shared-gates form of 1.
+ * Its operand (73.4 MB per GPU at the 128-bit set, 67.1 MB at the 80-bit set) is built from the resident key by the first such
+ * batch, on that batch's stream with stream-ordered allocation — no call blocks, the null stream is not touched — and counted by
+ * iyk_hip_resident_key_bytes from then on.  IYK_HIP_KS_MATRIX_MAX_BYTES (read when the operand is first asked for) caps it: below
+ * the operand's size, or when the allocation fails, the GPU remembers that it has no operand until the next iyk_hip_init and
+ * every batch runs the form 0 / 1 / 2 would have chosen; no batch fails for it. */
 int iyk_hip_ntt_path(void);
 
 /* Round 4: return value 2 = the default since — both rotation kernels (a wave per rotation for full rounds, a workgroup per
@@ -500,7 +508,8 @@ const char* iyk_hip_init_profile(void);
 /* Bytes of device memory holding keys on one GPU: the key spectra (FFT path) or the NTT-domain BK (field / integer paths), the
  * padded KSK and the tables — 179.8 MB at the 128-bit set on the default path — plus, once a cross-check kernel has asked for
  * it, the field form of the BK (62.5 MB; round 5 built and kept it at init: 242.3 MB) and, once a batch wider than 4 096 gates has
- * run, the key switch's table of pre-added rows (136 MB; IYK_HIP_KS_KERNEL above). */
+ * run on the table kernel, the key switch's table of pre-added rows (136 MB) and, once a batch has run the matrix form, its int8
+ * operand (73.4 MB; both: IYK_HIP_KS_KERNEL above). */
 int iyk_hip_resident_key_bytes(uint64_t* out);
 
 #ifdef __cplusplus

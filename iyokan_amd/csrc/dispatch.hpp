@@ -119,6 +119,51 @@ inline KsPlan ks_plan(int kind, int shared_max, int shared_wg, int njobs, int T,
     return plan(KS_FORM_KIND0, KS_KIND0_GATES, 64, 512);
 }
 
+// ---- key switch as an integer matrix product (keyswitch_mfma.hpp) ---------------------------------------------------------------
+//
+// out = (0,..,0,b') - A x B mod 2^32: A[gate][k] is the one-hot form of the gate's digits, B[k][word] the key rows, each 32-bit word
+// split into four signed base-256 planes so that the product runs on the int8 matrix instruction (32 x 32 x 32 per step).
+//   k = 4 (i t + j) + v,  v = the digit's value: v = u + 1 selects row KSK[i][j][u]; v = 0 is padding (a zero row: digit 0 subtracts
+//   nothing), so that a digit expands to one dword, 1 << 8 v, and a k-step of 32 is 8 whole digits.
+// The operand is stored as the matrix instruction reads it: a CHUNK of 4 KB per (group of 32 words, k-step), in it one tile of 1 KB
+// per plane, in it 16 bytes per lane (lane = 32 (half of the k-step) + word of the group): 16 consecutive k of one column.
+constexpr int KS_MATRIX_MIN_JOBS = 4608;   // IYK_HIP_KS_KERNEL unset: batches from here on run the matrix form (sweep: profiles/ks_matrix_ab.txt)
+constexpr int KS_MATRIX_GATES = 256;       // gates per workgroup of keyswitch_mfma_kernel: four waves of KS_MATRIX_WAVE_GATES
+constexpr int KS_MATRIX_WAVE_GATES = 64;
+constexpr int KS_MATRIX_WORDS = 32;        // words per workgroup (x 4 planes): grid y
+constexpr long KS_MATRIX_TILE_BYTES = 1024, KS_MATRIX_CHUNK_BYTES = 4 * KS_MATRIX_TILE_BYTES;
+
+constexpr int ks_matrix_ksteps(int T) { return KS_N * T * 4 / 32; }
+constexpr int ks_matrix_word_groups(int nc) { return nc * 128 / KS_MATRIX_WORDS; }
+constexpr long ks_matrix_bytes(int T, int nc) { return (long)ks_matrix_word_groups(nc) * ks_matrix_ksteps(T) * KS_MATRIX_CHUNK_BYTES; }
+// where the chunk of (word group, k-step) starts
+constexpr long ks_matrix_chunk_offset(int T, int word_group, int kstep) { return ((long)word_group * ks_matrix_ksteps(T) + kstep) * KS_MATRIX_CHUNK_BYTES; }
+// byte of (column k, word, plane); THE layout: the build kernel writes through it, the product kernel and the tests read through it
+constexpr long ks_matrix_offset_k(int T, int k, int word, int plane)
+{
+    return ks_matrix_chunk_offset(T, word / KS_MATRIX_WORDS, k / 32) + plane * KS_MATRIX_TILE_BYTES +
+           (long)((k % 32 / 16) * 32 + word % KS_MATRIX_WORDS) * 16 + k % 16;
+}
+constexpr int ks_matrix_k(int T, int i, int j, int u) { return 4 * (i * T + j) + u + 1; }
+constexpr long ks_matrix_offset(int T, int i, int j, int u, int word, int plane) { return ks_matrix_offset_k(T, ks_matrix_k(T, i, j, u), word, plane); }
+// plane p of a word: signed base-256 digits s_p in [-128, 127] with sum s_p 256^p = w mod 2^32 (carries propagated, the top one dropped)
+constexpr int ks_signed_plane(unsigned w, int plane)
+{
+    unsigned carry = 0, d = 0;
+    for (int p = 0; p <= plane; ++p) {
+        d = ((w >> (8 * p)) & 0xFFu) + carry;   // 0 .. 256
+        carry = d >= 128u ? 1u : 0u;
+    }
+    return (int)d - (d >= 128u ? 256 : 0);
+}
+// Does the batch run the matrix form?  kind_env: what IYK_HIP_KS_KERNEL names, negative where it is unset or names nothing.
+// Explicit 0 .. 2 keep ks_plan's meaning; the form exists for the (t, nc) of the two parameter sets only.
+constexpr bool ks_matrix_form(int kind_env, int njobs, int T, int nc)
+{
+    const bool instantiated = (T == 7 && nc == 5) || (T == 8 && nc == 4);
+    return instantiated && (kind_env == 3 || (kind_env < 0 && njobs >= KS_MATRIX_MIN_JOBS));
+}
+
 // ---- private key switch (privks.hpp) --------------------------------------------------------------------------------------------
 
 constexpr int PRIVKS_WG_PER_CU = 4;   // workgroups of 256 lanes a launch aims to have per CU: 16 waves, each with up to PRIVKS_UNROLL rows in flight

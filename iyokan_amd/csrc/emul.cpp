@@ -1170,6 +1170,22 @@ int iyk_emul_blind_rotate(const iyk_params* p, const uint32_t* lin, const uint64
     else return -1;
     return 0;
 }
+/* the matrix form of the key switch (dispatch.hpp): does a batch run it (kind_env < 0: IYK_HIP_KS_KERNEL unset), the threshold, the
+ * operand's size and layout (byte of (i, j, u, word, plane), u = digit value - 1; of (column k, word, plane)), the signed planes */
+int iyk_emul_ks_matrix_form(int kind_env, int njobs, int T, int nc) { return dispatch::ks_matrix_form(kind_env, njobs, T, nc) ? 1 : 0; }
+int iyk_emul_ks_matrix_min_jobs(void) { return dispatch::KS_MATRIX_MIN_JOBS; }
+int iyk_emul_ks_matrix_gates(int per_wave) { return per_wave ? dispatch::KS_MATRIX_WAVE_GATES : dispatch::KS_MATRIX_GATES; }
+int64_t iyk_emul_ks_matrix_bytes(int T, int nc) { return dispatch::ks_matrix_bytes(T, nc); }
+int64_t iyk_emul_ks_matrix_offset(int T, int i, int j, int u, int word, int plane) { return dispatch::ks_matrix_offset(T, i, j, u, word, plane); }
+void iyk_emul_ks_matrix_offsets_k(int T, const int* k, int word, int plane, int count, int64_t* out)
+{
+    for (int c = 0; c < count; ++c) out[c] = dispatch::ks_matrix_offset_k(T, k[c], word, plane);
+}
+void iyk_emul_ks_signed_planes(const uint32_t* w, int count, int8_t* planes /* [count][4] */)
+{
+    for (int c = 0; c < count; ++c)
+        for (int p = 0; p < 4; ++p) planes[4 * c + p] = (int8_t)dispatch::ks_signed_plane(w[c], p);
+}
 /* privks_plan: splits and words per split of a private key-switch launch */
 void iyk_emul_privks_plan(int njobs, int n_words, int cus, int out[2])
 {

@@ -42,6 +42,7 @@
 #endif
 #include "cmux_fft.hpp"
 #include "privks.hpp"
+#include "keyswitch_mfma.hpp"
 #include "cb_rotate.hpp"
 
 using namespace iyk;
@@ -84,6 +85,13 @@ struct Device {
     u64* bk_ntt = nullptr;   // NTT-domain BK: u64 residues mod 2^64-2^32+1, or doubles mod p = 3*2^48+1097729 (fp path)
     u32* ksk = nullptr;
     u32* ksk_lut = nullptr;  // pre-added key-switch rows (keyswitch_lut_kernel), built on first use: ensure_ks_lut
+    // the int8 operand of keyswitch_mfma_kernel, built on first use on the asking stream (ensure_ks_matrix): the pointer is published
+    // once the build is enqueued, ks_mat_ready orders every other stream behind it; ks_mat_bytes counts in iyk_hip_resident_key_bytes
+    unsigned char* ks_mat = nullptr;
+    hipEvent_t ks_mat_ready = nullptr;
+    uint64_t ks_mat_bytes = 0;
+    uint64_t ks_mat_id = 0;       // of the live operand; never 0, never reused (a later operand may get the same address)
+    bool ks_mat_failed = false;   // allocation failed or IYK_HIP_KS_MATRIX_MAX_BYTES was below the operand: ks_plan's forms from then on
     u64* tw_fwd = nullptr;   // u64 or double tables, same size
     u64* tw_inv = nullptr;
     fp::NttConsts* fpc = nullptr;  // FP path: 32-point twiddles + twists, read by scalar loads
@@ -104,6 +112,12 @@ struct Device {
         if (ksk) (void)hipFree(ksk);
         if (ksk_lut) (void)hipFree(ksk_lut);
         ksk_lut = nullptr;
+        if (ks_mat) (void)hipFree(ks_mat);
+        if (ks_mat_ready) (void)hipEventDestroy(ks_mat_ready);
+        ks_mat = nullptr;
+        ks_mat_ready = nullptr;
+        ks_mat_bytes = 0;
+        ks_mat_failed = false;
         if (tw_fwd) (void)hipFree(tw_fwd);
         if (tw_inv) (void)hipFree(tw_inv);
         if (fpc) (void)hipFree(fpc);
@@ -187,6 +201,7 @@ struct iyk_hip_stream {
     u32* d_sel = nullptr;   // iyk_hip_trgsw_from_rows: the gathered torus rows of the selectors of one call, sel_cap selectors
     size_t sel_cap = 0;
     u32* d_rot = nullptr;
+    uint64_t ks_mat_seen = 0;   // Device::ks_mat_id of the key-switch operand this stream is already ordered behind (ensure_ks_matrix)
     u32* d_abar = nullptr;  // mod-switched rotation inputs, one row of ABAR_STRIDE words per job
     size_t rot_cap = 0;
     // timing of the most recent batch
@@ -470,6 +485,60 @@ int launch_keyswitch_lut(iyk_hip_stream* st, u32* d_arena, const KsJob* d_jobs, 
     HIP_TRY(hipGetLastError());
     return IYK_OK;
 }
+// The int8 operand of keyswitch_mfma_kernel on the stream's GPU, built from the resident KSK on first use: allocated stream-ordered
+// and built on the CALLER's stream (nothing blocks, nothing touches the null stream); other streams wait for the build's event
+// once.  false: no operand (IYK_HIP_KS_MATRIX_MAX_BYTES below its size, or no memory) — remembered for the device, the error
+// cleared, and the batch runs what ks_plan says.
+template <int T, int NC>
+bool ensure_ks_matrix(iyk_hip_stream* st)
+{
+    Device& D = G.devs[st->gpu];
+    if (!__atomic_load_n(&D.ks_mat, __ATOMIC_ACQUIRE)) {
+        std::lock_guard<std::mutex> lock(G.field_mu);
+        if (!D.ks_mat) {
+            if (D.ks_mat_failed) return false;
+            const uint64_t bytes = (uint64_t)ks_matrix_bytes(T, NC);
+            const char* cap = std::getenv("IYK_HIP_KS_MATRIX_MAX_BYTES");
+            void* d = nullptr;
+            hipEvent_t ev = nullptr;
+            bool ok = !(cap && std::strtoull(cap, nullptr, 10) < bytes);
+            ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+            ok = ok && hipMallocAsync(&d, bytes, st->s) == hipSuccess;
+            if (ok) {
+                hipLaunchKernelGGL(ks_matrix_build_kernel<T>, dim3((unsigned)(bytes / KS_MATRIX_CHUNK_BYTES)), dim3(256), 0, st->s,
+                                   (const u32*)D.ksk, (unsigned char*)d, G.ksk_stride);
+                ok = hipGetLastError() == hipSuccess && hipEventRecord(ev, st->s) == hipSuccess;
+            }
+            if (!ok) {
+                (void)hipGetLastError();   // the batch goes on without the operand
+                if (d) (void)hipFreeAsync(d, st->s);
+                if (ev) (void)hipEventDestroy(ev);
+                D.ks_mat_failed = true;
+                return false;
+            }
+            D.ks_mat_ready = ev;
+            D.ks_mat_bytes = bytes;
+            static uint64_t next_id = 0;   // under G.field_mu
+            D.ks_mat_id = ++next_id;
+            st->ks_mat_seen = D.ks_mat_id;   // the builder's own stream is ordered behind the build already
+            __atomic_store_n(&D.ks_mat, (unsigned char*)d, __ATOMIC_RELEASE);
+        }
+    }
+    if (st->ks_mat_seen != D.ks_mat_id) {
+        if (hipStreamWaitEvent(st->s, D.ks_mat_ready, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        st->ks_mat_seen = D.ks_mat_id;
+    }
+    return true;
+}
+// What IYK_HIP_KS_KERNEL names for ks_matrix_form: its digit, -1 where it is unset or names nothing
+int ks_kind_env()
+{
+    const char* force = std::getenv("IYK_HIP_KS_KERNEL");
+    return force && force[0] >= '0' && force[0] <= '3' ? force[0] - '0' : -1;
+}
 // ks_plan for this batch: IYK_HIP_KS_KERNEL ("0" .. "2"), IYK_HIP_KS_SHARED_MAX and IYK_HIP_KS_SHARED_WG are read per batch (A/B, tests),
 // like IYK_HIP_ROT_KERNEL
 KsPlan ks_plan_of_batch(const Device& D, int njobs, int T)
@@ -498,6 +567,14 @@ int launch_keyswitch_t(iyk_hip_stream* st, u32* d_arena, const KsJob* d_jobs, in
 {
     const Device& D = G.devs[st->gpu];
     const iyk_params& p = G.p;
+    if constexpr (NC != 0) {   // the matrix form writes every word itself: no initialisation launch, no atomics
+        if (ks_matrix_form(ks_kind_env(), njobs, T, NC) && (int)((G.ksk_stride + 127u) / 128u) == NC && ensure_ks_matrix<T, NC>(st)) {
+            hipLaunchKernelGGL((keyswitch_mfma_kernel<T, NC>), dim3((unsigned)((njobs + KS_MATRIX_GATES - 1) / KS_MATRIX_GATES), (unsigned)ks_matrix_word_groups(NC)),
+                               dim3(256), KSM_LDS_BYTES, st->s, (const u32*)st->d_rot, d_jobs, njobs, (const unsigned char*)D.ks_mat, d_arena, p.n);
+            HIP_TRY(hipGetLastError());
+            return IYK_OK;
+        }
+    }
     hipLaunchKernelGGL(keyswitch_init_kernel, dim3((unsigned)njobs), dim3(KS_THREADS), 0, st->s,
                        (const u32*)st->d_rot, d_jobs, d_arena, p.n);
     HIP_TRY(hipGetLastError());
@@ -1095,7 +1172,10 @@ int iyk_hip_resident_key_bytes(uint64_t* out)
     uint64_t lut = 0;     // likewise the table of pre-added key-switch rows (IYK_HIP_KS_KERNEL=2)
     for (const Device& D : G.devs)
         if (__atomic_load_n(&D.ksk_lut, __ATOMIC_ACQUIRE)) lut = G.ks_lut_bytes;
-    *out = G.key_bytes + field + lut;
+    uint64_t mat = 0;     // and the int8 operand of the matrix form (IYK_HIP_KS_KERNEL=3, the default for wide batches)
+    for (const Device& D : G.devs)
+        if (__atomic_load_n(&D.ks_mat, __ATOMIC_ACQUIRE)) mat = D.ks_mat_bytes;
+    *out = G.key_bytes + field + lut + mat;
     return IYK_OK;
 }
 
