@@ -33,6 +33,7 @@
 // reference's ROM / RAM ports (TaskTFHEppCB*, /root/reference/src/iyokan_tfhepp.hpp:194-236), restated from the published algorithm.
 #pragma once
 #include "blind_rotate_core.hpp"   // TwistTab / make_twist, ntt32.hpp, goldilocks.hpp
+#include "jobs.hpp"                // CbJob, CB_MAX_N0
 
 namespace iyk {
 
@@ -40,18 +41,10 @@ static constexpr int CB_N = 2048;                 // N2
 static constexpr int CB_LANES = 256;
 static constexpr int CB_ROWS = 8;                 // (k+1) l2
 static constexpr int CB_PSTRIDE = 2112;           // u64 words of one polynomial slot of the exchange buffer: max(32*65, 64*33, 2048)
-static constexpr u32 CB_MAX_N0 = 2047;            // n + 1 mod-switched words fit the LDS abar array
 static constexpr size_t CB_STEP_WORDS = (size_t)2 * CB_ROWS * 2 * CB_N;   // u64 words of one key step: [2 halves][8 rows][2 cols][N2]
 static constexpr size_t CB_TORUS_STEP_WORDS = (size_t)CB_ROWS * 2 * CB_N; // u64 words of one step of the host key
 static constexpr size_t CB_LDS_WORDS = 2 * CB_N + 4 * CB_PSTRIDE + 2 * CB_N + CB_N / 2;   // u64: acc, buf, twf + twi, abar (u32 [2048])
 static constexpr size_t CB_LDS_BYTES = CB_LDS_WORDS * sizeof(u64);
-
-struct CbJob {
-    int32_t in, sign;
-    uint32_t off;
-    int32_t out;
-    uint64_t mu;
-};
 
 template <int L2, int BGBIT2>
 struct CbConsts {

@@ -16,12 +16,9 @@
 // (/root/reference/src/iyokan_tfhepp.hpp:267,282-291,426-443,627); TFHEpp's product is an inexact FP64 FFT, this one is exact.
 #pragma once
 #include "blind_rotate_fft.hpp"
+#include "jobs.hpp"   // CmuxJob, CmuxChainJob, CMUX_CHAIN_MAX_STEPS
 
 namespace iyk {
-
-struct CmuxJob {
-    int32_t sel, in0, in1, rot, out;
-};
 
 namespace fft {
 
@@ -79,13 +76,8 @@ IYK_HD void cmux_acc_replace16(int L, const u32* mem_c, const cplx (&hi)[8], con
 
 }  // namespace fft
 
-// acc = T[src]; steps CMUXes against T[mem] with selector slots sel0 .. sel0 + steps - 1, oriented by the bits of pattern; T[out] = acc
-struct CmuxChainJob {
-    int32_t sel0, steps;
-    uint32_t pattern;
-    int32_t src, mem, out;
-};
-static constexpr int CMUX_CHAIN_MAX_STEPS = 32;   // the bits of pattern
+// A chain job (jobs.hpp: CmuxChainJob): acc = T[src]; steps CMUXes against T[mem] with selector slots sel0 .. sel0 + steps - 1, oriented
+// by the bits of pattern; T[out] = acc
 
 #if defined(__HIPCC__)
 // One wavefront per job, BR_WAVES jobs per workgroup, the LDS map of blind_rotate_fft_kernel (kernels_fft.hpp, included first).  The

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <array>
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -17,6 +18,7 @@
 #include "blind_rotate_fft.hpp"
 #include "cmux_fft.hpp"
 #include "fft256.hpp"
+#include "batch_args.hpp"
 #include "dispatch.hpp"
 #include "privks.hpp"
 #include "cb_rotate.hpp"
@@ -1322,5 +1324,134 @@ int iyk_emul_cb_rotate(uint32_t n, uint32_t l2, uint32_t Bgbit2, const uint32_t*
     if (l2 != 4 || Bgbit2 != 9 || n == 0 || n > CB_MAX_N0 || (sign != 1 && sign != -1)) return -1;
     cb_rotate<4, 9>(n, w, CbJob{0, sign, off, 0, mu}, bk_ntt, out);
     return 0;
+}
+}
+
+/* ---- batch_args.hpp: the argument checks and job lists of the batch entry points ------------------------------------------------
+ * Every iyk_emul_check_* returns the refusal's code and writes its text ("" when accepted) into msg[msg_cap].  An accepted call also
+ * writes the job lists it built, one after the other, as 32-bit words into words[words_cap] (a list that does not fit is left out) and
+ * the number of jobs of each list into counts[]. */
+namespace {
+struct CheckOut {
+    char* msg;
+    size_t msg_cap;
+    uint32_t* words;
+    uint64_t room;
+    uint64_t* counts;
+    int finish(const args::Refusal& r)
+    {
+        std::snprintf(msg, msg_cap, "%s", r.text ? r.text : "");
+        return r.code;
+    }
+    template <class J>
+    void list(const std::vector<J>& v)
+    {
+        static_assert(sizeof(J) % 4 == 0, "a job is whole words");
+        const uint64_t n = v.size() * (sizeof(J) / 4);
+        *counts++ = v.size();
+        if (n > room) return;
+        if (n) std::memcpy(words, v.data(), n * 4);
+        words += n, room -= n;
+    }
+};
+}  // namespace
+#define IYK_CHECK_OUT char *msg, uint64_t msg_cap, uint32_t *words, uint64_t words_cap, uint64_t *counts
+#define IYK_CHECK_OUT_INIT CheckOut o{msg, (size_t)msg_cap, words, words_cap, counts}
+extern "C" {
+int iyk_emul_check_slot_list(uint64_t count, const int32_t* slots, uint64_t arena_slots, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    return o.finish(args::check_slot_list(count, slots, arena_slots));
+}
+int iyk_emul_check_gate_batch(const iyk_params* p, int debug, uint64_t arena_slots, uint64_t count, const int32_t* ops, const int32_t* in0,
+                              const int32_t* in1, const int32_t* in2, const int32_t* out, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    std::vector<RotJob> rot;
+    std::vector<KsJob> ks;
+    std::vector<EwJob> ew;
+    const args::Refusal r = args::check_gate_batch(*p, debug != 0, arena_slots, count, ops, in0, in1, in2, out, rot, ks, ew);
+    if (!r) o.list(rot), o.list(ks), o.list(ew);
+    return o.finish(r);
+}
+int iyk_emul_check_rotate_only(uint64_t arena_slots, uint64_t count, const int32_t* ia, const int32_t* ib, const int32_t* sa, const int32_t* sb,
+                               const uint32_t* off, uint64_t out_rows, const int32_t* out_index, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    std::vector<RotJob> rot;
+    const args::Refusal r = args::check_rotate_only(arena_slots, count, ia, ib, sa, sb, off, out_rows, out_index, rot);
+    if (!r) o.list(rot);
+    return o.finish(r);
+}
+int iyk_emul_check_sample_extract_keyswitch(uint64_t trlwe_slots, uint64_t arena_slots, uint64_t count, const int32_t* trlwe_index,
+                                            const int32_t* coeff_index, const int32_t* out_slot, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    std::vector<KsJob> ks;
+    const args::Refusal r = args::check_sample_extract_keyswitch(trlwe_slots, arena_slots, count, trlwe_index, coeff_index, out_slot, ks);
+    if (!r) o.list(ks);
+    return o.finish(r);
+}
+int iyk_emul_check_cmux_batch(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* sel, const int32_t* in0, const int32_t* in1,
+                              const int32_t* rot, const int32_t* out, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    std::vector<CmuxJob> jobs;
+    const args::Refusal r = args::check_cmux_batch(trgsw_slots, trlwe_slots, count, sel, in0, in1, rot, out, jobs);
+    if (!r) o.list(jobs);
+    return o.finish(r);
+}
+int iyk_emul_check_cmux_chain_batch(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* sel0, const int32_t* steps,
+                                    const uint32_t* pattern, const int32_t* src, const int32_t* mem, const int32_t* out, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    std::vector<CmuxChainJob> jobs;
+    const args::Refusal r = args::check_cmux_chain_batch(trgsw_slots, trlwe_slots, count, sel0, steps, pattern, src, mem, out, jobs);
+    if (!r) o.list(jobs);
+    return o.finish(r);
+}
+int iyk_emul_check_trlwe_add_batch(uint64_t trlwe_slots, uint64_t count, const int32_t* a, const int32_t* b, const int32_t* out, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    std::vector<TrlweAddJob> jobs;
+    const args::Refusal r = args::check_trlwe_add_batch(trlwe_slots, count, a, b, out, jobs);
+    if (!r) o.list(jobs);
+    return o.finish(r);
+}
+int iyk_emul_check_privks_batch(uint32_t k, uint64_t tlwe2_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* in, const int32_t* c,
+                                const int32_t* out, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    std::vector<PrivksJob> jobs;
+    const args::Refusal r = args::check_privks_batch(k, tlwe2_slots, trlwe_slots, count, in, c, out, jobs);
+    if (!r) o.list(jobs);
+    return o.finish(r);
+}
+int iyk_emul_check_trgsw_from_rows(const iyk_params* p, uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* out_slot,
+                                   const int32_t* rows, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    return o.finish(args::check_trgsw_from_rows(*p, trgsw_slots, trlwe_slots, count, out_slot, rows));
+}
+int iyk_emul_check_cb_rotate_batch(uint64_t tlwe0_slots, uint64_t tlwe2_slots, uint64_t count, const int32_t* in, const int32_t* sign,
+                                   const uint32_t* off, const uint64_t* mu, const int32_t* out, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    std::vector<CbJob> jobs;
+    const args::Refusal r = args::check_cb_rotate_batch(tlwe0_slots, tlwe2_slots, count, in, sign, off, mu, out, jobs);
+    if (!r) o.list(jobs);
+    return o.finish(r);
+}
+/* lists: the rotations, the private key switches, the scratch rows of every selector, the selector slots */
+int iyk_emul_check_circuit_bootstrap_batch(const iyk_params* p, uint32_t bk2_n, uint32_t privks_n_in, uint64_t tlwe0_slots, const int32_t* in,
+                                           const int32_t* sign, uint32_t tlwe2_n_in, uint64_t tlwe2_slots, uint64_t tlwe2_first, uint64_t trlwe_slots,
+                                           uint64_t trgsw_slots, uint64_t trgsw_first, uint64_t bits, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    args::CbLists l;
+    const args::Refusal r = args::check_circuit_bootstrap_batch(*p, bk2_n, privks_n_in, tlwe0_slots, in, sign, tlwe2_n_in, tlwe2_slots, tlwe2_first,
+                                                                trlwe_slots, trgsw_slots, trgsw_first, bits, l);
+    if (!r) o.list(l.rot), o.list(l.privks), o.list(l.rows), o.list(l.sel);
+    return o.finish(r);
 }
 }

@@ -6,7 +6,10 @@
 // (wave-per-rotation kernel for full rounds of 2048 + a workgroup-per-rotation kernel for the remainder),
 // keyswitch_init + keyswitch.  WHICH kernel takes which part of a batch, and with what launch shape, is decided by the pure
 // functions of dispatch.hpp (host only, visible to the CPU tests through libiyk_emul.so); this file reads the environment and
-// the device, calls them and launches what they say.  Chooses the exact-arithmetic field at init (FP64 p = 3*2^48+1097729 where its
+// the device, calls them and launches what they say.  WHETHER a batch's arguments are legal, and what job lists they make, is decided by
+// the pure functions of batch_args.hpp (same arrangement; the structs and limits: jobs.hpp): an entry point here checks what needs the
+// library's state (initialised, the FFT path, null handles, one GPU), calls its builder, stages the lists (stage_put) and launches, so
+// this file holds state, HIP calls and launches only.  Chooses the exact-arithmetic field at init (FP64 p = 3*2^48+1097729 where its
 // bound holds, else / on request the 64-bit Goldilocks integers).  Replaces the cuFHE host API used at
 // /root/reference/src/iyokan_cufhe.cpp:530-536,721 and /root/reference/src/iyokan_cufhe.hpp:8-27,249-261,601,634.
 //
@@ -27,10 +30,10 @@
 #include <new>
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/iyokan_hip.h"
+#include "batch_args.hpp"
 #include "dispatch.hpp"
 #include "kernels.hpp"
 #ifdef IYK_EXPERIMENT_KERNELS_FFT   // A/B builds only (tools/ab_*.sh): a header of tools/experiments/ in place of the product's FFT kernels
@@ -51,6 +54,8 @@ using namespace iyk::dispatch;
 // dispatch.hpp restates these figures of the kernel headers (it includes none of them)
 static_assert(ROT_WAVES == BR_WAVES && KS_N == NTT_N && KS_KIND0_GATES == KS_G && KS_TABLE_GATES == KSL_WAVES * KSL_G,
               "dispatch.hpp and kernels.hpp disagree about a workgroup's share of a batch");
+// and batch_args.hpp these two
+static_assert(args::RING_N == NTT_N && args::CB_RING_N == (u32)CB_N, "batch_args.hpp and the kernel headers disagree about a ring degree");
 
 namespace {
 
@@ -61,6 +66,7 @@ int fail(int code, const std::string& msg)
     g_last_error = msg;
     return code;
 }
+int refuse(const args::Refusal& r) { return fail(r.code, r.text); }
 
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \
@@ -225,8 +231,6 @@ struct iyk_hip_stream {
 
 namespace {
 
-constexpr u32 ABAR_STRIDE = 1024;  // words per job in d_abar (n + 1 <= 768 used)
-
 int set_device(int gpu)
 {
     if (gpu < 0 || gpu >= (int)G.devs.size()) return fail(IYK_ERR_INVALID, "gpu_index out of range");
@@ -263,6 +267,30 @@ int acquire_stage(iyk_hip_stream* st, size_t bytes, size_t* off)
 int release_stage(iyk_hip_stream* st)
 {
     HIP_TRY(hipEventRecord(st->stage_free[st->stage_sel], st->s));
+    return IYK_OK;
+}
+
+// The descriptors of one call into one slot of the staging ring: part i starts at the next 16-byte-aligned offset (the slot ends with
+// the last part, so an empty last part pads the one before it), non-empty parts are copied into the pinned half — the caller's arrays
+// are free on return — and ONE copy sends the slot.  d[i]: device address of part i.  The caller records release_stage.
+struct StagePart {
+    const void* src;
+    size_t bytes;
+};
+template <size_t NP>
+int stage_put(iyk_hip_stream* st, const StagePart (&parts)[NP], char* (&d)[NP])
+{
+    size_t off[NP], total = 0, soff = 0;
+    for (size_t i = 0; i < NP; ++i) {
+        off[i] = (total + 15) & ~(size_t)15;
+        total = off[i] + parts[i].bytes;
+    }
+    if (int rc = acquire_stage(st, total, &soff)) return rc;
+    for (size_t i = 0; i < NP; ++i) {
+        if (parts[i].bytes) std::memcpy(st->h_stage + soff + off[i], parts[i].src, parts[i].bytes);
+        d[i] = st->d_stage + soff + off[i];
+    }
+    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, total, hipMemcpyHostToDevice, st->s));
     return IYK_OK;
 }
 
@@ -641,24 +669,6 @@ int set_kernel_attrs(const iyk_params& p, bool use_fp, int split)
     });
 }
 
-// linear-step coefficients of TFHEpp HomGate (SURVEY.md §8 a-ext)
-bool gate_coeffs(int op, u32 mu, int32_t& sa, int32_t& sb, u32& off)
-{
-    switch (op) {
-    case IYK_OP_AND: sa = 1; sb = 1; off = 0u - mu; return true;
-    case IYK_OP_NAND: sa = -1; sb = -1; off = mu; return true;
-    case IYK_OP_ANDNOT: sa = 1; sb = -1; off = 0u - mu; return true;
-    case IYK_OP_OR: sa = 1; sb = 1; off = mu; return true;
-    case IYK_OP_NOR: sa = -1; sb = -1; off = 0u - mu; return true;
-    case IYK_OP_ORNOT: sa = 1; sb = -1; off = mu; return true;
-    case IYK_OP_XOR: sa = 2; sb = 2; off = 2u * mu; return true;
-    case IYK_OP_XNOR: sa = -2; sb = -2; off = 0u - 2u * mu; return true;
-    default: return false;
-    }
-}
-
-inline bool slot_ok(int32_t s, uint64_t slots) { return s >= 0 && (uint64_t)s < slots; }
-
 // fresh timing events for this batch when a log is active (so a whole timed region can be summed afterwards)
 int begin_timing(iyk_hip_stream* st)
 {
@@ -944,13 +954,6 @@ int row_copy(iyk_hip_stream* st, void* dst, const void* src, size_t row_words, u
     HIP_TRY(hipMemcpyAsync(device_is_dst ? (void*)((u32*)dst + off) : dst,
                            device_is_dst ? src : (const void*)((const u32*)src + off),
                            (size_t)count * row_words * sizeof(u32), kind, st->s));
-    return IYK_OK;
-}
-
-int check_slot_list(uint64_t count, const int32_t* slots, uint64_t arena_slots)
-{
-    for (uint64_t g = 0; g < count; ++g)
-        if (!slot_ok(slots[g], arena_slots)) return fail(IYK_ERR_INVALID, "slot index outside the arena");
     return IYK_OK;
 }
 
@@ -1433,7 +1436,7 @@ int iyk_hip_arena_free(int gpu_index, uint32_t* d_arena)
 int iyk_hip_trlwe_alloc(int gpu_index, uint64_t count, uint32_t** d_trlwe_out)
 {
     if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
-    if (!d_trlwe_out || count == 0 || count > (1ull << 28)) return fail(IYK_ERR_INVALID, "bad argument");
+    if (!d_trlwe_out || count == 0 || count > MAX_STORE_ROWS) return fail(IYK_ERR_INVALID, "bad argument");
     int rc = set_device(gpu_index);
     if (rc) return rc;
     HIP_TRY(hipMalloc((void**)d_trlwe_out, count * 2 * NTT_N * sizeof(u32)));
@@ -1489,18 +1492,12 @@ int iyk_hip_arena_upload_slots(iyk_hip_stream* st, uint32_t* d_arena, uint64_t a
     if (!st || !d_arena || !slots || !host_tlwe) return fail(IYK_ERR_INVALID, "null argument");
     if (count == 0) return IYK_OK;
     if (count > (1u << 24)) return fail(IYK_ERR_INVALID, "too many slots in one transfer");
-    int rc = check_slot_list(count, slots, arena_slots);
+    if (const args::Refusal r = args::check_slot_list(count, slots, arena_slots)) return refuse(r);
+    int rc = set_device(st->gpu);
     if (rc) return rc;
-    if ((rc = set_device(st->gpu))) return rc;
-    const size_t n1 = (size_t)G.p.n + 1;
-    const size_t idx_bytes = (count * sizeof(int32_t) + 15) & ~(size_t)15, row_bytes = count * n1 * sizeof(u32);
-    size_t soff = 0;
-    if ((rc = acquire_stage(st, idx_bytes + row_bytes, &soff))) return rc;
-    std::memcpy(st->h_stage + soff, slots, count * sizeof(int32_t));
-    std::memcpy(st->h_stage + soff + idx_bytes, host_tlwe, row_bytes);  // the caller's buffer is free on return
-    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, idx_bytes + row_bytes, hipMemcpyHostToDevice, st->s));
-    hipLaunchKernelGGL(scatter_slots_kernel, dim3((unsigned)count), dim3(256), 0, st->s, d_arena,
-                       (const int32_t*)(st->d_stage + soff), (const u32*)(st->d_stage + soff + idx_bytes), G.p.n);
+    char* d[2];
+    if ((rc = stage_put(st, {{slots, count * sizeof(int32_t)}, {host_tlwe, count * ((size_t)G.p.n + 1) * sizeof(u32)}}, d))) return rc;
+    hipLaunchKernelGGL(scatter_slots_kernel, dim3((unsigned)count), dim3(256), 0, st->s, d_arena, (const int32_t*)d[0], (const u32*)d[1], G.p.n);
     HIP_TRY(hipGetLastError());
     return release_stage(st);
     IYK_API_END
@@ -1514,9 +1511,9 @@ int iyk_hip_arena_download_slots(iyk_hip_stream* st, const uint32_t* d_arena, ui
     if (!st || !d_arena || !slots || !host_tlwe) return fail(IYK_ERR_INVALID, "null argument");
     if (count == 0) return IYK_OK;
     if (count > (1u << 24)) return fail(IYK_ERR_INVALID, "too many slots in one transfer");
-    int rc = check_slot_list(count, slots, arena_slots);
+    if (const args::Refusal r = args::check_slot_list(count, slots, arena_slots)) return refuse(r);
+    int rc = set_device(st->gpu);
     if (rc) return rc;
-    if ((rc = set_device(st->gpu))) return rc;
     const size_t n1 = (size_t)G.p.n + 1;
     const size_t idx_bytes = (count * sizeof(int32_t) + 15) & ~(size_t)15, row_bytes = count * n1 * sizeof(u32);
     size_t soff = 0;
@@ -1554,8 +1551,8 @@ int iyk_hip_arena_sync_slots_multi(iyk_hip_stream* st_src, const uint32_t* d_src
     }
     if (count == 0 || ndst == 0) return IYK_OK;
     if (count > (1u << 24)) return fail(IYK_ERR_INVALID, "too many slots in one transfer");
-    int rc = check_slot_list(count, slots, min_slots);
-    if (rc) return rc;
+    if (const args::Refusal r = args::check_slot_list(count, slots, min_slots)) return refuse(r);
+    int rc;
     const size_t n1 = (size_t)G.p.n + 1;
     const size_t idx_bytes = (count * sizeof(int32_t) + 15) & ~(size_t)15, row_bytes = count * n1 * sizeof(u32);
     // source GPU: gather the listed slots into its staging buffer, once
@@ -1624,98 +1621,30 @@ int iyk_hip_gate_batch(iyk_hip_stream* st, uint32_t* d_arena, uint64_t arena_slo
     if (!st || !d_arena) return fail(IYK_ERR_INVALID, "null argument");
     if (count == 0) return IYK_OK;
     if (!ops || !in0 || !in1 || !in2 || !out) return fail(IYK_ERR_INVALID, "null descriptor array");
-    if (count > (1u << 30)) return fail(IYK_ERR_INVALID, "batch too large");
     int rc = set_device(st->gpu);
     if (rc) return rc;
     const iyk_params& p = G.p;
-
     std::vector<RotJob> rot;
     std::vector<KsJob> ks;
     std::vector<EwJob> ew;
-    size_t nmux = 0;
-    for (uint64_t g = 0; g < count; ++g) nmux += (ops[g] == IYK_OP_MUX);
-    if (count + nmux > (size_t)INT32_MAX) return fail(IYK_ERR_INVALID, "batch too large: more than 2^31 - 1 rotations");
-    rot.reserve(count + nmux);
-    ks.reserve(count);
-    for (uint64_t g = 0; g < count; ++g) {
-        const int op = ops[g];
-        if (!slot_ok(out[g], arena_slots)) return fail(IYK_ERR_INVALID, "output slot outside the arena");
-        int32_t sa, sb;
-        u32 off;
-        if (gate_coeffs(op, p.mu, sa, sb, off)) {
-            if (!slot_ok(in0[g], arena_slots) || !slot_ok(in1[g], arena_slots))
-                return fail(IYK_ERR_INVALID, "binary gate needs two input slots inside the arena");
-            ks.push_back(KsJob{(int32_t)rot.size(), -1, 0u, out[g]});
-            rot.push_back(RotJob{in0[g], in1[g], sa, sb, off});
-        }
-        else if (op == IYK_OP_MUX) {
-            // HomMUX(cs = in2, c1 = in1, c0 = in0): BR(cs + c1 - mu) + BR(c0 - cs - mu) + (0, mu) -> KS
-            if (!slot_ok(in0[g], arena_slots) || !slot_ok(in1[g], arena_slots) || !slot_ok(in2[g], arena_slots))
-                return fail(IYK_ERR_INVALID, "MUX needs three input slots inside the arena");
-            ks.push_back(KsJob{(int32_t)rot.size(), (int32_t)rot.size() + 1, p.mu, out[g]});
-            rot.push_back(RotJob{in2[g], in1[g], 1, 1, 0u - p.mu});
-            rot.push_back(RotJob{in0[g], in2[g], 1, -1, 0u - p.mu});
-        }
-        else if (op == IYK_OP_NOT || op == IYK_OP_COPY) {
-            if (!slot_ok(in0[g], arena_slots)) return fail(IYK_ERR_INVALID, "NOT/COPY needs one input slot inside the arena");
-            ew.push_back(EwJob{op, in0[g], out[g]});
-        }
-        else if (op == IYK_OP_CONSTONE || op == IYK_OP_CONSTZERO) {
-            ew.push_back(EwJob{op, -1, out[g]});
-        }
-        else {
-            return fail(IYK_ERR_INVALID, "unknown gate op");
-        }
-    }
-    if (G.debug) {
-        // the independence contract (header): output slots are pairwise distinct and no gate reads a slot that
-        // ANOTHER gate of this batch writes.  O(count) with a hash map; only under IYK_HIP_DEBUG=1.
-        std::unordered_map<int32_t, uint64_t> writer;
-        writer.reserve(count * 2);
-        for (uint64_t g = 0; g < count; ++g)
-            if (!writer.emplace(out[g], g).second)
-                return fail(IYK_ERR_INVALID, "debug: two gates of one batch write the same slot");
-        for (uint64_t g = 0; g < count; ++g) {
-            const int op = ops[g];
-            const int nin = op == IYK_OP_MUX ? 3 : op < IYK_OP_MUX ? 2 : (op == IYK_OP_NOT || op == IYK_OP_COPY) ? 1 : 0;
-            const int32_t ins[3] = {in0[g], in1[g], in2[g]};
-            for (int k = 0; k < nin; ++k) {
-                auto it = writer.find(ins[k]);
-                if (it != writer.end() && it->second != g)
-                    return fail(IYK_ERR_INVALID, "debug: a gate reads a slot another gate of the same batch writes");
-            }
-        }
-    }
-
-    const size_t rot_bytes = rot.size() * sizeof(RotJob);
-    const size_t ks_bytes = ks.size() * sizeof(KsJob);
-    const size_t ew_bytes = ew.size() * sizeof(EwJob);
-    const size_t ks_off = (rot_bytes + 15) & ~(size_t)15;
-    const size_t ew_off = (ks_off + ks_bytes + 15) & ~(size_t)15;
-    const size_t total = ew_off + ew_bytes;
-    size_t soff = 0;
-    if ((rc = acquire_stage(st, total, &soff))) return rc;
+    if (const args::Refusal r = args::check_gate_batch(p, G.debug, arena_slots, count, ops, in0, in1, in2, out, rot, ks, ew)) return refuse(r);
     if ((rc = ensure_rot(st, rot.size()))) return rc;
-    char* hs = st->h_stage + soff;
-    char* ds = st->d_stage + soff;
-    if (rot_bytes) std::memcpy(hs, rot.data(), rot_bytes);
-    if (ks_bytes) std::memcpy(hs + ks_off, ks.data(), ks_bytes);
-    if (ew_bytes) std::memcpy(hs + ew_off, ew.data(), ew_bytes);
-    HIP_TRY(hipMemcpyAsync(ds, hs, total, hipMemcpyHostToDevice, st->s));
+    char* d[3];   // the last part is not padded
+    if ((rc = stage_put(st, {{rot.data(), rot.size() * sizeof(RotJob)}, {ks.data(), ks.size() * sizeof(KsJob)}, {ew.data(), ew.size() * sizeof(EwJob)}}, d)))
+        return rc;
     if ((rc = release_stage(st))) return rc;
 
     if (!ew.empty()) {
-        hipLaunchKernelGGL(elementwise_kernel, dim3((unsigned)ew.size()), dim3(256), 0, st->s, d_arena,
-                           (const EwJob*)(ds + ew_off), p.n, p.mu);
+        hipLaunchKernelGGL(elementwise_kernel, dim3((unsigned)ew.size()), dim3(256), 0, st->s, d_arena, (const EwJob*)d[2], p.n, p.mu);
         HIP_TRY(hipGetLastError());
     }
     st->timing_valid = false;
     if (!rot.empty()) {
         if ((rc = begin_timing(st))) return rc;
-        if ((rc = launch_blind_rotate(st, d_arena, (const RotJob*)ds, (int)rot.size(), RotOut{st->d_rot, nullptr, 0})))
+        if ((rc = launch_blind_rotate(st, d_arena, (const RotJob*)d[0], (int)rot.size(), RotOut{st->d_rot, nullptr, 0})))
             return rc;
         HIP_TRY(hipEventRecord(st->ev_br1, st->s));
-        if ((rc = launch_keyswitch(st, d_arena, (const KsJob*)(ds + ks_off), (int)ks.size()))) return rc;
+        if ((rc = launch_keyswitch(st, d_arena, (const KsJob*)d[1], (int)ks.size()))) return rc;
         HIP_TRY(hipEventRecord(st->ev_ks1, st->s));
         st->timing_valid = true;
         st->timing_has_ks = true;
@@ -2048,27 +1977,15 @@ static int rotate_only(iyk_hip_stream* st, const uint32_t* d_arena, uint64_t are
     if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
     if (!st || !d_arena || !d_out || !ia || !ib || !sa || !sb || !off) return fail(IYK_ERR_INVALID, "null argument");
     if (count == 0) return IYK_OK;
-    if (count > (1u << 30)) return fail(IYK_ERR_INVALID, "batch too large");
     int rc = set_device(st->gpu);
     if (rc) return rc;
-    std::vector<RotJob> rot(count);
-    for (uint64_t g = 0; g < count; ++g) {
-        if (!slot_ok(ia[g], arena_slots) || (ib[g] >= 0 && !slot_ok(ib[g], arena_slots)))
-            return fail(IYK_ERR_INVALID, "input slot outside the arena");
-        if (out_index && !slot_ok(out_index[g], out_rows)) return fail(IYK_ERR_INVALID, "output index outside the buffer");
-        rot[g] = RotJob{ia[g], ib[g], sa[g], sb[g], off[g]};
-    }
-    if (!out_index && out_rows && count > out_rows) return fail(IYK_ERR_INVALID, "more jobs than output rows");
-    const size_t bytes = rot.size() * sizeof(RotJob), idx_off = (bytes + 15) & ~(size_t)15;
-    const size_t total = idx_off + (out_index ? count * sizeof(int32_t) : 0);
-    size_t soff = 0;
-    if ((rc = acquire_stage(st, total, &soff))) return rc;
-    std::memcpy(st->h_stage + soff, rot.data(), bytes);
-    if (out_index) std::memcpy(st->h_stage + soff + idx_off, out_index, count * sizeof(int32_t));
-    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, total, hipMemcpyHostToDevice, st->s));
+    std::vector<RotJob> rot;
+    if (const args::Refusal r = args::check_rotate_only(arena_slots, count, ia, ib, sa, sb, off, out_rows, out_index, rot)) return refuse(r);
+    char* d[2];
+    if ((rc = stage_put(st, {{rot.data(), rot.size() * sizeof(RotJob)}, {out_index, out_index ? count * sizeof(int32_t) : 0}}, d))) return rc;
     if ((rc = begin_timing(st))) return rc;
-    const RotOut o{d_out, out_index ? (const int32_t*)(st->d_stage + soff + idx_off) : nullptr, trlwe};
-    if ((rc = launch_blind_rotate(st, d_arena, (const RotJob*)(st->d_stage + soff), (int)count, o))) return rc;
+    const RotOut o{d_out, out_index ? (const int32_t*)d[1] : nullptr, trlwe};
+    if ((rc = launch_blind_rotate(st, d_arena, (const RotJob*)d[0], (int)count, o))) return rc;
     HIP_TRY(hipEventRecord(st->ev_br1, st->s));
     if (st->log_on) HIP_TRY(hipEventRecord(st->ev_ks1, st->s));  // empty key-switch interval: the log's triples stay well formed
     if ((rc = release_stage(st))) return rc;
@@ -2104,27 +2021,16 @@ int iyk_hip_sample_extract_keyswitch_batch(iyk_hip_stream* st, const uint32_t* d
     if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
     if (!st || !d_trlwe || !trlwe_index || !out_slot || !d_arena) return fail(IYK_ERR_INVALID, "null argument");
     if (count == 0) return IYK_OK;
-    if (count > (1u << 30)) return fail(IYK_ERR_INVALID, "batch too large");
     int rc = set_device(st->gpu);
     if (rc) return rc;
-    std::vector<KsJob> ks(count);
-    for (uint64_t g = 0; g < count; ++g) {
-        if (!slot_ok(trlwe_index[g], trlwe_slots)) return fail(IYK_ERR_INVALID, "TRLWE index outside the buffer");
-        if (!slot_ok(out_slot[g], arena_slots)) return fail(IYK_ERR_INVALID, "output slot outside the arena");
-        ks[g] = KsJob{(int32_t)g, -1, 0u, out_slot[g]};
-    }
-    const size_t ks_bytes = ks.size() * sizeof(KsJob), idx_off = (ks_bytes + 15) & ~(size_t)15;
-    const size_t total = idx_off + count * sizeof(int32_t);
-    size_t soff = 0;
-    if ((rc = acquire_stage(st, total, &soff))) return rc;
+    std::vector<KsJob> ks;
+    if (const args::Refusal r = args::check_sample_extract_keyswitch(trlwe_slots, arena_slots, count, trlwe_index, nullptr, out_slot, ks)) return refuse(r);
     if ((rc = ensure_rot(st, count))) return rc;
-    std::memcpy(st->h_stage + soff, ks.data(), ks_bytes);
-    std::memcpy(st->h_stage + soff + idx_off, trlwe_index, count * sizeof(int32_t));
-    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, total, hipMemcpyHostToDevice, st->s));
-    hipLaunchKernelGGL(sample_extract_kernel, dim3((unsigned)count), dim3(256), 0, st->s, d_trlwe,
-                       (const int32_t*)(st->d_stage + soff + idx_off), st->d_rot);
+    char* d[2];
+    if ((rc = stage_put(st, {{ks.data(), ks.size() * sizeof(KsJob)}, {trlwe_index, count * sizeof(int32_t)}}, d))) return rc;
+    hipLaunchKernelGGL(sample_extract_kernel, dim3((unsigned)count), dim3(256), 0, st->s, d_trlwe, (const int32_t*)d[1], st->d_rot);
     HIP_TRY(hipGetLastError());
-    if ((rc = launch_keyswitch(st, d_arena, (const KsJob*)(st->d_stage + soff), (int)count))) return rc;
+    if ((rc = launch_keyswitch(st, d_arena, (const KsJob*)d[0], (int)count))) return rc;
     return release_stage(st);
     IYK_API_END
 }
@@ -2149,7 +2055,7 @@ constexpr uint64_t TRGSW_UPLOAD_CHUNK = 16;   // selectors per staging slot (768
 int iyk_hip_trgsw_alloc(int gpu_index, uint64_t count, void** d_trgsw_out)
 {
     if (int rc = need_fft_path("iyk_hip_trgsw_alloc")) return rc;
-    if (!d_trgsw_out || count == 0 || count > (1ull << 24)) return fail(IYK_ERR_INVALID, "bad argument");
+    if (!d_trgsw_out || count == 0 || count > MAX_TRGSW_SLOTS) return fail(IYK_ERR_INVALID, "bad argument");
     int rc = set_device(gpu_index);
     if (rc) return rc;
     HIP_TRY(hipMalloc(d_trgsw_out, count * trgsw_slot_bytes()));
@@ -2171,7 +2077,7 @@ int iyk_hip_trgsw_upload(iyk_hip_stream* st, void* d_trgsw, uint64_t trgsw_slots
     IYK_API_BEGIN
     if (int rc = need_fft_path("iyk_hip_trgsw_upload")) return rc;
     if (!st || !d_trgsw || !host_trgsw) return fail(IYK_ERR_INVALID, "null argument");
-    if (trgsw_slots > (1ull << 24) || first > trgsw_slots || count > trgsw_slots - first)
+    if (trgsw_slots > MAX_TRGSW_SLOTS || first > trgsw_slots || count > trgsw_slots - first)
         return fail(IYK_ERR_INVALID, "slot range outside the selector store");
     int rc = set_device(st->gpu);
     if (rc) return rc;
@@ -2202,38 +2108,18 @@ int iyk_hip_cmux_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_s
     if (int rc = need_fft_path("iyk_hip_cmux_batch")) return rc;
     if (!st || !d_trgsw || !d_trlwe || !sel || !in0 || !in1 || !rot || !out) return fail(IYK_ERR_INVALID, "null argument");
     if (count == 0) return IYK_OK;
-    if (count > (1u << 24)) return fail(IYK_ERR_INVALID, "batch too large");
-    if (trgsw_slots > (1ull << 24) || trlwe_slots > (1ull << 28)) return fail(IYK_ERR_INVALID, "store larger than an allocation can be");
     int rc = set_device(st->gpu);
     if (rc) return rc;
-    std::vector<CmuxJob> jobs(count);
-    std::unordered_map<int32_t, uint64_t> writer;   // out row -> its job
-    writer.reserve(count * 2);
-    for (uint64_t g = 0; g < count; ++g) {
-        if (!slot_ok(sel[g], trgsw_slots)) return fail(IYK_ERR_INVALID, "selector index outside the selector store");
-        if (!slot_ok(in0[g], trlwe_slots) || !slot_ok(out[g], trlwe_slots) || (in1[g] >= 0 && !slot_ok(in1[g], trlwe_slots)))
-            return fail(IYK_ERR_INVALID, "TRLWE index outside the buffer");
-        if (in1[g] < 0 && (rot[g] < 0 || rot[g] >= 2 * NTT_N)) return fail(IYK_ERR_INVALID, "rot outside [0, 2N)");
-        if (!writer.emplace(out[g], g).second) return fail(IYK_ERR_INVALID, "two jobs of one batch write the same TRLWE row");
-        jobs[g] = CmuxJob{sel[g], in0[g], in1[g] >= 0 ? in1[g] : -1, in1[g] >= 0 ? 0 : rot[g], out[g]};
-    }
-    for (uint64_t g = 0; g < count; ++g)   // a job may write over its own inputs, never over another job's
-        for (const int32_t in : {in0[g], in1[g]}) {
-            if (in < 0) continue;
-            const auto w = writer.find(in);
-            if (w != writer.end() && w->second != g) return fail(IYK_ERR_INVALID, "a job reads a TRLWE row that another job of the batch writes");
-        }
-    const size_t bytes = jobs.size() * sizeof(CmuxJob);
-    size_t soff = 0;
-    if ((rc = acquire_stage(st, bytes, &soff))) return rc;
-    std::memcpy(st->h_stage + soff, jobs.data(), bytes);
-    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+    std::vector<CmuxJob> jobs;
+    if (const args::Refusal r = args::check_cmux_batch(trgsw_slots, trlwe_slots, count, sel, in0, in1, rot, out, jobs)) return refuse(r);
+    char* d[1];
+    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxJob)}}, d))) return rc;
     const Device& D = G.devs[st->gpu];
     rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
         typedef decltype(gd) GD;
         auto kern = G.debug ? cmux_fft_kernel<GD, true> : cmux_fft_kernel<GD, false>;
         hipLaunchKernelGGL(kern, dim3((unsigned)((count + BR_WAVES - 1) / BR_WAVES)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s,
-                           (const CmuxJob*)(st->d_stage + soff), (int)count, (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
+                           (const CmuxJob*)d[0], (int)count, (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
         HIP_TRY(hipGetLastError());
         return (int)IYK_OK;
     });
@@ -2241,26 +2127,6 @@ int iyk_hip_cmux_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_s
     return release_stage(st);
     IYK_API_END
 }
-
-namespace {
-
-// The independence contract of the chain and add batches, O(count): job g reads rows in_a[g] and in_b[g] and writes out[g].  No out may
-// be a row another job reads or writes; a job may write over what it reads itself, and jobs may share what they only read.
-int check_independent(uint64_t count, const int32_t* out, const int32_t* in_a, const int32_t* in_b)
-{
-    std::unordered_map<int32_t, uint64_t> writer;   // out row -> its job
-    writer.reserve(count * 2);
-    for (uint64_t g = 0; g < count; ++g)
-        if (!writer.emplace(out[g], g).second) return fail(IYK_ERR_INVALID, "two jobs of one batch write the same TRLWE row");
-    for (uint64_t g = 0; g < count; ++g)
-        for (const int32_t in : {in_a[g], in_b[g]}) {
-            const auto w = writer.find(in);
-            if (w != writer.end() && w->second != g) return fail(IYK_ERR_INVALID, "a job reads a TRLWE row that another job of the batch writes");
-        }
-    return IYK_OK;
-}
-
-}  // namespace
 
 int iyk_hip_cmux_chain_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
                              uint64_t count, const int32_t* sel0, const int32_t* steps, const uint32_t* pattern, const int32_t* src,
@@ -2270,31 +2136,18 @@ int iyk_hip_cmux_chain_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t t
     if (int rc = need_fft_path("iyk_hip_cmux_chain_batch")) return rc;
     if (!st || !d_trgsw || !d_trlwe || !sel0 || !steps || !pattern || !src || !mem || !out) return fail(IYK_ERR_INVALID, "null argument");
     if (count == 0) return IYK_OK;
-    if (count > (1u << 24)) return fail(IYK_ERR_INVALID, "batch too large");
-    if (trgsw_slots > (1ull << 24) || trlwe_slots > (1ull << 28)) return fail(IYK_ERR_INVALID, "store larger than an allocation can be");
     int rc = set_device(st->gpu);
     if (rc) return rc;
-    std::vector<CmuxChainJob> jobs(count);
-    for (uint64_t g = 0; g < count; ++g) {
-        if (steps[g] < 1 || steps[g] > CMUX_CHAIN_MAX_STEPS) return fail(IYK_ERR_INVALID, "steps outside [1, 32]");
-        if (sel0[g] < 0 || (uint64_t)sel0[g] + (uint64_t)steps[g] > trgsw_slots)
-            return fail(IYK_ERR_INVALID, "selector slots sel0 .. sel0 + steps - 1 outside the selector store");
-        if (!slot_ok(src[g], trlwe_slots) || !slot_ok(mem[g], trlwe_slots) || !slot_ok(out[g], trlwe_slots))
-            return fail(IYK_ERR_INVALID, "TRLWE index outside the buffer");
-        jobs[g] = CmuxChainJob{sel0[g], steps[g], pattern[g], src[g], mem[g], out[g]};
-    }
-    if ((rc = check_independent(count, out, src, mem))) return rc;
-    const size_t bytes = jobs.size() * sizeof(CmuxChainJob);
-    size_t soff = 0;
-    if ((rc = acquire_stage(st, bytes, &soff))) return rc;
-    std::memcpy(st->h_stage + soff, jobs.data(), bytes);
-    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+    std::vector<CmuxChainJob> jobs;
+    if (const args::Refusal r = args::check_cmux_chain_batch(trgsw_slots, trlwe_slots, count, sel0, steps, pattern, src, mem, out, jobs)) return refuse(r);
+    char* d[1];
+    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxChainJob)}}, d))) return rc;
     const Device& D = G.devs[st->gpu];
     rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
         typedef decltype(gd) GD;
         auto kern = G.debug ? cmux_chain_kernel<GD, true> : cmux_chain_kernel<GD, false>;
         hipLaunchKernelGGL(kern, dim3((unsigned)((count + BR_WAVES - 1) / BR_WAVES)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s,
-                           (const CmuxChainJob*)(st->d_stage + soff), (int)count, (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
+                           (const CmuxChainJob*)d[0], (int)count, (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
         HIP_TRY(hipGetLastError());
         return (int)IYK_OK;
     });
@@ -2310,24 +2163,13 @@ int iyk_hip_trlwe_add_batch(iyk_hip_stream* st, uint32_t* d_trlwe, uint64_t trlw
     if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
     if (!st || !d_trlwe || !a || !b || !out) return fail(IYK_ERR_INVALID, "null argument");
     if (count == 0) return IYK_OK;
-    if (count > (1u << 24)) return fail(IYK_ERR_INVALID, "batch too large");
-    if (trlwe_slots > (1ull << 28)) return fail(IYK_ERR_INVALID, "store larger than an allocation can be");
     int rc = set_device(st->gpu);
     if (rc) return rc;
-    std::vector<TrlweAddJob> jobs(count);
-    for (uint64_t g = 0; g < count; ++g) {
-        if (!slot_ok(a[g], trlwe_slots) || !slot_ok(b[g], trlwe_slots) || !slot_ok(out[g], trlwe_slots))
-            return fail(IYK_ERR_INVALID, "TRLWE index outside the buffer");
-        jobs[g] = TrlweAddJob{a[g], b[g], out[g]};
-    }
-    if ((rc = check_independent(count, out, a, b))) return rc;
-    const size_t bytes = jobs.size() * sizeof(TrlweAddJob);
-    size_t soff = 0;
-    if ((rc = acquire_stage(st, bytes, &soff))) return rc;
-    std::memcpy(st->h_stage + soff, jobs.data(), bytes);
-    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
-    hipLaunchKernelGGL(trlwe_add_kernel, dim3((unsigned)count), dim3(256), 0, st->s, d_trlwe, (const TrlweAddJob*)(st->d_stage + soff),
-                       b0_offset);
+    std::vector<TrlweAddJob> jobs;
+    if (const args::Refusal r = args::check_trlwe_add_batch(trlwe_slots, count, a, b, out, jobs)) return refuse(r);
+    char* d[1];
+    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(TrlweAddJob)}}, d))) return rc;
+    hipLaunchKernelGGL(trlwe_add_kernel, dim3((unsigned)count), dim3(256), 0, st->s, d_trlwe, (const TrlweAddJob*)d[0], b0_offset);
     HIP_TRY(hipGetLastError());
     return release_stage(st);
     IYK_API_END
@@ -2341,29 +2183,17 @@ int iyk_hip_sample_extract_index_keyswitch_batch(iyk_hip_stream* st, const uint3
     if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
     if (!st || !d_trlwe || !trlwe_index || !coeff_index || !out_slot || !d_arena) return fail(IYK_ERR_INVALID, "null argument");
     if (count == 0) return IYK_OK;
-    if (count > (1u << 30)) return fail(IYK_ERR_INVALID, "batch too large");
     int rc = set_device(st->gpu);
     if (rc) return rc;
-    std::vector<KsJob> ks(count);
-    for (uint64_t g = 0; g < count; ++g) {
-        if (!slot_ok(trlwe_index[g], trlwe_slots)) return fail(IYK_ERR_INVALID, "TRLWE index outside the buffer");
-        if (coeff_index[g] < 0 || coeff_index[g] >= NTT_N) return fail(IYK_ERR_INVALID, "coefficient index outside [0, N)");
-        if (!slot_ok(out_slot[g], arena_slots)) return fail(IYK_ERR_INVALID, "output slot outside the arena");
-        ks[g] = KsJob{(int32_t)g, -1, 0u, out_slot[g]};
-    }
-    const size_t ks_bytes = ks.size() * sizeof(KsJob), idx_off = (ks_bytes + 15) & ~(size_t)15;
-    const size_t idx_bytes = (count * sizeof(int32_t) + 15) & ~(size_t)15, total = idx_off + 2 * idx_bytes;
-    size_t soff = 0;
-    if ((rc = acquire_stage(st, total, &soff))) return rc;
+    std::vector<KsJob> ks;
+    if (const args::Refusal r = args::check_sample_extract_keyswitch(trlwe_slots, arena_slots, count, trlwe_index, coeff_index, out_slot, ks)) return refuse(r);
     if ((rc = ensure_rot(st, count))) return rc;
-    std::memcpy(st->h_stage + soff, ks.data(), ks_bytes);
-    std::memcpy(st->h_stage + soff + idx_off, trlwe_index, count * sizeof(int32_t));
-    std::memcpy(st->h_stage + soff + idx_off + idx_bytes, coeff_index, count * sizeof(int32_t));
-    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, total, hipMemcpyHostToDevice, st->s));
-    hipLaunchKernelGGL(sample_extract_index_kernel, dim3((unsigned)count), dim3(256), 0, st->s, d_trlwe,
-                       (const int32_t*)(st->d_stage + soff + idx_off), (const int32_t*)(st->d_stage + soff + idx_off + idx_bytes), st->d_rot);
+    char* d[4];   // both index lists are padded: the empty part
+    if ((rc = stage_put(st, {{ks.data(), ks.size() * sizeof(KsJob)}, {trlwe_index, count * sizeof(int32_t)}, {coeff_index, count * sizeof(int32_t)}, {nullptr, 0}}, d)))
+        return rc;
+    hipLaunchKernelGGL(sample_extract_index_kernel, dim3((unsigned)count), dim3(256), 0, st->s, d_trlwe, (const int32_t*)d[1], (const int32_t*)d[2], st->d_rot);
     HIP_TRY(hipGetLastError());
-    if ((rc = launch_keyswitch(st, d_arena, (const KsJob*)(st->d_stage + soff), (int)count))) return rc;
+    if ((rc = launch_keyswitch(st, d_arena, (const KsJob*)d[0], (int)count))) return rc;
     return release_stage(st);
     IYK_API_END
 }
@@ -2381,7 +2211,6 @@ struct PrivksKey {
     u32* d = nullptr;
 };
 constexpr uint64_t PRIVKS_UPLOAD_CHUNK = 256;   // key rows per staging slot (2 MiB)
-constexpr u32 PRIVKS_MAX_N_IN = 1u << 16;
 
 int ensure_sel(iyk_hip_stream* st, size_t selectors, size_t words_per_selector)
 {
@@ -2480,7 +2309,7 @@ int iyk_hip_privks_key_upload(iyk_hip_stream* st, void* key_, uint64_t first_row
 int iyk_hip_tlwe2_alloc(int gpu_index, uint32_t n_in, uint64_t slots, uint64_t** out)
 {
     if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
-    if (!out || slots == 0 || slots > (1ull << 28) || n_in == 0 || n_in > PRIVKS_MAX_N_IN) return fail(IYK_ERR_INVALID, "bad argument");
+    if (!out || slots == 0 || slots > MAX_STORE_ROWS || n_in == 0 || n_in > PRIVKS_MAX_N_IN) return fail(IYK_ERR_INVALID, "bad argument");
     int rc = set_device(gpu_index);
     if (rc) return rc;
     HIP_TRY(hipMalloc((void**)out, slots * ((uint64_t)n_in + 1) * sizeof(u64)));
@@ -2503,6 +2332,26 @@ int iyk_hip_tlwe2_download(iyk_hip_stream* st, const uint64_t* d_tlwe2, uint32_t
     return row_copy(st, host_tlwe2, d_tlwe2, 2 * ((size_t)n_in + 1), tlwe2_slots, first, count, false, hipMemcpyDeviceToHost);
 }
 
+namespace {
+
+// stage, launch, release of iyk_hip_privks_batch; jobs: args::check_privks_batch's
+int launch_privks(iyk_hip_stream* st, const PrivksKey* key, const uint64_t* d_tlwe2, uint32_t* d_trlwe, const std::vector<PrivksJob>& jobs)
+{
+    const uint64_t count = jobs.size();
+    char* d[1];
+    if (int rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(PrivksJob)}}, d)) return rc;
+    const PrivksJob* d_jobs = (const PrivksJob*)d[0];
+    const PrivksPlan plan = privks_plan((int)count, (int)key->n_in + 1, G.devs[st->gpu].cus);
+    hipLaunchKernelGGL(privks_zero_kernel, dim3((unsigned)count), dim3(256), 0, st->s, d_jobs, d_trlwe);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(privks_kernel, dim3((unsigned)(count * (uint64_t)plan.splits)), dim3(256), 0, st->s, d_jobs, plan.splits,
+                       plan.i_per_split, (const u64*)d_tlwe2, key->n_in + 1, key->t, key->basebit, (const u32*)key->d, d_trlwe);
+    HIP_TRY(hipGetLastError());
+    return release_stage(st);
+}
+
+}  // namespace
+
 int iyk_hip_privks_batch(iyk_hip_stream* st, const void* key_, const uint64_t* d_tlwe2, uint64_t tlwe2_slots, uint64_t count,
                          const int32_t* in, const int32_t* c, uint32_t* d_trlwe, uint64_t trlwe_slots, const int32_t* out)
 {
@@ -2512,65 +2361,25 @@ int iyk_hip_privks_batch(iyk_hip_stream* st, const void* key_, const uint64_t* d
     if (!st || !key || !d_tlwe2 || !in || !c || !d_trlwe || !out) return fail(IYK_ERR_INVALID, "null argument");
     if (st->gpu != key->gpu) return fail(IYK_ERR_INVALID, "the stream and the key are on different GPUs");
     if (count == 0) return IYK_OK;
-    if (count > (1u << 20)) return fail(IYK_ERR_INVALID, "batch too large");
-    if (tlwe2_slots > (1ull << 28) || trlwe_slots > (1ull << 28)) return fail(IYK_ERR_INVALID, "store larger than an allocation can be");
-    int rc = set_device(st->gpu);
-    if (rc) return rc;
-    std::vector<PrivksJob> jobs(count);
-    std::unordered_map<int32_t, uint64_t> writer;   // out row -> its job
-    writer.reserve(count * 2);
-    for (uint64_t g = 0; g < count; ++g) {
-        if (!slot_ok(in[g], tlwe2_slots)) return fail(IYK_ERR_INVALID, "TLWE index outside the lvl2 store");
-        if (c[g] < 0 || c[g] > (int32_t)G.p.k) return fail(IYK_ERR_INVALID, "c outside [0, k]");
-        if (!slot_ok(out[g], trlwe_slots)) return fail(IYK_ERR_INVALID, "TRLWE index outside the buffer");
-        if (!writer.emplace(out[g], g).second) return fail(IYK_ERR_INVALID, "two jobs of one batch write the same TRLWE row");
-        jobs[g] = PrivksJob{in[g], c[g], out[g]};
-    }
-    const size_t bytes = jobs.size() * sizeof(PrivksJob);
-    size_t soff = 0;
-    if ((rc = acquire_stage(st, bytes, &soff))) return rc;
-    std::memcpy(st->h_stage + soff, jobs.data(), bytes);
-    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
-    const PrivksJob* d_jobs = (const PrivksJob*)(st->d_stage + soff);
-    const PrivksPlan plan = privks_plan((int)count, (int)key->n_in + 1, G.devs[st->gpu].cus);
-    hipLaunchKernelGGL(privks_zero_kernel, dim3((unsigned)count), dim3(256), 0, st->s, d_jobs, d_trlwe);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(privks_kernel, dim3((unsigned)(count * (uint64_t)plan.splits)), dim3(256), 0, st->s, d_jobs, plan.splits,
-                       plan.i_per_split, (const u64*)d_tlwe2, key->n_in + 1, key->t, key->basebit, (const u32*)key->d, d_trlwe);
-    HIP_TRY(hipGetLastError());
-    return release_stage(st);
+    if (int rc = set_device(st->gpu)) return rc;
+    std::vector<PrivksJob> jobs;
+    if (const args::Refusal r = args::check_privks_batch(G.p.k, tlwe2_slots, trlwe_slots, count, in, c, out, jobs)) return refuse(r);
+    return launch_privks(st, key, d_tlwe2, d_trlwe, jobs);
     IYK_API_END
 }
 
-int iyk_hip_trgsw_from_rows(iyk_hip_stream* st, void* d_trgsw, uint64_t trgsw_slots, uint64_t count, const int32_t* out_slot,
-                            const uint32_t* d_trlwe, uint64_t trlwe_slots, const int32_t* rows)
+namespace {
+
+// scratch, stage, launches, release of iyk_hip_trgsw_from_rows on lists args::check_trgsw_from_rows has accepted
+int launch_trgsw_from_rows(iyk_hip_stream* st, void* d_trgsw, uint64_t count, const int32_t* out_slot, const uint32_t* d_trlwe, const int32_t* rows)
 {
-    IYK_API_BEGIN
-    if (int rc = need_fft_path("iyk_hip_trgsw_from_rows")) return rc;
-    if (!st || !d_trgsw || !out_slot || !d_trlwe || !rows) return fail(IYK_ERR_INVALID, "null argument");
-    if (count == 0) return IYK_OK;
-    if (trgsw_slots > (1ull << 24) || trlwe_slots > (1ull << 28)) return fail(IYK_ERR_INVALID, "store larger than an allocation can be");
-    if (count > trgsw_slots) return fail(IYK_ERR_INVALID, "more selectors than the store has slots");
-    int rc = set_device(st->gpu);
-    if (rc) return rc;
     const size_t per = (size_t)(G.p.k + 1) * G.p.l, polys = trgsw_polys(), words = polys * NTT_N;   // rows, polynomials, words of a selector
-    std::unordered_map<int32_t, uint64_t> writer;
-    writer.reserve(count * 2);
-    for (uint64_t g = 0; g < count; ++g) {
-        if (!slot_ok(out_slot[g], trgsw_slots)) return fail(IYK_ERR_INVALID, "selector index outside the selector store");
-        if (!writer.emplace(out_slot[g], g).second) return fail(IYK_ERR_INVALID, "two selectors of one call go to the same slot");
-        for (size_t r = 0; r < per; ++r)
-            if (!slot_ok(rows[g * per + r], trlwe_slots)) return fail(IYK_ERR_INVALID, "TRLWE index outside the buffer");
-    }
     const Device& D = G.devs[st->gpu];
-    const size_t bytes = (size_t)count * per * sizeof(int32_t);
-    size_t soff = 0;
-    if ((rc = ensure_sel(st, count, words))) return rc;
-    if ((rc = acquire_stage(st, bytes, &soff))) return rc;
-    std::memcpy(st->h_stage + soff, rows, bytes);
-    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
-    hipLaunchKernelGGL(trlwe_gather_rows_kernel, dim3((unsigned)(count * per)), dim3(256), 0, st->s, d_trlwe,
-                       (const int32_t*)(st->d_stage + soff), st->d_sel);
+    int rc = ensure_sel(st, count, words);
+    if (rc) return rc;
+    char* d[1];
+    if ((rc = stage_put(st, {{rows, (size_t)count * per * sizeof(int32_t)}}, d))) return rc;
+    hipLaunchKernelGGL(trlwe_gather_rows_kernel, dim3((unsigned)(count * per)), dim3(256), 0, st->s, d_trlwe, (const int32_t*)d[0], st->d_sel);
     HIP_TRY(hipGetLastError());
     for (uint64_t g = 0; g < count;) {   // one transform launch per run of consecutive destination slots
         uint64_t e = g + 1;
@@ -2583,6 +2392,20 @@ int iyk_hip_trgsw_from_rows(iyk_hip_stream* st, void* d_trgsw, uint64_t trgsw_sl
         g = e;
     }
     return release_stage(st);
+}
+
+}  // namespace
+
+int iyk_hip_trgsw_from_rows(iyk_hip_stream* st, void* d_trgsw, uint64_t trgsw_slots, uint64_t count, const int32_t* out_slot,
+                            const uint32_t* d_trlwe, uint64_t trlwe_slots, const int32_t* rows)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_trgsw_from_rows")) return rc;
+    if (!st || !d_trgsw || !out_slot || !d_trlwe || !rows) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    if (int rc = set_device(st->gpu)) return rc;
+    if (const args::Refusal r = args::check_trgsw_from_rows(G.p, trgsw_slots, trlwe_slots, count, out_slot, rows)) return refuse(r);
+    return launch_trgsw_from_rows(st, d_trgsw, count, out_slot, d_trlwe, rows);
     IYK_API_END
 }
 
@@ -2690,6 +2513,29 @@ int iyk_hip_bk2_key_upload(iyk_hip_stream* st, void* key_, uint64_t first_step, 
     IYK_API_END
 }
 
+namespace {
+
+// stage, launch, release of iyk_hip_cb_rotate_batch; jobs: args::check_cb_rotate_batch's
+int launch_cb_rotate(iyk_hip_stream* st, const Bk2Key* key, const uint32_t* d_tlwe0, uint64_t* d_tlwe2, const std::vector<CbJob>& jobs)
+{
+    const uint64_t count = jobs.size();
+    char* d[1];
+    if (int rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CbJob)}}, d)) return rc;
+    const unsigned grid = (unsigned)std::min<uint64_t>(count, (uint64_t)G.devs[st->gpu].cus);   // wider batches run in rounds
+    const bool timed = !st->log_on && st->ev_br0 && st->ev_br1;
+    if (timed) HIP_TRY(hipEventRecord(st->ev_br0, st->s));
+    hipLaunchKernelGGL((cb_rotate_kernel<4, 9>), dim3(grid), dim3(CB_LANES), CB_LDS_BYTES, st->s, (const CbJob*)d[0], (int)count,
+                       d_tlwe0, key->n, (const u64*)key->d, (const u64*)key->tw, d_tlwe2);
+    HIP_TRY(hipGetLastError());
+    if (timed) {
+        HIP_TRY(hipEventRecord(st->ev_br1, st->s));
+        st->timing_valid = true, st->timing_has_ks = false;
+    }
+    return release_stage(st);
+}
+
+}  // namespace
+
 int iyk_hip_cb_rotate_batch(iyk_hip_stream* st, const void* key_, const uint32_t* d_tlwe0, uint64_t tlwe0_slots, uint64_t count,
                             const int32_t* in, const int32_t* sign, const uint32_t* off, const uint64_t* mu, uint64_t* d_tlwe2,
                             uint64_t tlwe2_slots, const int32_t* out)
@@ -2700,36 +2546,10 @@ int iyk_hip_cb_rotate_batch(iyk_hip_stream* st, const void* key_, const uint32_t
     if (!st || !key || !d_tlwe0 || !in || !sign || !off || !mu || !d_tlwe2 || !out) return fail(IYK_ERR_INVALID, "null argument");
     if (st->gpu != key->gpu) return fail(IYK_ERR_INVALID, "the stream and the key are on different GPUs");
     if (count == 0) return IYK_OK;
-    if (count > (1u << 20)) return fail(IYK_ERR_INVALID, "batch too large");
-    if (tlwe0_slots > (1ull << 28) || tlwe2_slots > (1ull << 28)) return fail(IYK_ERR_INVALID, "store larger than an allocation can be");
-    int rc = set_device(st->gpu);
-    if (rc) return rc;
-    std::vector<CbJob> jobs(count);
-    std::unordered_map<int32_t, uint64_t> writer;   // out slot -> its job
-    writer.reserve(count * 2);
-    for (uint64_t g = 0; g < count; ++g) {
-        if (!slot_ok(in[g], tlwe0_slots)) return fail(IYK_ERR_INVALID, "TLWE index outside the lvl0 store");
-        if (sign[g] != 1 && sign[g] != -1) return fail(IYK_ERR_INVALID, "sign outside {+1, -1}");
-        if (!slot_ok(out[g], tlwe2_slots)) return fail(IYK_ERR_INVALID, "TLWE index outside the lvl2 store");
-        if (!writer.emplace(out[g], g).second) return fail(IYK_ERR_INVALID, "two jobs of one batch write the same lvl2 TLWE");
-        jobs[g] = CbJob{in[g], sign[g], off[g], out[g], mu[g]};
-    }
-    const size_t bytes = jobs.size() * sizeof(CbJob);
-    size_t soff = 0;
-    if ((rc = acquire_stage(st, bytes, &soff))) return rc;
-    std::memcpy(st->h_stage + soff, jobs.data(), bytes);
-    HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
-    const unsigned grid = (unsigned)std::min<uint64_t>(count, (uint64_t)G.devs[st->gpu].cus);   // wider batches run in rounds
-    const bool timed = !st->log_on && st->ev_br0 && st->ev_br1;
-    if (timed) HIP_TRY(hipEventRecord(st->ev_br0, st->s));
-    hipLaunchKernelGGL((cb_rotate_kernel<4, 9>), dim3(grid), dim3(CB_LANES), CB_LDS_BYTES, st->s, (const CbJob*)(st->d_stage + soff), (int)count,
-                       d_tlwe0, key->n, (const u64*)key->d, (const u64*)key->tw, d_tlwe2);
-    HIP_TRY(hipGetLastError());
-    if (timed) {
-        HIP_TRY(hipEventRecord(st->ev_br1, st->s));
-        st->timing_valid = true, st->timing_has_ks = false;
-    }
-    return release_stage(st);
+    if (int rc = set_device(st->gpu)) return rc;
+    std::vector<CbJob> jobs;
+    if (const args::Refusal r = args::check_cb_rotate_batch(tlwe0_slots, tlwe2_slots, count, in, sign, off, mu, out, jobs)) return refuse(r);
+    return launch_cb_rotate(st, key, d_tlwe0, d_tlwe2, jobs);
     IYK_API_END
 }
 
@@ -2745,54 +2565,23 @@ int iyk_hip_circuit_bootstrap_batch(iyk_hip_stream* st, const void* bk2_key, con
     const Bk2Key* bk2 = (const Bk2Key*)bk2_key;
     const PrivksKey* pk = (const PrivksKey*)privks_key;
     if (!st || !bk2 || !pk || !d_tlwe0 || !in || !sign || !d_tlwe2 || !d_trlwe || !d_trgsw) return fail(IYK_ERR_INVALID, "null argument");
-    // everything the three calls below check, and what only their combination can: all of it before the first launch
     if (st->gpu != bk2->gpu || st->gpu != pk->gpu) return fail(IYK_ERR_INVALID, "the stream and the key are on different GPUs");
     if (bits == 0) return IYK_OK;
-    const uint64_t l = G.p.l, per = (uint64_t)(G.p.k + 1) * l;
-    if (bits > (1u << 20) / per) return fail(IYK_ERR_INVALID, "batch too large");
-    if (tlwe0_slots > (1ull << 28) || tlwe2_slots > (1ull << 28) || trlwe_slots > (1ull << 28) || trgsw_slots > (1ull << 24))
-        return fail(IYK_ERR_INVALID, "store larger than an allocation can be");
-    if (bk2->n != G.p.n) return fail(IYK_ERR_INVALID, "the lvl2 bootstrapping key's n is not the initialised n of the lvl0 store's rows");
-    if (tlwe2_n_in != (uint32_t)CB_N) return fail(IYK_ERR_INVALID, "the lvl2 store's n_in is not the 2048 the rotation writes");
-    if (tlwe2_n_in != pk->n_in) return fail(IYK_ERR_INVALID, "the lvl2 store's n_in is not the private key-switching key's");
-    if (tlwe2_first > tlwe2_slots || bits * l > tlwe2_slots - tlwe2_first) return fail(IYK_ERR_INVALID, "bits * l lvl2 slots from the first do not fit the lvl2 store");
-    if (trlwe_slots < bits * per) return fail(IYK_ERR_INVALID, "the TRLWE scratch store has fewer than bits (k+1) l rows");
-    if (trgsw_first > trgsw_slots || bits > trgsw_slots - trgsw_first) return fail(IYK_ERR_INVALID, "selector slots outside the selector store");
-    for (uint64_t b = 0; b < bits; ++b) {
-        if (!slot_ok(in[b], tlwe0_slots)) return fail(IYK_ERR_INVALID, "TLWE index outside the lvl0 store");
-        if (sign[b] != 1 && sign[b] != -1) return fail(IYK_ERR_INVALID, "sign outside {+1, -1}");
-    }
     int rc = set_device(st->gpu);
     if (rc) return rc;
-    // the two buffers the calls below could have to grow, grown here: the selector scratch and the staging ring's slot (the largest of
-    // the three job lists).  What can still fail after the first launch is the HIP runtime itself (a copy, a launch, an event).
+    // what only the combination can check, then the three parts' own builders: all of it before the first launch
+    args::CbLists lists;
+    if (const args::Refusal r = args::check_circuit_bootstrap_batch(G.p, bk2->n, pk->n_in, tlwe0_slots, in, sign, tlwe2_n_in, tlwe2_slots, tlwe2_first,
+                                                                    trlwe_slots, trgsw_slots, trgsw_first, bits, lists))
+        return refuse(r);
+    // the two buffers the launches below could have to grow, grown here: the selector scratch and the staging ring's slot (the largest of
+    // the three lists).  What can still fail after the first launch is the HIP runtime itself (a copy, a launch, an event).
     if ((rc = ensure_sel(st, bits, trgsw_polys() * NTT_N))) return rc;
-    if ((rc = ensure_stage(st, std::max({(size_t)(bits * l) * sizeof(CbJob), (size_t)(bits * per) * sizeof(PrivksJob),
-                                         (size_t)(bits * per) * sizeof(int32_t)}))))
+    if ((rc = ensure_stage(st, std::max({lists.rot.size() * sizeof(CbJob), lists.privks.size() * sizeof(PrivksJob), lists.rows.size() * sizeof(int32_t)}))))
         return rc;
-    // slot and row order of cmux.selectors_from_tlwe0: lvl2 slot first + bit l + r, scratch row (bit (k+1) + c) l + r
-    std::vector<int32_t> r_in(bits * l), r_sign(bits * l), r_out(bits * l), p_in(bits * per), p_c(bits * per), rows(bits * per), sel(bits);
-    std::vector<uint32_t> r_off(bits * l, 0u);
-    std::vector<uint64_t> r_mu(bits * l);
-    for (uint64_t b = 0; b < bits; ++b) {
-        sel[b] = (int32_t)(trgsw_first + b);
-        for (uint64_t r = 0; r < l; ++r) {
-            r_in[b * l + r] = in[b], r_sign[b * l + r] = sign[b];
-            r_mu[b * l + r] = 1ull << (63 - (r + 1) * G.p.Bgbit);
-            r_out[b * l + r] = (int32_t)(tlwe2_first + b * l + r);
-        }
-        for (uint64_t c = 0; c <= G.p.k; ++c)
-            for (uint64_t r = 0; r < l; ++r) {
-                const uint64_t row = b * per + c * l + r;
-                p_in[row] = (int32_t)(tlwe2_first + b * l + r), p_c[row] = (int32_t)c, rows[row] = (int32_t)row;
-            }
-    }
-    if ((rc = iyk_hip_cb_rotate_batch(st, bk2, d_tlwe0, tlwe0_slots, bits * l, r_in.data(), r_sign.data(), r_off.data(), r_mu.data(), d_tlwe2,
-                                      tlwe2_slots, r_out.data())))
-        return rc;
-    if ((rc = iyk_hip_privks_batch(st, pk, d_tlwe2, tlwe2_slots, bits * per, p_in.data(), p_c.data(), d_trlwe, trlwe_slots, rows.data())))
-        return rc;
-    return iyk_hip_trgsw_from_rows(st, d_trgsw, trgsw_slots, bits, sel.data(), d_trlwe, trlwe_slots, rows.data());
+    if ((rc = launch_cb_rotate(st, bk2, d_tlwe0, d_tlwe2, lists.rot))) return rc;
+    if ((rc = launch_privks(st, pk, d_tlwe2, d_trlwe, lists.privks))) return rc;
+    return launch_trgsw_from_rows(st, d_trgsw, bits, lists.sel.data(), d_trlwe, lists.rows.data());
     IYK_API_END
 }
 

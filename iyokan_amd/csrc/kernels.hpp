@@ -26,27 +26,9 @@
 #include "blind_rotate_fp.hpp"
 #include "blind_rotate_lat3.hpp"
 #include "blind_rotate_t16.hpp"   // arrangement-P helpers of the 16-points-per-lane transform (used by the lat3 kernel)
+#include "jobs.hpp"               // RotJob, KsJob, EwJob, TrlweAddJob
 
 namespace iyk {
-
-// one blind rotation: lin = sa*arena[ia] + sb*arena[ib] + (0,..,0,off)
-struct RotJob {
-    int32_t ia, ib;
-    int32_t sa, sb;
-    uint32_t off;
-};
-
-// one key switch: tlwe1 = rot[ra] (+ rot[rb] if rb >= 0) + (0,..,0,off); result -> arena[out]
-struct KsJob {
-    int32_t ra, rb;
-    uint32_t off;
-    int32_t out;
-};
-
-// NOT / COPY / CONST on arena slots
-struct EwJob {
-    int32_t op, in, out;
-};
 
 static constexpr int BR_WAVES = 8;  // rotation jobs (wavefronts) per workgroup; one workgroup per CU
 
@@ -905,9 +887,6 @@ __global__ __launch_bounds__(256) void sample_extract_index_kernel(const u32* __
 // T[out] = T[a] + T[b] mod 2^32 on TRLWE rows, b0_offset added to coefficient 0 of the b polynomial: the tail of TFHEpp's HomMUXwoSE
 // (the sum of its two blind rotations, + mu).  One workgroup per job {a, b, out}; a word is read and written by the same thread, so
 // out may be a or b.
-struct TrlweAddJob {
-    int32_t a, b, out;
-};
 IYK_HD u32 trlwe_add_word(const u32* ra, const u32* rb, int j, u32 b0_offset) { return ra[j] + rb[j] + (j == NTT_N ? b0_offset : 0u); }
 __global__ __launch_bounds__(256) void trlwe_add_kernel(u32* trlwe, const TrlweAddJob* __restrict__ jobs, u32 b0_offset)
 {

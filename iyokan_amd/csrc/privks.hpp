@@ -22,12 +22,9 @@
 // /root/reference/src/iyokan_tfhepp.hpp:194-236), restated from the published algorithm.
 #pragma once
 #include "goldilocks.hpp"   // IYK_HD, u32 / u64
+#include "jobs.hpp"         // PrivksJob
 
 namespace iyk {
-
-struct PrivksJob {
-    int32_t in, c, out;
-};
 
 static constexpr int PRIVKS_UNROLL = 5;    // key rows of one input word in flight per lane pair of loads (t = 10: two rounds)
 static constexpr int PRIVKS_ROW_WORDS = 2 * 1024;   // 2N, N = 1024 (static_assert against NTT_N where the kernels are compiled)
