@@ -246,6 +246,11 @@ def growth_points(prog, n1):
 THREAD_INPUTS = 64
 FRESH_GATES = 64          # leading gates of a wide level that read the common inputs only: the oracle needs no earlier level for them
 KS_TABLE_MIN = 4097       # smallest batch the key-switch table kernel takes (dispatch.hpp: KS_LUT_MIN_JOBS + 1)
+KS_MATRIX_GROUP = 256     # key switches per workgroup of the matrix form (dispatch.hpp: KS_MATRIX_GATES)
+KS_MATRIX_EDGE = 2 * KS_MATRIX_GROUP + 1   # two whole workgroups and a third that holds one job
+# key-switch jobs of the core gates that write high slots, per batch of the huge-arena test: between them job 0, both sides of the
+# boundary between two workgroups, and the last job
+KS_MATRIX_AT = {"X": (0, KS_MATRIX_GROUP - 1, KS_MATRIX_GROUP), "Y": (KS_MATRIX_GROUP - 1, KS_MATRIX_GROUP, KS_MATRIX_EDGE - 1)}
 
 
 def thread_programs(rng, threads, rotation_round=2048):

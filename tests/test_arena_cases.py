@@ -88,6 +88,25 @@ def test_sentinels_are_recognisable(n1):
         assert lo >= start and not set(range(lo, lo + count)) & (set(sent) | set(chosen))
 
 
+def test_key_switch_thresholds_mirror_the_library():
+    """KS_TABLE_MIN and the matrix form's workgroup are the library's (csrc/dispatch.hpp through libiyk_emul.so), and the jobs the
+    huge-arena test gives its high outputs under the matrix form are the first, both sides of a workgroup boundary, and the last."""
+    import ctypes
+    import os
+
+    import ks_words as K
+
+    em = ctypes.CDLL(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "iyokan_amd", "lib", "libiyk_emul.so"))
+    assert ac.KS_TABLE_MIN == K.TABLE_MIN_JOBS + 1 < em.iyk_emul_ks_matrix_min_jobs()
+    assert ac.KS_MATRIX_GROUP == em.iyk_emul_ks_matrix_gates(0) and ac.KS_MATRIX_EDGE == 513
+    for t, nc in ((7, 5), (8, 4)):
+        assert K.ks_geometry("2", None, ac.KS_TABLE_MIN, t, 256)[0] == "table" and K.ks_geometry("2", None, ac.KS_TABLE_MIN - 1, t, 256)[0] != "table"
+    at = ac.KS_MATRIX_AT
+    assert set(at["X"]) | set(at["Y"]) == {0, 255, 256, 512} and all(len(v) == 3 and max(v) < ac.KS_MATRIX_EDGE for v in at.values())
+    assert {j // ac.KS_MATRIX_GROUP for v in at.values() for j in v} == {0, 1, 2}
+    assert -(-ac.KS_MATRIX_EDGE // ac.KS_MATRIX_GROUP) == 3 and ac.KS_MATRIX_EDGE % ac.KS_MATRIX_GROUP == 1
+
+
 def _levels_of_growth(prog):
     return [s[1] for s in prog["steps"] if s[0] == "gates"]
 

@@ -74,8 +74,10 @@ def test_arena_beyond_16_gib(keys128, oracle128, monkeypatch):
       stage 2  gate_batch with inputs and outputs on the high slots, every gate kind (NOT / COPY / CONST* write and read them too), once
                per key-switch form: IYK_HIP_KS_KERNEL=0, =1 with IYK_HIP_KS_SHARED_MAX=0 (wide form), default (shared form), and =2 with
                4 097 key switches (the table kernel; the high outputs are jobs 0, 2 050 and 4 096: its first, a middle and its last
-               workgroup).  The 4 088 filler gates run on low slots: a 24-gate sample against the oracle, all against the same batch
-               under IYK_HIP_KS_KERNEL=1.
+               workgroup), and =3 with 2 x 256 + 1 key switches (the matrix form, keyswitch_mfma_kernel; the high outputs are jobs 0,
+               255 and 256 of the first batch and 255, 256 and 512 of the second: the first job, both sides of a workgroup boundary and
+               the last job, a workgroup's only one).  The filler gates run on low slots: a 24-gate sample against the oracle, all
+               against the same batch under IYK_HIP_KS_KERNEL=1.
       stage 3  blind_rotate_batch reading the high slots; bootstrap_trlwe_batch + sample_extract_keyswitch_batch writing them.
     Left out: iyk_hip_arena_sync_slots wants the same slot range on both arenas, so two such arenas; its two kernels are the ones
     upload_slots / download_slots run.  Arenas above 2^31 slots do not exist (int32 descriptors)."""
@@ -191,6 +193,15 @@ def test_arena_beyond_16_gib(keys128, oracle128, monkeypatch):
         for lv, core in ((X2, X), (Y2, Y)):                        # first, a middle and the last 128-gate workgroup of the table kernel
             ks_out = lv["out"][lv["ops"] <= OPS["MUX"]]
             assert len(ks_out) == ac.KS_TABLE_MIN and [ks_out[0], ks_out[2050], ks_out[4096]] == list(core["out"][:3])
+        rng3 = np.random.default_rng(13)                           # the matrix form's fillers: their own stream, the draws above stay as they were
+        at3 = {"X": list(ac.KS_MATRIX_AT["X"]) + [1, 2, 3, 4, 5, 6], "Y": list(ac.KS_MATRIX_AT["Y"]) + [0, 1, 2]}
+        fx3 = ac.gate_level(rng3, ac.KS_MATRIX_EDGE - 9, np.concatenate([LIN, A]), FILL)
+        fy3 = ac.gate_level(rng3, ac.KS_MATRIX_EDGE - 6, np.concatenate([LIN, B]), FILL)
+        X3, Y3 = _widen(X, fx3, at3["X"]), _widen(Y, fy3, at3["Y"])
+        assert ac.independent(X3) and ac.independent(Y3)
+        for lv, core, name in ((X3, X, "X"), (Y3, Y, "Y")):         # job 0, jobs 255 | 256 (two workgroups), job 512 (the third's only one)
+            ks_out = lv["out"][lv["ops"] <= OPS["MUX"]]
+            assert len(ks_out) == ac.KS_MATRIX_EDGE and [ks_out[j] for j in ac.KS_MATRIX_AT[name]] == list(core["out"][:3])
         start = dict(zip(list(H) + [int(s) for s in LIN], fresh(len(H) + len(LIN))))
         after = {}                                                 # the oracle, once: every form starts from the same rows
         state = dict(start)
@@ -198,30 +209,32 @@ def test_arena_beyond_16_gib(keys128, oracle128, monkeypatch):
             state.update(_oracle_levels(orc, state, [lv]))
             after[name] = dict(state)
         sample = rng.choice(len(fx["ops"]), size=24, replace=False)
-        forms = [("0", None, "keyswitch_kernel"), ("1", "0", "wave kernel, wide form"), (None, None, "wave kernel, shared form"),
-                 ("2", None, "table kernel")]
-        for kernel, shared_max, what in forms:
+        sample3 = rng3.choice(len(fx3["ops"]), size=24, replace=False)
+        forms = [("0", None, "keyswitch_kernel", None), ("1", "0", "wave kernel, wide form", None), (None, None, "wave kernel, shared form", None),
+                 ("2", None, "table kernel", {"X": (X2, fx), "Y": (Y2, fy), "sample": sample}),
+                 ("3", None, "matrix form", {"X": (X3, fx3), "Y": (Y3, fy3), "sample": sample3})]
+        for kernel, shared_max, what, wide in forms:
             for var, val in (("IYK_HIP_KS_KERNEL", kernel), ("IYK_HIP_KS_SHARED_MAX", shared_max)):
                 monkeypatch.delenv(var, raising=False) if val is None else monkeypatch.setenv(var, val)
             for s, row in start.items():
                 put(s, row)
             arm()
-            for name, small, big, fill in (("X", X, X2, fx), ("Y", Y, Y2, fy), ("Z", Z, Z, None)):
+            for name, small in (("X", X), ("Y", Y), ("Z", Z)):
                 stage = f"stage 2 ({what}, batch {name})"
-                lv = big if kernel == "2" else small
+                lv, fill = wide[name] if wide is not None and name in wide else (small, None)
                 st.gate_batch(arena, *ac.level_args(lv))
                 st.sync()
                 model.update({s: after[name][s] for s in list(H) + [int(o) for o in small["out"]]})
                 check(stage, also=[o for o in small["out"] if o not in H])
-                if kernel == "2" and fill is not None:
+                if fill is not None:
                     got = st.download(arena, FILL, len(fill["ops"]))
                     monkeypatch.setenv("IYK_HIP_KS_KERNEL", "1")    # the batch writes none of its inputs: run again, same rows
                     st.gate_batch(arena, *ac.level_args(lv))
                     st.sync()
-                    monkeypatch.setenv("IYK_HIP_KS_KERNEL", "2")
+                    monkeypatch.setenv("IYK_HIP_KS_KERNEL", kernel)
                     assert np.array_equal(got, st.download(arena, FILL, len(fill["ops"]))), f"{stage}: filler gates differ from IYK_HIP_KS_KERNEL=1"
                     # the fillers read the low inputs and A (batch X) or B as X left it (batch Y): the rows after X hold both
-                    ref = _oracle_levels(orc, {s: after["X"][s] for s in list(H) + [int(x) for x in LIN]}, [_take(fill, sample)])
+                    ref = _oracle_levels(orc, {s: after["X"][s] for s in list(H) + [int(x) for x in LIN]}, [_take(fill, wide["sample"])])
                     for o, r in ref.items():
                         assert np.array_equal(got[o - FILL], r), f"{stage}: filler gate writing slot {o} differs from the oracle"
                     check(stage + ", after the second run", also=[o for o in small["out"] if o not in H])
@@ -263,17 +276,15 @@ def test_arena_beyond_16_gib(keys128, oracle128, monkeypatch):
         hip.cleanup()
 
 
-@pytest.mark.parametrize("which", ["128", "80"])
-def test_buffers_grow_behind_queued_batches(which, request, monkeypatch):
-    """One stream, nothing that synchronises between the first upload and the last download: arena_cases.growth_program queues 2 gates
-    (which leave a 4 352-byte staging slot and 67 rotation rows), 200 gates (both buffers are reallocated while the 2 gates may still
-    run), 1 gate, upload_slots of 300 rows (staging reallocated again), 700 gates that read those rows (rotation buffer reallocated
-    again), ten batches of 1 - 3 gates (the ring of eight staging slots wraps after the growths) and a download_slots behind all of it
-    — each step reading what the step before wrote.  tests/test_arena_cases.py derives the reallocations from the growth policy.  The
-    whole arena equals the oracle's, the download_slots rows equal the same rows of the final download, every bit decrypts right."""
+def _growth_case(which, request, monkeypatch, ks_kernel=None):
+    """arena_cases.growth_program on one stream with nothing that synchronises between the first upload and the last download, under
+    IYK_HIP_KS_KERNEL=ks_kernel (None: unset), and its three assertions: the whole arena equals the oracle's, the download_slots rows
+    equal the same rows of the final download, every bit decrypts right."""
     from iyokan_amd import hip
 
     _default_env(monkeypatch)
+    if ks_kernel is not None:
+        monkeypatch.setenv("IYK_HIP_KS_KERNEL", ks_kernel)
     keys = request.getfixturevalue("keys" + which)
     orc = request.getfixturevalue("oracle" + which)
     n1 = keys.params.n + 1
@@ -311,6 +322,17 @@ def test_buffers_grow_behind_queued_batches(which, request, monkeypatch):
     assert bad.size == 0, f"slots that differ from the oracle: {bad[:10]} ... ({bad.size})"
     assert np.array_equal(final, got[prog["final"]])
     assert np.array_equal(client.decrypt_bits(keys, got), ac.simulate_growth(prog).astype(np.uint8))
+
+
+@pytest.mark.parametrize("which", ["128", "80"])
+def test_buffers_grow_behind_queued_batches(which, request, monkeypatch):
+    """One stream, nothing that synchronises between the first upload and the last download: arena_cases.growth_program queues 2 gates
+    (which leave a 4 352-byte staging slot and 67 rotation rows), 200 gates (both buffers are reallocated while the 2 gates may still
+    run), 1 gate, upload_slots of 300 rows (staging reallocated again), 700 gates that read those rows (rotation buffer reallocated
+    again), ten batches of 1 - 3 gates (the ring of eight staging slots wraps after the growths) and a download_slots behind all of it
+    — each step reading what the step before wrote.  tests/test_arena_cases.py derives the reallocations from the growth policy.  The
+    whole arena equals the oracle's, the download_slots rows equal the same rows of the final download, every bit decrypts right."""
+    _growth_case(which, request, monkeypatch)
 
 
 def _join(threads, what):

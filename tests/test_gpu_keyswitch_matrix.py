@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import ks_matrix_cases as M
 import ks_words as K
 from iyokan_amd import client
 from iyokan_amd.params import OPS
@@ -25,50 +26,14 @@ def _emul():
     return L
 
 
-def _carry_keys(keys):
-    """The key set with the rows of coefficients 0, 1, 511 and 1023 replaced by words whose four bytes are 0x80 / 0x7F in every
-    mix: the signed split carries (or not) out of every plane.  Both kernels get the same key, so they stay comparable."""
-    p = keys.params
-    ksk = np.array(keys.ksk, dtype=np.uint32).reshape(p.N, p.t, 3, p.n + 1).copy()
-    pat = np.array([sum((0x80 if (m >> b) & 1 else 0x7F) << (8 * b) for b in range(4)) for m in range(16)], dtype=np.uint32)
-    for i in (0, 1, 511, 1023):
-        for j in range(p.t):
-            for u in range(3):
-                ksk[i, j, u] = pat[(np.arange(p.n + 1) + i + 3 * j + u) % 16]
-    return client.KeySet(p, keys.s0, keys.s1, keys.bk, ksk.ravel())
+_carry_keys = M.carry_keys    # the doctored key and the named cells live in ks_matrix_cases.py (checked by test_ks_matrix_cases.py)
 
 
 def _cells(p, seed):
     """[NCELLS][2 N] TRLWE images: first the cells named by the test — every digit 0, every digit 3, a' = 0xFFFFFFFF, a' = -prec,
     one non-zero digit at (i, j) in the four corners —, then the families of ks_words.chosen_images, then uniform words.
     Returns (cells, number of named cells, number of named + chosen cells, t1[N] of the every-digit-0 cell)."""
-    N, t = p.N, p.t
-    rng = np.random.default_rng(seed)
-    low = 1 << (32 - 2 * t)
-    named = []
-
-    def add(a):
-        w = np.empty(N + 1, dtype=np.uint32)
-        w[:N] = a
-        w[N] = rng.integers(0, 1 << 32, dtype=np.uint64)
-        named.append(w)
-
-    add(K.words_from_digits(np.zeros(N, dtype=np.int64), rng.integers(0, low, size=N, dtype=np.uint64), t))
-    add(K.words_from_digits(np.full(N, (1 << 2 * t) - 1), rng.integers(0, low, size=N, dtype=np.uint64), t))
-    add(np.full(N, 0xFFFFFFFF, dtype=np.uint32))
-    add(np.full(N, (1 << 32) - K.prec_of(t), dtype=np.uint64).astype(np.uint32))
-    for k, (i, j) in enumerate(((0, 0), (0, t - 1), (N - 1, 0), (N - 1, t - 1))):
-        D = np.zeros(N, dtype=np.int64)
-        D[i] = (1 + k % 3) << (2 * (t - 1 - j))
-        add(K.words_from_digits(D, rng.integers(0, low, size=N, dtype=np.uint64), t))
-    imgs, _ = K.chosen_images(p, seed)
-    cells = np.empty((NCELLS, 2 * N), dtype=np.uint32)
-    for c, w in enumerate(named):
-        cells[c] = K.image_from_t1(w, rng, N)
-    cells[len(named):len(named) + len(imgs)] = imgs
-    first = len(named) + len(imgs)
-    cells[first:] = rng.integers(0, 1 << 32, size=(NCELLS - first, 2 * N), dtype=np.uint32)
-    return cells, len(named), first, int(named[0][N])
+    return M.cells(p, seed, NCELLS)
 
 
 def _both(hip, st, d_trlwe, idx, p, monkeypatch, kinds, seed):
