@@ -388,6 +388,12 @@ int iyk_hip_bk2_key_bytes(int gpu_index, uint64_t* out);
 int iyk_hip_cb_rotate_batch(iyk_hip_stream* st, const void* key, const uint32_t* d_tlwe0, uint64_t tlwe0_slots, uint64_t count,
                             const int32_t* in, const int32_t* sign, const uint32_t* off, const uint64_t* mu, uint64_t* d_tlwe2,
                             uint64_t tlwe2_slots, const int32_t* out);
+/* *form_out = the kernel form a batch of count rotations would run on GPU gpu_index now: 0 = cb_rotate_kernel (256 lanes, the wide-batch
+ * form), 1 = cb_rotate_lat_kernel (512 lanes, wave-owned polynomials, 4 barriers per step: the narrow-batch form).  Both give the same
+ * words.  The answer of dispatch::cb_plan (csrc/dispatch.hpp) with the current environment: IYK_HIP_CB_KERNEL = wg / lat forces a form
+ * and is read per batch; any other value is IYK_ERR_INVALID here and in every call that rotates (nothing is launched).  A GPU that did
+ * not grant the narrow-batch form its 160 KiB of LDS at iyk_hip_init answers 0 whatever is asked for. */
+int iyk_hip_cb_rotate_form(int gpu_index, uint64_t count, int* form_out);
 
 /* The whole circuit bootstrapping of `bits` address bits as ONE checked call: the three calls above with the slot and row order of
  * cmux.selectors_from_tlwe0.  Bit b is TLWE in[b] of the lvl0 store, taken with sign[b] (-1: the selector of the negated bit); its l

@@ -184,5 +184,38 @@ inline PrivksPlan privks_plan(int njobs, int n_words, int cus)
     return PrivksPlan{(n_words + per - 1) / per, per};
 }
 
+// ---- circuit bootstrapping's lvl0 -> lvl2 rotation (cb_rotate.hpp, cb_rotate_lat.hpp) ------------------------------------------
+
+enum { CB_FORM_WG = 0, CB_FORM_LAT = 1 };   // cb_rotate_kernel (256 lanes), cb_rotate_lat_kernel (512 lanes, wave-owned polynomials)
+// What IYK_HIP_CB_KERNEL names: unset, "wg", "lat", anything else
+enum { CB_KIND_AUTO = -1, CB_KIND_WG = 0, CB_KIND_LAT = 1, CB_KIND_UNKNOWN = 2 };
+// IYK_HIP_CB_KERNEL unset: batches of up to this many rotations run the latency form, wider ones cb_rotate_kernel; 0: none does.
+// The widths at which the latency form was faster in every interleaved pair by more than the larger spread: all five measured, 1 to
+// 258 rotations (two rounds on 256 CUs), at both parameter sets, by a factor of two (profiles/cb_rotate_lat_ab.txt).  Wider batches
+// are more rounds of the same workgroups in either form, so no width is left to cb_rotate_kernel: no limit.
+constexpr long CB_LAT_MAX_JOBS = 1L << 62;
+
+struct CbPlan {
+    int form;   // CB_FORM_*; negative: the kind is refused, nothing is launched
+    int grid;   // workgroups: one per rotation up to one per CU, wider batches run in rounds inside the launch
+};
+constexpr int cb_kind_of(const char* text)
+{
+    if (!text) return CB_KIND_AUTO;
+    if (text[0] == 'w' && text[1] == 'g' && text[2] == 0) return CB_KIND_WG;
+    if (text[0] == 'l' && text[1] == 'a' && text[2] == 't' && text[3] == 0) return CB_KIND_LAT;
+    return CB_KIND_UNKNOWN;
+}
+// A device that was not granted the latency form's LDS runs cb_rotate_kernel whatever is asked for; an unknown kind stays refused.
+constexpr int cb_kind_for_device(int kind_env, bool lat_granted) { return lat_granted || kind_env == CB_KIND_UNKNOWN ? kind_env : CB_KIND_WG; }
+constexpr CbPlan cb_plan(long count, int cus, int kind_env)
+{
+    const int grid = (int)(count < (long)cus ? count : (long)cus);
+    if (kind_env == CB_KIND_WG) return {CB_FORM_WG, grid};
+    if (kind_env == CB_KIND_LAT) return {CB_FORM_LAT, grid};
+    if (kind_env != CB_KIND_AUTO) return {-1, 0};
+    return {count <= CB_LAT_MAX_JOBS ? CB_FORM_LAT : CB_FORM_WG, grid};
+}
+
 }  // namespace dispatch
 }  // namespace iyk

@@ -22,6 +22,7 @@
 #include "dispatch.hpp"
 #include "privks.hpp"
 #include "cb_rotate.hpp"
+#include "cb_rotate_lat.hpp"
 
 using namespace iyk;
 
@@ -1325,6 +1326,116 @@ int iyk_emul_cb_rotate(uint32_t n, uint32_t l2, uint32_t Bgbit2, const uint32_t*
     cb_rotate<4, 9>(n, w, CbJob{0, sign, off, 0, mu}, bk_ntt, out);
     return 0;
 }
+}
+
+/* ---- cb_rotate_lat.hpp: the latency form's passes and one job, lane by lane; dispatch::cb_plan ------------------------------------ */
+namespace {
+// the N2 transform through the latency form's passes and one unpadded, swizzled slot
+void cbl_forward(const u64* in, u64* out)
+{
+    const u64* twf = cb_tables().tw.data();
+    std::vector<u64> bp(CBL_SLOT);
+    for (int j1 = 0; j1 < 64; ++j1) {
+        u64 x[32];
+        for (int j2 = 0; j2 < 32; ++j2) x[j2] = gl_mul_pow2(in[j1 + 64 * j2], LOG_ZETA * j2);
+        cbl_pass1_fwd(j1, x, twf, bp.data());
+    }
+    std::vector<std::array<u64, 32>> X(64);
+    for (int u = 0; u < 64; ++u) cbl_pass2_fwd_read(u, bp.data(), reinterpret_cast<u64(&)[32]>(*X[u].data()));
+    for (int u = 0; u < 64; ++u) cbl_pass2_fwd_write(u, reinterpret_cast<const u64(&)[32]>(*X[u].data()), out);
+}
+void cbl_inverse(const u64* in, u64* out)
+{
+    const u64* twi = cb_tables().tw.data() + CB_N;
+    std::vector<u64> bp(in, in + CB_N);
+    std::vector<std::array<u64, 32>> X(64);
+    for (int u = 0; u < 64; ++u) cbl_pass1_inv_read(u, bp.data(), twi, reinterpret_cast<u64(&)[32]>(*X[u].data()));
+    for (int u = 0; u < 64; ++u) cbl_pass1_inv_write(u, reinterpret_cast<const u64(&)[32]>(*X[u].data()), bp.data());
+    for (int j1 = 0; j1 < 64; ++j1) {
+        u64 y[32];
+        cbl_pass2_inv(j1, bp.data(), y);
+        for (int p = 0; p < 32; ++p) out[j1 + 64 * brv5(p)] = y[p];
+    }
+}
+
+// lane-by-lane run of cb_rotate_lat_kernel for one job: the same phase functions in the same order, one loop over the lanes wherever
+// the kernel has a workgroup barrier or a wave-level ordering point
+template <int L2, int BGBIT2>
+void cb_rotate_lat(u32 n, const u32* w, const CbJob& jb, const u64* bk, u64* out)
+{
+    const u64* twf = cb_tables().tw.data();
+    const u64* twi = twf + CB_N;
+    std::vector<u64> acc(2 * CB_N), buf((size_t)CB_ROWS * CBL_SLOT);
+    struct Lane {
+        u64 x[32], accum[16];
+        CbPair pf[CBL_PF];
+    };
+    std::vector<Lane> R(CBL_LANES);
+#define CBL_LANES_ALL for (int lane = 0; lane < CBL_LANES; ++lane)
+#define CBL_LANES_INV for (int lane = 0; lane < 4 * 64; ++lane)
+    CBL_LANES_ALL cbl_prologue(lane, jb, w, n, acc.data());
+    CBL_LANES_ALL cbl_prefetch(lane, bk, R[lane].pf);
+    u32 ab = cbl_abar(jb, w, n, 0);
+    for (u32 i = 0; i < n; ++i) {
+        const u64* bk_step = bk + (size_t)i * CB_STEP_WORDS;
+        const u32 ab_next = cbl_abar(jb, w, n, i + 1);
+        CBL_LANES_ALL cbl_fwd1<L2, BGBIT2>(lane, ab, acc.data(), twf, buf.data());
+        CBL_LANES_ALL cbl_fwd2_read(lane, buf.data(), R[lane].x);
+        CBL_LANES_ALL cbl_fwd2_write(lane, R[lane].x, buf.data());
+        CBL_LANES_ALL cbl_mac(lane, buf.data(), bk_step, R[lane].pf, R[lane].accum);
+        CBL_LANES_ALL cbl_inv_write(lane, R[lane].accum, buf.data());
+        if (i + 1 < n) CBL_LANES_ALL cbl_prefetch(lane, bk_step + CB_STEP_WORDS, R[lane].pf);
+        CBL_LANES_INV cbl_inv1_read(lane, buf.data(), twi, R[lane].x);
+        CBL_LANES_INV cbl_inv1_write(lane, R[lane].x, buf.data());
+        CBL_LANES_INV cbl_inv2(lane, buf.data(), acc.data());
+        ab = ab_next;
+    }
+    for (int j = 0; j <= CB_N; ++j) out[j] = cb_extract_word(acc.data(), j, jb.mu);
+#undef CBL_LANES_ALL
+#undef CBL_LANES_INV
+}
+}  // namespace
+
+extern "C" {
+/* the latency form's 64-point pass alone (two lanes of 32 points, the first butterfly stage folded into the read), result in natural
+ * order; inverse != 0: the root 2^-3, unscaled (a table of ones) */
+void iyk_emul_cb_lat_ntt64(const uint64_t* in, int inverse, uint64_t* out)
+{
+    const int k2 = 5;
+    std::vector<u64> bp(CBL_SLOT, 0), ones(CB_N, 1);
+    for (int j = 0; j < 64; ++j) bp[inverse ? k2 + 32 * j : k2 * 64 + (j ^ k2)] = in[j];
+    for (int half = 0; half < 2; ++half) {
+        u64 x[32];
+        if (inverse) cbl_pass1_inv_read(k2 + 32 * half, bp.data(), ones.data(), x);
+        else cbl_pass2_fwd_read(k2 + 32 * half, bp.data(), x);
+        for (int p = 0; p < 32; ++p) out[2 * brv5(p) + half] = x[p];
+    }
+}
+/* the N2 = 2048 negacyclic transform through the latency form's passes, natural order on both sides */
+void iyk_emul_cb_lat_ntt(const uint64_t* in, int inverse, uint64_t* out)
+{
+    if (inverse) cbl_inverse(in, out);
+    else cbl_forward(in, out);
+}
+/* one job of cb_rotate_lat_kernel: the arguments of iyk_emul_cb_rotate */
+int iyk_emul_cb_rotate_lat(uint32_t n, uint32_t l2, uint32_t Bgbit2, const uint32_t* w, int32_t sign, uint32_t off, uint64_t mu,
+                           const uint64_t* bk_ntt, uint64_t* out)
+{
+    if (l2 != 4 || Bgbit2 != 9 || n == 0 || n > CB_MAX_N0 || (sign != 1 && sign != -1)) return -1;
+    cb_rotate_lat<4, 9>(n, w, CbJob{0, sign, off, 0, mu}, bk_ntt, out);
+    return 0;
+}
+/* dispatch::cb_plan; kind_env: -1 unset, 0 wg, 1 lat, 2 anything else.  Returns 0, or -1 where the kind is refused (form = -1, grid = 0) */
+int iyk_emul_cb_plan(uint64_t count, int cus, int kind_env, int* form, int* grid)
+{
+    const dispatch::CbPlan p = dispatch::cb_plan((long)count, cus, kind_env);
+    *form = p.form, *grid = p.grid;
+    return p.form < 0 ? -1 : 0;
+}
+/* the kind cb_plan is given: what the text of IYK_HIP_CB_KERNEL names (null: unset) on a device that was or was not granted the latency form's LDS */
+int iyk_emul_cb_kind(const char* text, int lat_granted) { return dispatch::cb_kind_for_device(dispatch::cb_kind_of(text), lat_granted != 0); }
+/* dispatch::CB_LAT_MAX_JOBS: the widest batch the latency form takes when nothing is forced (0: none) */
+uint64_t iyk_emul_cb_lat_max_jobs(void) { return (uint64_t)dispatch::CB_LAT_MAX_JOBS; }
 }
 
 /* ---- batch_args.hpp: the argument checks and job lists of the batch entry points ------------------------------------------------

@@ -47,6 +47,7 @@
 #include "privks.hpp"
 #include "keyswitch_mfma.hpp"
 #include "cb_rotate.hpp"
+#include "cb_rotate_lat.hpp"
 
 using namespace iyk;
 using namespace iyk::dispatch;
@@ -108,6 +109,7 @@ struct Device {
     struct GateCoalescer* co = nullptr;   // lazily created by iyk_hip_gate_host (one per GPU); freed by iyk_hip_cleanup
     uint64_t privks_bytes = 0;     // device memory of the live private key-switch keys of this GPU (iyk_hip_privks_key_*): __atomic adds
     uint64_t bk2_bytes = 0;        // device memory of the live lvl2 bootstrapping keys of this GPU (iyk_hip_bk2_key_*): __atomic adds
+    bool cb_lat_granted = false;   // cb_rotate_lat_kernel's dynamic LDS was granted at init (set_kernel_attrs); else every batch runs cb_rotate_kernel
     int max_passes = 0;            // cost.max_passes as the dispatch reads it: __atomic loads / stores, lock-free (a calibration may run
                                    // beside a batch; a plain int keeps Device copyable)
     void release()
@@ -651,8 +653,13 @@ int set_fft_attrs()
     if ((rc = set_lds(cmux_chain_kernel<GD, false>, BR_FFT_LDS_BYTES))) return rc;
     return set_lds(cmux_chain_kernel<GD, true>, BR_FFT_LDS_BYTES);
 }
-int set_kernel_attrs(const iyk_params& p, bool use_fp, int split)
+int set_kernel_attrs(const iyk_params& p, bool use_fp, int split, bool* cb_lat_granted)
 {
+    // the latency form of the lvl2 rotation asks for the whole LDS of a CU: a device that does not grant it runs cb_rotate_kernel
+    // (dispatch::cb_kind_for_device), initialisation does not fail
+    *cb_lat_granted = hipFuncSetAttribute(reinterpret_cast<const void*>(cb_rotate_lat_kernel<4, 9>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)CBL_LDS_BYTES) == hipSuccess;
+    if (!*cb_lat_granted) (void)hipGetLastError();   // not sticky: leave no pending error behind
     int rc = with_rot_set(p, split, [&](auto dc, auto gd) {
         typedef decltype(dc) DC;
         if (!use_fp) return set_lds(blind_rotate_kernel<DC::L, DC::BGBIT>, BR_LDS_BYTES);
@@ -781,7 +788,7 @@ int init_devices(std::vector<Device>& devs, const int* device_ids, int avail, co
             cleanup();
             return fail(IYK_ERR_HIP, "device reports no compute units");
         }
-        int rc = set_kernel_attrs(p, use_fp, split);
+        int rc = set_kernel_attrs(p, use_fp, split, &D.cb_lat_granted);
         if (rc) {
             cleanup();
             return rc;
@@ -2515,17 +2522,28 @@ int iyk_hip_bk2_key_upload(iyk_hip_stream* st, void* key_, uint64_t first_step, 
 
 namespace {
 
+// cb_plan for this batch: IYK_HIP_CB_KERNEL ("wg" / "lat") is read per batch (A/B, tests), like IYK_HIP_ROT_KERNEL
+CbPlan cb_plan_of_batch(const Device& D, uint64_t count)
+{
+    return cb_plan((long)count, D.cus, cb_kind_for_device(cb_kind_of(std::getenv("IYK_HIP_CB_KERNEL")), D.cb_lat_granted));
+}
+
 // stage, launch, release of iyk_hip_cb_rotate_batch; jobs: args::check_cb_rotate_batch's
 int launch_cb_rotate(iyk_hip_stream* st, const Bk2Key* key, const uint32_t* d_tlwe0, uint64_t* d_tlwe2, const std::vector<CbJob>& jobs)
 {
     const uint64_t count = jobs.size();
+    const CbPlan plan = cb_plan_of_batch(G.devs[st->gpu], count);   // before anything is staged: a refused kind launches nothing
+    if (plan.form < 0) return fail(IYK_ERR_INVALID, "IYK_HIP_CB_KERNEL names neither wg nor lat");
     char* d[1];
     if (int rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CbJob)}}, d)) return rc;
-    const unsigned grid = (unsigned)std::min<uint64_t>(count, (uint64_t)G.devs[st->gpu].cus);   // wider batches run in rounds
     const bool timed = !st->log_on && st->ev_br0 && st->ev_br1;
     if (timed) HIP_TRY(hipEventRecord(st->ev_br0, st->s));
-    hipLaunchKernelGGL((cb_rotate_kernel<4, 9>), dim3(grid), dim3(CB_LANES), CB_LDS_BYTES, st->s, (const CbJob*)d[0], (int)count,
-                       d_tlwe0, key->n, (const u64*)key->d, (const u64*)key->tw, d_tlwe2);
+    if (plan.form == CB_FORM_LAT)
+        hipLaunchKernelGGL((cb_rotate_lat_kernel<4, 9>), dim3((unsigned)plan.grid), dim3(CBL_LANES), CBL_LDS_BYTES, st->s, (const CbJob*)d[0],
+                           (int)count, d_tlwe0, key->n, (const u64*)key->d, (const u64*)key->tw, d_tlwe2);
+    else
+        hipLaunchKernelGGL((cb_rotate_kernel<4, 9>), dim3((unsigned)plan.grid), dim3(CB_LANES), CB_LDS_BYTES, st->s, (const CbJob*)d[0],
+                           (int)count, d_tlwe0, key->n, (const u64*)key->d, (const u64*)key->tw, d_tlwe2);
     HIP_TRY(hipGetLastError());
     if (timed) {
         HIP_TRY(hipEventRecord(st->ev_br1, st->s));
@@ -2550,6 +2568,19 @@ int iyk_hip_cb_rotate_batch(iyk_hip_stream* st, const void* key_, const uint32_t
     std::vector<CbJob> jobs;
     if (const args::Refusal r = args::check_cb_rotate_batch(tlwe0_slots, tlwe2_slots, count, in, sign, off, mu, out, jobs)) return refuse(r);
     return launch_cb_rotate(st, key, d_tlwe0, d_tlwe2, jobs);
+    IYK_API_END
+}
+
+int iyk_hip_cb_rotate_form(int gpu_index, uint64_t count, int* form_out)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    if (!form_out) return fail(IYK_ERR_INVALID, "null form_out");
+    if (gpu_index < 0 || gpu_index >= (int)G.devs.size()) return fail(IYK_ERR_INVALID, "gpu_index out of range");
+    const CbPlan plan = cb_plan_of_batch(G.devs[gpu_index], count);
+    if (plan.form < 0) return fail(IYK_ERR_INVALID, "IYK_HIP_CB_KERNEL names neither wg nor lat");
+    *form_out = plan.form;
+    return IYK_OK;
     IYK_API_END
 }
 

@@ -42,7 +42,7 @@ EXPORTS = [
     "iyk_hip_tlwe2_alloc", "iyk_hip_tlwe2_free", "iyk_hip_tlwe2_upload", "iyk_hip_tlwe2_download", "iyk_hip_privks_batch",
     "iyk_hip_trgsw_from_rows",
     "iyk_hip_bk2_key_create", "iyk_hip_bk2_key_upload", "iyk_hip_bk2_key_free", "iyk_hip_bk2_key_bytes", "iyk_hip_cb_rotate_batch",
-    "iyk_hip_circuit_bootstrap_batch",
+    "iyk_hip_circuit_bootstrap_batch", "iyk_hip_cb_rotate_form",
 ]
 
 
@@ -113,6 +113,7 @@ def lib():
         L.iyk_hip_bk2_key_free.argtypes = [_vp]
         L.iyk_hip_bk2_key_bytes.argtypes = [ctypes.c_int, ctypes.POINTER(u64)]
         L.iyk_hip_cb_rotate_batch.argtypes = [_vp, _vp, _vp, u64, u64, _i32p, _i32p, _u32p, _u64p, _vp, u64, _i32p]
+        L.iyk_hip_cb_rotate_form.argtypes = [ctypes.c_int, u64, ctypes.POINTER(ctypes.c_int)]
         L.iyk_hip_trgsw_from_rows.argtypes = [_vp, _vp, u64, u64, _i32p, _vp, u64, _i32p]
         L.iyk_hip_circuit_bootstrap_batch.argtypes = [_vp, _vp, _vp, _vp, u64, _i32p, _i32p, _vp, u32, u64, u64, _vp, u64, _vp, u64, u64, u64]
         L.iyk_hip_last_batch_timing.argtypes = [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
@@ -393,6 +394,14 @@ def bk2_key_bytes(gpu=0):
     """Device bytes of the live lvl2 bootstrapping keys of GPU `gpu`."""
     v = ctypes.c_uint64()
     _check(lib().iyk_hip_bk2_key_bytes(int(gpu), ctypes.byref(v)), "iyk_hip_bk2_key_bytes")
+    return v.value
+
+
+def cb_rotate_form(count, gpu_index=0):
+    """The kernel form a Stream.cb_rotate_batch of `count` rotations would run on GPU `gpu_index` now: 0 = cb_rotate_kernel (wide
+    batches), 1 = cb_rotate_lat_kernel (narrow ones).  IYK_HIP_CB_KERNEL = wg / lat forces one; any other value is an IykHipError."""
+    v = ctypes.c_int()
+    _check(lib().iyk_hip_cb_rotate_form(int(gpu_index), int(count), ctypes.byref(v)), "iyk_hip_cb_rotate_form")
     return v.value
 
 
