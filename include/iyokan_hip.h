@@ -518,6 +518,20 @@ const char* iyk_hip_init_profile(void);
  * operand (73.4 MB; both: IYK_HIP_KS_KERNEL above). */
 int iyk_hip_resident_key_bytes(uint64_t* out);
 
+/* The two FORMS of the lvl2 bootstrapping key object (iyk_hip_bk2_key_create above creates form 0).  The form is a property of the
+ * key, because the device layouts differ; nothing is chosen per batch, and every output word is the same under either form.
+ *   form 0  the integer key: the two 32-bit halves' spectra in Z_P (512 KiB per step); iyk_hip_cb_rotate_batch runs cb_rotate_kernel
+ *           or cb_rotate_lat_kernel on it, as IYK_HIP_CB_KERNEL / dispatch::cb_plan say
+ *   form 1  the FP64 key: the spectra of the four signed 16-bit quarters of every word, 1024 complex points each with the 1/1024 of
+ *           the inverse transform folded in (1 MiB per step, 666 MB at n = 636); iyk_hip_cb_rotate_batch and
+ *           iyk_hip_circuit_bootstrap_batch run cb_rotate_fft_kernel on it — exact by the proven rounding margin of DESIGN.md §2b (lvl2
+ *           row).  IYK_HIP_CB_KERNEL = wg / lat changes nothing for such a key; any other value is still IYK_ERR_INVALID before
+ *           anything is staged.  With IYK_HIP_DEBUG=1 the kernel feeds iyk_hip_fft_round_error.
+ * Any other form, (l2, Bgbit2) != (4, 9), or form 1 on a device that did not grant the kernel its 160 KiB of LDS at iyk_hip_init, is
+ * IYK_ERR_INVALID with a text that says which.  _upload, _free and _bytes serve both forms (the same host windows; _bytes counts both). */
+int iyk_hip_bk2_key_create_form(int gpu_index, uint32_t n, uint32_t l2, uint32_t Bgbit2, int form, void** out);
+int iyk_hip_bk2_key_form(const void* key, int* form_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,5 +217,18 @@ constexpr CbPlan cb_plan(long count, int cus, int kind_env)
     return {count <= CB_LAT_MAX_JOBS ? CB_FORM_LAT : CB_FORM_WG, grid};
 }
 
+// ---- the FP64 FFT form of the lvl2 key (cb_rotate_fft.hpp) ----------------------------------------------------------------------
+// The form is a property of the key object (iyk_hip_bk2_key_create_form), not of the batch: a form-1 key has ONE kernel, and cb_plan
+// above decides nothing for it (IYK_HIP_CB_KERNEL is still parsed, and an unknown value refused, before anything is staged).
+enum { BK2_FORM_NTT = 0, BK2_FORM_FFT = 1 };
+constexpr bool bk2_form_known(int form) { return form == BK2_FORM_NTT || form == BK2_FORM_FFT; }
+// Workgroups of a cb_rotate_fft_kernel launch: one per rotation up to one per CU (the kernel takes a CU's whole LDS); a wider batch
+// runs in rounds inside the launch, workgroup b taking jobs b, b + grid, ...  0 where there is nothing to launch.
+constexpr int cb_fft_grid(long count, int cus)
+{
+    if (count <= 0 || cus <= 0) return 0;
+    return (int)(count < (long)cus ? count : (long)cus);
+}
+
 }  // namespace dispatch
 }  // namespace iyk

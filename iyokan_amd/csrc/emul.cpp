@@ -23,6 +23,7 @@
 #include "privks.hpp"
 #include "cb_rotate.hpp"
 #include "cb_rotate_lat.hpp"
+#include "cb_rotate_fft.hpp"
 
 using namespace iyk;
 
@@ -1436,6 +1437,150 @@ int iyk_emul_cb_plan(uint64_t count, int cus, int kind_env, int* form, int* grid
 int iyk_emul_cb_kind(const char* text, int lat_granted) { return dispatch::cb_kind_for_device(dispatch::cb_kind_of(text), lat_granted != 0); }
 /* dispatch::CB_LAT_MAX_JOBS: the widest batch the latency form takes when nothing is forced (0: none) */
 uint64_t iyk_emul_cb_lat_max_jobs(void) { return (uint64_t)dispatch::CB_LAT_MAX_JOBS; }
+}
+
+/* ---- fft1024.hpp / cb_rotate_fft.hpp: the FP64 form of the lvl2 rotation — its transform, its key and one job, lane by lane ---------- */
+namespace {
+struct CbfTables {
+    std::vector<cplx> tab;
+    CbfTables() : tab(fft1k::TAB_POINTS) { fft1k::make_tables(tab.data()); }
+};
+const cplx* cbf_tables()
+{
+    static CbfTables t;
+    return t.tab.data();
+}
+double g_cbf_worst = 0.0;   // largest |z - rint(z)| iyk_emul_cb_rotate_fft has met since the last reset
+
+typedef std::array<cplx, 16> Cbf16;
+inline cplx (&cbf_regs(Cbf16& a))[16] { return reinterpret_cast<cplx(&)[16]>(*a.data()); }
+
+// z (time order, already folded) -> spectrum in position order, through one slot
+void cbf_forward(std::vector<Cbf16>& X, cplx* sp)
+{
+    const cplx* tab = cbf_tables();
+    for (int L = 0; L < 64; ++L) fft1k::fwd1(L, cbf_regs(X[L]), tab, sp);
+    for (int L = 0; L < 64; ++L) fft1k::fwd2_read(L, tab, sp, cbf_regs(X[L]));
+    for (int L = 0; L < 64; ++L) fft1k::fwd2_write(L, cbf_regs(X[L]), sp);
+    for (int L = 0; L < 64; ++L) fft1k::fwd3_read(L, sp, cbf_regs(X[L]));
+}
+// spectrum in position order in sp -> the slot ready for fft1k::inv1
+void cbf_inverse_to_last_pass(std::vector<Cbf16>& X, cplx* sp)
+{
+    const cplx* tab = cbf_tables();
+    for (int L = 0; L < 64; ++L) fft1k::inv3_read(L, sp, cbf_regs(X[L]));
+    for (int L = 0; L < 64; ++L) fft1k::inv3_write(L, cbf_regs(X[L]), sp);
+    for (int L = 0; L < 64; ++L) fft1k::inv2_read(L, tab, sp, cbf_regs(X[L]));
+    for (int L = 0; L < 64; ++L) fft1k::inv2_write(L, cbf_regs(X[L]), sp);
+}
+
+// lane-by-lane run of cb_rotate_fft_kernel for one job: the same phase functions in the same order, one loop over the lanes wherever
+// the kernel has a workgroup barrier or a wave-level ordering point
+template <int L2, int BGBIT2>
+void cb_rotate_fft(u32 n, const u32* w, const CbJob& jb, const cplx* bk, u64* out)
+{
+    const cplx* tab = cbf_tables();
+    std::vector<u64> acc(2 * CB_N);
+    std::vector<cplx> buf((size_t)CB_ROWS * CBF_SLOT);
+    struct Lane {
+        cplx x[16], accum[16];
+    };
+    std::vector<Lane> R(CBF_LANES);
+#define CBF_LANES_ALL for (int lane = 0; lane < CBF_LANES; ++lane)
+    CBF_LANES_ALL cbl_prologue(lane, jb, w, n, acc.data());
+    for (u32 i = 0; i < n; ++i) {
+        const u32 ab = cbl_abar(jb, w, n, i);
+        const cplx* bk_step = bk + (size_t)i * CBF_STEP_POINTS;
+        CBF_LANES_ALL cbf_digits<L2, BGBIT2>(lane, ab, acc.data(), R[lane].x);
+        CBF_LANES_ALL fft1k::fwd1(lane & 63, R[lane].x, tab, cbf_slot(buf.data(), lane));
+        CBF_LANES_ALL fft1k::fwd2_read(lane & 63, tab, cbf_slot(buf.data(), lane), R[lane].x);
+        CBF_LANES_ALL fft1k::fwd2_write(lane & 63, R[lane].x, cbf_slot(buf.data(), lane));
+        CBF_LANES_ALL fft1k::fwd3_read(lane & 63, cbf_slot(buf.data(), lane), R[lane].x);
+        CBF_LANES_ALL fft1k::spec_write(lane & 63, R[lane].x, cbf_slot(buf.data(), lane));
+        CBF_LANES_ALL cbf_mac(lane, buf.data(), bk_step, R[lane].accum);
+        CBF_LANES_ALL cbf_inv_write(lane, R[lane].accum, buf.data());
+        CBF_LANES_ALL fft1k::inv3_read(lane & 63, cbf_slot(buf.data(), lane), R[lane].x);
+        CBF_LANES_ALL fft1k::inv3_write(lane & 63, R[lane].x, cbf_slot(buf.data(), lane));
+        CBF_LANES_ALL fft1k::inv2_read(lane & 63, tab, cbf_slot(buf.data(), lane), R[lane].x);
+        CBF_LANES_ALL fft1k::inv2_write(lane & 63, R[lane].x, cbf_slot(buf.data(), lane));
+        CBF_LANES_ALL g_cbf_worst = std::max(g_cbf_worst, cbf_inv_add<true>(lane, tab, buf.data(), acc.data()));
+    }
+    for (int j = 0; j <= CB_N; ++j) out[j] = cb_extract_word(acc.data(), j, jb.mu);
+#undef CBF_LANES_ALL
+}
+}  // namespace
+
+extern "C" {
+/* the 1024-point transform of fft1024.hpp alone, in: double [1024][2], out: double [1024][2].  inverse == 0: z in time order ->
+ * A[k] = sum_j z[j] psi^j W^(jk) in NATURAL frequency order (the position order undone through fft1k::freq_of_pos); inverse != 0:
+ * C in natural frequency order -> psi^-j sum_k C[k] W^(-jk) in time order, unscaled (1024 times the inverse) */
+void iyk_emul_fft1024(const double* in, int inverse, double* out)
+{
+    std::vector<cplx> sp(fft1k::M);
+    std::vector<Cbf16> X(64);
+    if (!inverse) {
+        for (int L = 0; L < 64; ++L)
+            for (int j2 = 0; j2 < 16; ++j2) X[L][j2] = {in[2 * (L + 64 * j2)], in[2 * (L + 64 * j2) + 1]};
+        cbf_forward(X, sp.data());
+        for (int L = 0; L < 64; ++L)
+            for (int r = 0; r < 16; ++r) {
+                const int k = fft1k::freq_of_pos(L + 64 * r);
+                out[2 * k] = X[L][r].re, out[2 * k + 1] = X[L][r].im;
+            }
+        return;
+    }
+    for (int pos = 0; pos < fft1k::M; ++pos) sp[pos] = {in[2 * fft1k::freq_of_pos(pos)], in[2 * fft1k::freq_of_pos(pos) + 1]};
+    cbf_inverse_to_last_pass(X, sp.data());
+    for (int L = 0; L < 64; ++L) {
+        fft1k::inv1(L, cbf_tables(), sp.data(), cbf_regs(X[L]));
+        for (int j2 = 0; j2 < 16; ++j2) out[2 * (L + 64 * j2)] = X[L][j2].re, out[2 * (L + 64 * j2) + 1] = X[L][j2].im;
+    }
+}
+/* the signed 16-bit quarters of `count` key words: q[count][4] */
+void iyk_emul_cb_key_quarters(const uint64_t* w, int count, int32_t* q)
+{
+    for (int g = 0; g < count; ++g)
+        for (int j = 0; j < 4; ++j) q[4 * g + j] = fft1k::key_quarter(w[g], j);
+}
+/* R_0 + (R_1 << 16) + (R_2 << 32) + (R_3 << 48) of `count` quadruples of doubles, each rounded as the kernel rounds */
+void iyk_emul_cb_recombine(const double* z, int count, uint64_t* out)
+{
+    for (int g = 0; g < count; ++g) {
+        const int64_t R[4] = {fft1k::round_i64(z[4 * g]), fft1k::round_i64(z[4 * g + 1]), fft1k::round_i64(z[4 * g + 2]), fft1k::round_i64(z[4 * g + 3])};
+        out[g] = fft1k::recombine(R);
+    }
+}
+/* bk2_fft_kernel on the CPU: torus u64 [steps][8][2][N2] -> double [steps][4 quarters][8][2][1024][2] */
+void iyk_emul_bk2_fft(uint64_t steps, const uint64_t* torus, double* dst_)
+{
+    cplx* dst = reinterpret_cast<cplx*>(dst_);
+    std::vector<cplx> sp(fft1k::M);
+    std::vector<Cbf16> X(64);
+    for (uint64_t poly = 0; poly < steps * CB_ROWS * 2; ++poly)
+        for (int q = 0; q < CBF_QUARTERS; ++q) {
+            for (int L = 0; L < 64; ++L) cbf_key_fold(L, q, torus + poly * CB_N, cbf_regs(X[L]));
+            cbf_forward(X, sp.data());
+            for (int L = 0; L < 64; ++L) cbf_key_write(L, cbf_regs(X[L]), dst + cbf_key_offset(poly / (CB_ROWS * 2), q, (int)(poly % (CB_ROWS * 2))));
+        }
+}
+/* one job of cb_rotate_fft_kernel: the arguments of iyk_emul_cb_rotate with the key of iyk_emul_bk2_fft */
+int iyk_emul_cb_rotate_fft(uint32_t n, uint32_t l2, uint32_t Bgbit2, const uint32_t* w, int32_t sign, uint32_t off, uint64_t mu,
+                           const double* bk_fft, uint64_t* out)
+{
+    if (l2 != 4 || Bgbit2 != 9 || n == 0 || n > CB_MAX_N0 || (sign != 1 && sign != -1)) return -1;
+    cb_rotate_fft<4, 9>(n, w, CbJob{0, sign, off, 0, mu}, reinterpret_cast<const cplx*>(bk_fft), out);
+    return 0;
+}
+/* largest |z - rint(z)| over every rounded sum of iyk_emul_cb_rotate_fft since the last reset */
+double iyk_emul_cb_fft_round_error(int reset)
+{
+    const double w = g_cbf_worst;
+    if (reset) g_cbf_worst = 0.0;
+    return w;
+}
+/* dispatch::cb_fft_grid, dispatch::bk2_form_known */
+int iyk_emul_cb_fft_grid(int64_t count, int cus) { return dispatch::cb_fft_grid((long)count, cus); }
+int iyk_emul_bk2_form_known(int form) { return dispatch::bk2_form_known(form) ? 1 : 0; }
 }
 
 /* ---- batch_args.hpp: the argument checks and job lists of the batch entry points ------------------------------------------------

@@ -48,6 +48,7 @@
 #include "keyswitch_mfma.hpp"
 #include "cb_rotate.hpp"
 #include "cb_rotate_lat.hpp"
+#include "cb_rotate_fft.hpp"
 
 using namespace iyk;
 using namespace iyk::dispatch;
@@ -110,6 +111,7 @@ struct Device {
     uint64_t privks_bytes = 0;     // device memory of the live private key-switch keys of this GPU (iyk_hip_privks_key_*): __atomic adds
     uint64_t bk2_bytes = 0;        // device memory of the live lvl2 bootstrapping keys of this GPU (iyk_hip_bk2_key_*): __atomic adds
     bool cb_lat_granted = false;   // cb_rotate_lat_kernel's dynamic LDS was granted at init (set_kernel_attrs); else every batch runs cb_rotate_kernel
+    bool cb_fft_granted = false;   // cb_rotate_fft_kernel's was: else no lvl2 key of the FP64 form is created (iyk_hip_bk2_key_create_form)
     int max_passes = 0;            // cost.max_passes as the dispatch reads it: __atomic loads / stores, lock-free (a calibration may run
                                    // beside a batch; a plain int keeps Device copyable)
     void release()
@@ -653,13 +655,20 @@ int set_fft_attrs()
     if ((rc = set_lds(cmux_chain_kernel<GD, false>, BR_FFT_LDS_BYTES))) return rc;
     return set_lds(cmux_chain_kernel<GD, true>, BR_FFT_LDS_BYTES);
 }
-int set_kernel_attrs(const iyk_params& p, bool use_fp, int split, bool* cb_lat_granted)
+int set_kernel_attrs(const iyk_params& p, bool use_fp, int split, bool* cb_lat_granted, bool* cb_fft_granted)
 {
     // the latency form of the lvl2 rotation asks for the whole LDS of a CU: a device that does not grant it runs cb_rotate_kernel
     // (dispatch::cb_kind_for_device), initialisation does not fail
     *cb_lat_granted = hipFuncSetAttribute(reinterpret_cast<const void*>(cb_rotate_lat_kernel<4, 9>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)CBL_LDS_BYTES) == hipSuccess;
     if (!*cb_lat_granted) (void)hipGetLastError();   // not sticky: leave no pending error behind
+    // the FP64 form of the lvl2 rotation asks for the same: a device that does not grant it creates no key of that form
+    *cb_fft_granted = true;
+    for (const void* f : {reinterpret_cast<const void*>(cb_rotate_fft_kernel<4, 9, false>), reinterpret_cast<const void*>(cb_rotate_fft_kernel<4, 9, true>)})
+        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CBF_LDS_BYTES) != hipSuccess) {
+            (void)hipGetLastError();
+            *cb_fft_granted = false;
+        }
     int rc = with_rot_set(p, split, [&](auto dc, auto gd) {
         typedef decltype(dc) DC;
         if (!use_fp) return set_lds(blind_rotate_kernel<DC::L, DC::BGBIT>, BR_LDS_BYTES);
@@ -788,7 +797,7 @@ int init_devices(std::vector<Device>& devs, const int* device_ids, int avail, co
             cleanup();
             return fail(IYK_ERR_HIP, "device reports no compute units");
         }
-        int rc = set_kernel_attrs(p, use_fp, split, &D.cb_lat_granted);
+        int rc = set_kernel_attrs(p, use_fp, split, &D.cb_lat_granted, &D.cb_fft_granted);
         if (rc) {
             cleanup();
             return rc;
@@ -2427,6 +2436,12 @@ struct Bk2Key {
     uint64_t generation = 0;  // G.generation at create
     u64* d = nullptr;         // u64 [n][2 halves][(k+1) l2][k+1][N2], NTT domain; then the transform's tables (twf, twi: 2 x N2 words)
     u64* tw = nullptr;        // d + n * CB_STEP_WORDS
+    // form BK2_FORM_FFT (cb_rotate_fft.hpp): d holds cplx [n][4 quarters][(k+1) l2][k+1][1024] instead, then fft1k's tables
+    int form = BK2_FORM_NTT;
+    const fft::cplx* spectra() const { return reinterpret_cast<const fft::cplx*>(d); }
+    fft::cplx* spectra() { return reinterpret_cast<fft::cplx*>(d); }
+    fft::cplx* tab() { return spectra() + (size_t)n * CBF_STEP_POINTS; }
+    const fft::cplx* tab() const { return spectra() + (size_t)n * CBF_STEP_POINTS; }
     std::atomic<bool> tables_sent{false};   // the first upload sends the tables, on its stream, ahead of its window
 };
 constexpr uint64_t BK2_UPLOAD_CHUNK = 8;   // key steps per staging slot (2 MiB of torus words)
@@ -2435,14 +2450,23 @@ constexpr uint64_t BK2_UPLOAD_CHUNK = 8;   // key steps per staging slot (2 MiB 
 
 int iyk_hip_bk2_key_create(int gpu_index, uint32_t n, uint32_t l2, uint32_t Bgbit2, void** out)
 {
+    return iyk_hip_bk2_key_create_form(gpu_index, n, l2, Bgbit2, BK2_FORM_NTT, out);
+}
+
+int iyk_hip_bk2_key_create_form(int gpu_index, uint32_t n, uint32_t l2, uint32_t Bgbit2, int form, void** out)
+{
     IYK_API_BEGIN
     if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
     if (!out) return fail(IYK_ERR_INVALID, "null out");
+    if (!bk2_form_known(form)) return fail(IYK_ERR_INVALID, "form names neither the integer key (0) nor the FP64 key (1)");
     if (n == 0 || n > CB_MAX_N0) return fail(IYK_ERR_INVALID, "n outside [1, 2047]");
     if (l2 != 4 || Bgbit2 != 9) return fail(IYK_ERR_INVALID, "the lvl2 rotation is built for l2 = 4, Bgbit2 = 9");
     int rc = set_device(gpu_index);
     if (rc) return rc;
-    const uint64_t bytes = ((uint64_t)n * CB_STEP_WORDS + 2 * CB_N) * sizeof(u64);
+    if (form == BK2_FORM_FFT && !G.devs[gpu_index].cb_fft_granted)
+        return fail(IYK_ERR_INVALID, "the device did not grant cb_rotate_fft_kernel its LDS (160 KiB per workgroup): no lvl2 key of the FP64 form");
+    const uint64_t bytes = form == BK2_FORM_FFT ? ((uint64_t)n * CBF_STEP_POINTS + fft1k::TAB_POINTS) * sizeof(fft::cplx)
+                                                : ((uint64_t)n * CB_STEP_WORDS + 2 * CB_N) * sizeof(u64);
     u64* d = nullptr;
     hipError_t e = hipMalloc((void**)&d, bytes);
     if (e != hipSuccess) {
@@ -2454,12 +2478,20 @@ int iyk_hip_bk2_key_create(int gpu_index, uint32_t n, uint32_t l2, uint32_t Bgbi
         (void)hipFree(d);
         return fail(IYK_ERR_NOMEM, "out of host memory");
     }
-    key->gpu = gpu_index, key->n = n, key->l2 = l2, key->Bgbit2 = Bgbit2;
-    key->bytes = bytes, key->generation = G.generation, key->d = d, key->tw = d + (size_t)n * CB_STEP_WORDS;
+    key->gpu = gpu_index, key->n = n, key->l2 = l2, key->Bgbit2 = Bgbit2, key->form = form;
+    key->bytes = bytes, key->generation = G.generation, key->d = d, key->tw = form == BK2_FORM_FFT ? nullptr : d + (size_t)n * CB_STEP_WORDS;
     __atomic_fetch_add(&G.devs[gpu_index].bk2_bytes, bytes, __ATOMIC_RELAXED);
     *out = key;
     return IYK_OK;
     IYK_API_END
+}
+
+int iyk_hip_bk2_key_form(const void* key_, int* form_out)
+{
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    if (!key_ || !form_out) return fail(IYK_ERR_INVALID, "null argument");
+    *form_out = ((const Bk2Key*)key_)->form;
+    return IYK_OK;
 }
 
 int iyk_hip_bk2_key_free(void* key_)
@@ -2496,12 +2528,14 @@ int iyk_hip_bk2_key_upload(iyk_hip_stream* st, void* key_, uint64_t first_step, 
     if (first_step > key->n || step_count > key->n - first_step) return fail(IYK_ERR_INVALID, "step range outside the key");
     int rc = set_device(st->gpu);
     if (rc) return rc;
+    const bool fft_form = key->form == BK2_FORM_FFT;
     if (!key->tables_sent.exchange(true)) {   // once per key, by its first upload (create only allocates)
-        const size_t bytes = 2 * CB_N * sizeof(u64);
+        const size_t bytes = fft_form ? fft1k::TAB_POINTS * sizeof(fft::cplx) : 2 * CB_N * sizeof(u64);
         size_t soff = 0;
         if ((rc = acquire_stage(st, bytes, &soff))) return rc;
-        cb_make_tables((u64*)(st->h_stage + soff), (u64*)(st->h_stage + soff) + CB_N);
-        HIP_TRY(hipMemcpyAsync(key->tw, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+        if (fft_form) fft1k::make_tables((fft::cplx*)(st->h_stage + soff));
+        else cb_make_tables((u64*)(st->h_stage + soff), (u64*)(st->h_stage + soff) + CB_N);
+        HIP_TRY(hipMemcpyAsync(fft_form ? (void*)key->tab() : (void*)key->tw, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
         if ((rc = release_stage(st))) return rc;
     }
     for (uint64_t done = 0; done < step_count; done += BK2_UPLOAD_CHUNK) {
@@ -2511,8 +2545,12 @@ int iyk_hip_bk2_key_upload(iyk_hip_stream* st, void* key_, uint64_t first_step, 
         if ((rc = acquire_stage(st, bytes, &soff))) return rc;
         std::memcpy(st->h_stage + soff, host_trgsw + (size_t)done * CB_TORUS_STEP_WORDS, bytes);   // the caller's window is free on return
         HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
-        hipLaunchKernelGGL(bk2_ntt_kernel, dim3((unsigned)(c * CB_ROWS * 2 * 2)), dim3(64), 0, st->s, (const u64*)(st->d_stage + soff),
-                           key->d + (size_t)(first_step + done) * CB_STEP_WORDS, (const u64*)key->tw);
+        if (fft_form)   // one workgroup per (polynomial, quarter); the kernel places its spectrum from the step it is given
+            hipLaunchKernelGGL(bk2_fft_kernel, dim3((unsigned)(c * CB_ROWS * 2 * CBF_QUARTERS)), dim3(64), 0, st->s, (const u64*)(st->d_stage + soff),
+                               key->spectra() + (size_t)(first_step + done) * CBF_STEP_POINTS, key->tab());
+        else
+            hipLaunchKernelGGL(bk2_ntt_kernel, dim3((unsigned)(c * CB_ROWS * 2 * 2)), dim3(64), 0, st->s, (const u64*)(st->d_stage + soff),
+                               key->d + (size_t)(first_step + done) * CB_STEP_WORDS, (const u64*)key->tw);
         HIP_TRY(hipGetLastError());
         if ((rc = release_stage(st))) return rc;
     }
@@ -2538,7 +2576,13 @@ int launch_cb_rotate(iyk_hip_stream* st, const Bk2Key* key, const uint32_t* d_tl
     if (int rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CbJob)}}, d)) return rc;
     const bool timed = !st->log_on && st->ev_br0 && st->ev_br1;
     if (timed) HIP_TRY(hipEventRecord(st->ev_br0, st->s));
-    if (plan.form == CB_FORM_LAT)
+    if (key->form == BK2_FORM_FFT) {   // the key's form, not the batch's plan: wg / lat name kernels of the integer key
+        const Device& D = G.devs[st->gpu];
+        auto kern = G.debug ? cb_rotate_fft_kernel<4, 9, true> : cb_rotate_fft_kernel<4, 9, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)cb_fft_grid((long)count, D.cus)), dim3(CBF_LANES), CBF_LDS_BYTES, st->s, (const CbJob*)d[0], (int)count,
+                           d_tlwe0, key->n, key->spectra(), key->tab(), d_tlwe2, D.fft_err);
+    }
+    else if (plan.form == CB_FORM_LAT)
         hipLaunchKernelGGL((cb_rotate_lat_kernel<4, 9>), dim3((unsigned)plan.grid), dim3(CBL_LANES), CBL_LDS_BYTES, st->s, (const CbJob*)d[0],
                            (int)count, d_tlwe0, key->n, (const u64*)key->d, (const u64*)key->tw, d_tlwe2);
     else

@@ -42,7 +42,7 @@ EXPORTS = [
     "iyk_hip_tlwe2_alloc", "iyk_hip_tlwe2_free", "iyk_hip_tlwe2_upload", "iyk_hip_tlwe2_download", "iyk_hip_privks_batch",
     "iyk_hip_trgsw_from_rows",
     "iyk_hip_bk2_key_create", "iyk_hip_bk2_key_upload", "iyk_hip_bk2_key_free", "iyk_hip_bk2_key_bytes", "iyk_hip_cb_rotate_batch",
-    "iyk_hip_circuit_bootstrap_batch", "iyk_hip_cb_rotate_form",
+    "iyk_hip_circuit_bootstrap_batch", "iyk_hip_cb_rotate_form", "iyk_hip_bk2_key_create_form", "iyk_hip_bk2_key_form",
 ]
 
 
@@ -109,6 +109,8 @@ def lib():
         L.iyk_hip_tlwe2_download.argtypes = [_vp, _vp, u32, u64, u64, u64, _u64p]
         L.iyk_hip_privks_batch.argtypes = [_vp, _vp, _vp, u64, u64, _i32p, _i32p, _vp, u64, _i32p]
         L.iyk_hip_bk2_key_create.argtypes = [ctypes.c_int, u32, u32, u32, ctypes.POINTER(_vp)]
+        L.iyk_hip_bk2_key_create_form.argtypes = [ctypes.c_int, u32, u32, u32, ctypes.c_int, ctypes.POINTER(_vp)]
+        L.iyk_hip_bk2_key_form.argtypes = [_vp, ctypes.POINTER(ctypes.c_int)]
         L.iyk_hip_bk2_key_upload.argtypes = [_vp, _vp, u64, u64, _u64p]
         L.iyk_hip_bk2_key_free.argtypes = [_vp]
         L.iyk_hip_bk2_key_bytes.argtypes = [ctypes.c_int, ctypes.POINTER(u64)]
@@ -368,15 +370,27 @@ def privks_key_bytes(gpu=0):
 
 class Bk2Key:
     """Device-resident lvl2 bootstrapping key of one GPU (the lvl0 -> lvl2 rotation of circuit bootstrapping, Stream.cb_rotate_batch):
-    the torus-domain rows u64 [n][(k+1) l2][k+1][N2] of client.bk2_rows, uploaded in windows of steps and transformed on the stream."""
+    the torus-domain rows u64 [n][(k+1) l2][k+1][N2] of client.bk2_rows, uploaded in windows of steps and transformed on the stream.
+    form: "ntt" (the default) is the integer key (Z_P, 512 KiB per step), "fft" the FP64 key (the spectra of the signed 16-bit quarters,
+    1 MiB per step, rotated by cb_rotate_fft_kernel); the output words are the same.  Everything that takes a Bk2Key takes either."""
     N2 = 2048
+    FORMS = {"ntt": 0, "fft": 1}
 
-    def __init__(self, n, l2=4, Bgbit2=9, gpu_index=0):
+    def __init__(self, n, l2=4, Bgbit2=9, gpu_index=0, form="ntt"):
         self.n, self.l2, self.Bgbit2, self.gpu_index = int(n), int(l2), int(Bgbit2), gpu_index
         self.step_words = 2 * self.l2 * 2 * self.N2
         h = _vp()
-        _check(lib().iyk_hip_bk2_key_create(gpu_index, self.n, self.l2, self.Bgbit2, ctypes.byref(h)), "iyk_hip_bk2_key_create")
+        if form not in self.FORMS:
+            raise ValueError(f"Bk2Key form {form!r}: expected one of {sorted(self.FORMS)}")
+        if form == "ntt":
+            _check(lib().iyk_hip_bk2_key_create(gpu_index, self.n, self.l2, self.Bgbit2, ctypes.byref(h)), "iyk_hip_bk2_key_create")
+        else:
+            _check(lib().iyk_hip_bk2_key_create_form(gpu_index, self.n, self.l2, self.Bgbit2, self.FORMS[form], ctypes.byref(h)),
+                   "iyk_hip_bk2_key_create_form")
         self.h = h
+        v = ctypes.c_int()
+        _check(lib().iyk_hip_bk2_key_form(self.h, ctypes.byref(v)), "iyk_hip_bk2_key_form")
+        self.form = {c: name for name, c in self.FORMS.items()}[v.value]
 
     def upload(self, stream, first_step, host_steps):
         """Steps first_step .. of the host layout; copied before return, transformed on the stream."""

@@ -107,12 +107,14 @@ def clocks(eng, be, sysm, n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clocks", type=int, default=3)
+    ap.add_argument("--bk2-form", choices=sorted(hip.Bk2Key.FORMS), default="ntt",
+                    help="the lvl2 bootstrapping key's form: ntt = the integer key, fft = the FP64 key (cb_rotate_fft_kernel)")
     args = ap.parse_args()
     keys = client.keygen(params_128bit(), seed=1)
     hip.initialize(keys, device_ids=(0,))
     st = hip.Stream(0)
     rng = np.random.default_rng(2)
-    bk2 = hip.Bk2Key(keys.params.n)
+    bk2 = hip.Bk2Key(keys.params.n, form=args.bk2_form)
     for first in range(0, bk2.n, 100):
         count = min(100, bk2.n - first)
         bk2.upload(st, first, rng.integers(0, 1 << 63, size=(count, bk2.step_words), dtype=np.uint64))
@@ -121,7 +123,7 @@ def main():
     for first in range(0, pk.rows, 8192):
         pk.upload(st, first, window[:min(8192, pk.rows - first)])
     st.sync()
-    print(f"build {hip.build_id()}; {args.clocks} clocks per figure; 128-bit set; bk2 n = {bk2.n}, private key n_in = 2048, t = 10, basebit = 3")
+    print(f"build {hip.build_id()}; {args.clocks} clocks per figure; 128-bit set; bk2 n = {bk2.n} form {bk2.form}, private key n_in = 2048, t = 10, basebit = 3")
     tmp = tempfile.mkdtemp()
     systems = [("small: ROM 3-bit address x 4 bits, RAM 2-bit address x 2 bits, 12 gates", cases.write_blueprint(tmp)),
                ("ram-addr8bit: RAM 8-bit address x 8 bits", os.path.join(ROOT, "tests", "golden", "reftest", "config-toml", "ram-addr8bit.toml"))]
