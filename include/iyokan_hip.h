@@ -306,6 +306,23 @@ int iyk_hip_cmux_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_s
 int iyk_hip_cmux_chain_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe,
                              uint64_t trlwe_slots, uint64_t count, const int32_t* sel0, const int32_t* steps,
                              const uint32_t* pattern, const int32_t* src, const int32_t* mem, const int32_t* out);
+/* `count` independent chains of ROTATE-form CMUXes, asynchronous on st: the lower half (LROMUX) of one ROM read per job.  Job g, with
+ * (sel_j, rot_j) the entries first[g] + j of sel / rot, first[g] = steps[0] + .. + steps[g - 1] and j over 0 .. steps[g] - 1:
+ *     acc = T[src]
+ *     acc = acc + S[sel_j] [.] ((X^rot_j - 1) acc)                          the cmux job (sel_j, in0 = acc, in1 < 0, rot_j, out = acc)
+ *     T[out] = acc
+ * Replaces the loop of TaskTFHEppROMUX over the low address bits (/root/reference/src/iyokan_tfhepp.hpp:282-291: PolynomialMulByXaiMinusOne
+ * of the accumulator by 2N - (N >> bit), trgswfftExternalProduct with that bit's selector, added to the accumulator): sel_j = the
+ * selector of address bit log2(words per TRLWE) - bit, rot_j = 2N - (N >> bit), src = the row the upper tree left, out = the result
+ * row.  One kernel, the accumulator in LDS for all steps, nothing read from the TRLWE store between them; word for word what
+ * steps[g] successive iyk_hip_cmux_batch rotate jobs give (the product is exact).  sel and rot have sum(steps) entries, the jobs' steps
+ * one after the other; the five arrays are host arrays, copied before return.  Checked on every call, in O(count + sum(steps)): 1 <=
+ * steps <= 32, every sel in [0, trgsw_slots), every rot in [0, 2N), every row < trlwe_slots, and no out[g] is the src / out of ANOTHER
+ * job — a job may write over its own src, and jobs may share src.  A violation is IYK_ERR_INVALID and nothing is staged or launched;
+ * IYK_ERR_STATE off the FFT path.  With IYK_HIP_DEBUG=1 the kernel feeds iyk_hip_fft_round_error. */
+int iyk_hip_cmux_rotate_chain_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe,
+                                    uint64_t trlwe_slots, uint64_t count, const int32_t* steps, const int32_t* sel,
+                                    const int32_t* rot, const int32_t* src, const int32_t* out);
 /* T[out] = T[a] + T[b] mod 2^32 per job, with b0_offset added to coefficient 0 of the b polynomial; asynchronous on st, host
  * arrays copied before return.  The tail of TFHEpp::HomMUXwoSE<Lvl01> (TaskTFHEppGateMUXWoSE, /root/reference/src/iyokan_tfhepp.hpp:
  * 500-508): with a, b the rows of the two blind rotations iyk_hip_bootstrap_trlwe_batch(cs + c1 - mu) and (-cs + c0 - mu) and

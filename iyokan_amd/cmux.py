@@ -1,4 +1,5 @@
-"""CMUX memories on the GPU: the read tree of a ROM over TRLWE rows (Stream.cmux_batch + index extraction), and a RAM — read tree,
+"""CMUX memories on the GPU: the read tree of a ROM over TRLWE rows (Stream.cmux_batch + index extraction; the rotate tail optionally as
+one fused Stream.cmux_rotate_chain_batch), and a RAM — read tree,
 MUXwoSE, one fused chain of CMUXes per cell (Stream.cmux_chain_batch) and the refresh of every cell.
 
 Replaces the reference's TaskTFHEppROMUX (UROMUX + LROMUX, /root/reference/src/iyokan_tfhepp.hpp:238-300) followed by one
@@ -58,6 +59,28 @@ def rom_read_plan(addr_width, log2_word_bits, N):
         launches.append([PlanJob(W - bit, cur, -1, 2 * N - (N >> bit), lay.result)])
         cur = lay.result
     return launches   # empty for a one-word ROM: nothing to select
+
+
+# The rotate tail of a read plan as ONE job of Stream.cmux_rotate_chain_batch: acc = row src; step j is the rotate-form CMUX selected by
+# address bit bits[j] with rotation rots[j]; row out = acc.
+RotateChain = namedtuple("RotateChain", "steps bits rots src out")
+
+
+def rom_rotate_chain(plan):
+    """The trailing rotate-form launches of a rom_read_plan (LROMUX: one job each, every one but the first in place on the result row)
+    as one RotateChain; the len(plan) - steps launches in front of them are the upper tree.  None where the plan has no rotate step:
+    every word fills a whole TRLWE."""
+    tail = []
+    for jobs in reversed(plan):
+        if len(jobs) != 1 or jobs[0].in1 >= 0:
+            break
+        tail.append(jobs[0])
+    if not tail:
+        return None
+    tail.reverse()
+    out = tail[-1].out
+    assert all(j.out == out for j in tail) and all(j.in0 == out for j in tail[1:])
+    return RotateChain(len(tail), tuple(j.bit for j in tail), tuple(j.rot for j in tail), tail[0].in0, out)
 
 
 def selectors_from_tlwe2(stream, key, tlwe2, first, addr_width, trlwe_scratch, trgsw, first_slot=0):
@@ -149,10 +172,26 @@ class Rom:
             out.append(tuple(cols))
         return out
 
-    def read(self, addr_trgsw, arena, out_slots, resident=False):
+    def launches_fused(self, reads):
+        """(the cmux_batch argument lists of the upper tree, exactly the first ones of launches(reads); ONE cmux_rotate_chain_batch
+        argument tuple (steps, sel, rot, src, out) with one job per read for the rotate tail, None where the plan has none)."""
+        chain = rom_rotate_chain(self.plan)
+        if chain is None:
+            return self.launches(reads), None
+        steps, sel, rot, src, out = [], [], [], [], []
+        for r in range(reads):
+            steps.append(chain.steps)
+            sel.extend(r * self.addr_width + b for b in chain.bits)
+            rot.extend(chain.rots)
+            src.append(self.row(r, chain.src))
+            out.append(self.row(r, chain.out))
+        return self.launches(reads)[: len(self.plan) - chain.steps], (steps, sel, rot, src, out)
+
+    def read(self, addr_trgsw, arena, out_slots, resident=False, fused=False):
         """addr_trgsw: u32 [R][addr_width][(k+1) l][k+1][N] (client.encrypt_trgsw of every read's address bits, bit 0 first);
         out_slots: [R][word_bits] arena slots.  Asynchronous on the stream.  resident=True: the selectors are in self.trgsw already
-        (slot read * addr_width + bit, e.g. from selectors_from_tlwe2 on this stream): addr_trgsw is ignored and nothing is uploaded."""
+        (slot read * addr_width + bit, e.g. from selectors_from_tlwe2 on this stream): addr_trgsw is ignored and nothing is uploaded.
+        fused=True sends the rotate tail of all reads as ONE cmux_rotate_chain_batch instead of one cmux_batch per step: the same words."""
         if resident:
             out_slots = np.asarray(out_slots, dtype=np.int32).reshape(-1, self.word_bits)
             reads = out_slots.shape[0]
@@ -164,8 +203,11 @@ class Rom:
             raise ValueError(f"{reads} reads, sized for {self.max_reads}")
         if not resident:
             self.trgsw.upload(self.stream, 0, sel)
-        for args in self.launches(reads):
+        upper, chain = self.launches_fused(reads) if fused else (self.launches(reads), None)
+        for args in upper:
             self.stream.cmux_batch(self.trgsw, self.trlwe, *args)
+        if chain is not None:
+            self.stream.cmux_rotate_chain_batch(self.trgsw, self.trlwe, *chain)
         rows = np.repeat([self.row(r, self.layout.result) for r in range(reads)], self.word_bits)
         coeff = np.tile(np.arange(self.word_bits), reads)
         self.stream.sample_extract_index_keyswitch_batch(self.trlwe, rows, coeff, out_slots.ravel(), arena)

@@ -221,6 +221,38 @@ inline Refusal check_cmux_chain_batch(uint64_t trgsw_slots, uint64_t trlwe_slots
     return ACCEPT;
 }
 
+// iyk_hip_cmux_rotate_chain_batch, O(count + sum of steps).  sel and rot hold the jobs' steps one after the other: job g's are entries
+// first[g] .. first[g] + steps[g] - 1, first[g] the sum of the steps before it — so steps[g] is checked before any of its entries is
+// read, and nothing is read behind the entries the accepted jobs before it account for.
+// Not named check_*: the check_* functions are the ones whose answers tests/golden/batch_refusals_parent.json records from a library
+// that had them (tests/test_batch_args.py lists them by that name); this entry point is newer than the record, and its refusals and
+// job words have tests/test_rom_chain_args.py, which also holds every text below against a set that reaches it.
+inline Refusal cmux_rotate_chain_args(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* steps, const int32_t* sel,
+                                      const int32_t* rot, const int32_t* src, const int32_t* out, std::vector<CmuxRotChainJob>& jobs,
+                                      std::vector<CmuxRotStep>& list)
+{
+    if (count > MAX_ROW_BATCH) return invalid("batch too large");
+    if (trgsw_slots > MAX_TRGSW_SLOTS || trlwe_slots > MAX_STORE_ROWS) return invalid("store larger than an allocation can be");
+    jobs.resize(count);
+    list.clear();
+    list.reserve(count);
+    for (uint64_t g = 0; g < count; ++g) {
+        if (steps[g] < 1 || steps[g] > CMUX_ROT_CHAIN_MAX_STEPS) return invalid("steps outside [1, 32]");
+        const size_t first = list.size();   // <= 2^24 * 32: an int32_t
+        for (int32_t j = 0; j < steps[g]; ++j) {
+            if (!slot_ok(sel[first + j], trgsw_slots)) return invalid("selector index outside the selector store");
+            if (rot[first + j] < 0 || rot[first + j] >= 2 * RING_N) return invalid("rot outside [0, 2N)");
+            list.push_back(CmuxRotStep{sel[first + j], rot[first + j]});
+        }
+        if (!slot_ok(src[g], trlwe_slots) || !slot_ok(out[g], trlwe_slots)) return invalid("TRLWE index outside the buffer");
+        jobs[g] = CmuxRotChainJob{(int32_t)first, steps[g], src[g], out[g]};
+    }
+    const Clash c = find_clash(count, out, {src});   // a job may write over its own src, jobs may share src
+    if (c == CLASH_TWO_WRITERS) return invalid("two jobs of one batch write the same TRLWE row");
+    if (c == CLASH_READ_OF_WRITTEN) return invalid("a job reads a TRLWE row that another job of the batch writes");
+    return ACCEPT;
+}
+
 // iyk_hip_trlwe_add_batch
 inline Refusal check_trlwe_add_batch(uint64_t trlwe_slots, uint64_t count, const int32_t* a, const int32_t* b, const int32_t* out,
                                      std::vector<TrlweAddJob>& jobs)

@@ -16,7 +16,7 @@
 // (/root/reference/src/iyokan_tfhepp.hpp:267,282-291,426-443,627); TFHEpp's product is an inexact FP64 FFT, this one is exact.
 #pragma once
 #include "blind_rotate_fft.hpp"
-#include "jobs.hpp"   // CmuxJob, CmuxChainJob, CMUX_CHAIN_MAX_STEPS
+#include "jobs.hpp"   // CmuxJob, CmuxChainJob, CMUX_CHAIN_MAX_STEPS, CmuxRotChainJob, CmuxRotStep
 
 namespace iyk {
 
@@ -288,6 +288,118 @@ __global__ __launch_bounds__(64 * BR_WAVES, 2) void cmux_chain_kernel(const Cmux
             fft::round16(S[cc][0], lo);
             if (rev) fft::cmux_acc_replace16(lane, mem_row + cc * NTT_N, S[cc][1], lo, acc_lds + cc * NTT_N);
             else fft::acc_update16(lane, S[cc][1], lo, acc_lds + cc * NTT_N);
+        }
+        set_prio<0>();
+        lds_sync();
+    }
+    if (CHECK && max_err_bits) {   // non-negative doubles order like their bit patterns
+        unsigned long long b;
+        __builtin_memcpy(&b, &worst, 8);
+        atomicMax(max_err_bits, b);
+    }
+    if (live) fft::cmux_store_acc(lane0, acc_lds, trlwe + (size_t)j_out * (2 * NTT_N));
+}
+
+// A chain of ROTATE-form CMUXes per wavefront (CmuxRotChainJob): the lower half of a ROM read, LROMUX of TaskTFHEppROMUX
+// (/root/reference/src/iyokan_tfhepp.hpp:282-291: per low address bit PolynomialMulByXaiMinusOne of the accumulator, trgswfftExternalProduct
+// with that bit's selector, added to the accumulator).  Step j of job g takes the pair (sel, rot) = list[first + j] of the staged step
+// list:   acc = acc + S[sel] [.] ((X^rot - 1) acc),   each the in1 < 0 job of cmux_fft_kernel with in0 = out = acc.
+// The same workgroup shape, LDS map and row loop as cmux_chain_kernel; the accumulator stays in the wave's LDS for all steps and a step
+// reads NOTHING from the TRLWE store: the rotated difference comes from the accumulator itself (diff16, as in blind_rotate_fft_kernel,
+// whose step this is with the caller's selector in place of BK[i]).  diff16 reads other lanes' accumulator words, acc_update16 writes
+// the lane's own: both polynomials' differences are taken in the row loop, before the first update, and the lds_sync that ends a step
+// orders its updates before the next step's reads.  The words are those of `steps` cmux_fft_kernel rotate jobs one after the other.
+template <class G, bool CHECK>
+__global__ __launch_bounds__(64 * BR_WAVES, 2) void cmux_rotate_chain_kernel(const CmuxRotChainJob* __restrict__ jobs, int njobs,
+                                                                             const CmuxRotStep* __restrict__ list,
+                                                                             const fft::cplx* __restrict__ trgsw, u32* trlwe,
+                                                                             const fft::Consts* __restrict__ Cp,
+                                                                             unsigned long long* __restrict__ max_err_bits)
+{
+    const fft::Consts& C = *Cp;
+    constexpr int L = G::L;
+    extern __shared__ __attribute__((aligned(4096))) unsigned char smem[];
+    fft::cplx* s_t1 = reinterpret_cast<fft::cplx*>(smem);                                   // [k0][lane]
+    u32* s_acc = reinterpret_cast<u32*>(smem + BR_FFT_T1_BYTES);                            // [BR_WAVES][2][NTT_N]
+    fft::cplx* s_xb = reinterpret_cast<fft::cplx*>(smem + BR_FFT_T1_BYTES + (size_t)BR_WAVES * 2 * NTT_N * sizeof(u32));
+    fft::cplx* s_t2 = s_xb + (size_t)BR_WAVES * (fft::XCHG_BYTES / sizeof(fft::cplx));      // [b][a]
+    fft::Lf* s_lf3 = reinterpret_cast<fft::Lf*>(s_t2 + 64);   // [which][lane'']
+    fft::Lf* s_lf2 = s_lf3 + 4 * 64;                           // [which][k0]
+    for (int e = threadIdx.x; e < 8 * 64; e += 64 * BR_WAVES) s_t1[e] = C.t1[e >> 6][e & 63];
+    if (threadIdx.x < 64) s_t2[threadIdx.x] = C.t2t[threadIdx.x >> 3][threadIdx.x & 7];
+    if (threadIdx.x < 4 * 64) s_lf3[threadIdx.x] = C.lf3[threadIdx.x >> 6][threadIdx.x & 63];
+    if (threadIdx.x < 4 * 8) s_lf2[threadIdx.x] = C.lf2[threadIdx.x >> 3][threadIdx.x & 7];
+    __syncthreads();
+
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane0 = threadIdx.x & 63;
+    int job = blockIdx.x * BR_WAVES + wave;
+    const bool live = job < njobs;
+    if (!live) job = njobs - 1;
+    // the job's four words and every step's pair are wave-uniform (scalar registers, a provably uniform descriptor)
+    const int j_first = __builtin_amdgcn_readfirstlane(jobs[job].first), j_steps = __builtin_amdgcn_readfirstlane(jobs[job].steps);
+    const int j_src = __builtin_amdgcn_readfirstlane(jobs[job].src), j_out = __builtin_amdgcn_readfirstlane(jobs[job].out);
+
+    u32* acc_lds = s_acc + wave * 2 * NTT_N;
+    fft::cplx* xb = s_xb + (size_t)wave * (fft::XCHG_BYTES / sizeof(fft::cplx));
+    fft::cmux_load_acc(lane0, trlwe + (size_t)j_src * (2 * NTT_N), acc_lds);
+    lds_sync();
+
+    constexpr u32 SLOT = fft::trgsw_slot_cplx<G>();
+    fft::Twist U = C.u;
+    asm volatile("" : "+s"(U.c1), "+s"(U.s1), "+s"(U.c2), "+s"(U.s2), "+s"(U.c3), "+s"(U.s3));
+    fft::LfU LU = C.lu;
+    asm volatile("" : "+s"(LU.t2), "+s"(LU.c2), "+s"(LU.t1), "+s"(LU.c1), "+s"(LU.t1w), "+s"(LU.c1w));
+
+    double worst = 0.0;
+#pragma unroll 1
+    for (int j = 0; j < j_steps; ++j) {
+        const int s_sel = __builtin_amdgcn_readfirstlane(list[j_first + j].sel);
+        const u32 s_rot = (u32)__builtin_amdgcn_readfirstlane(list[j_first + j].rot);
+        const fft::Keys keys(trgsw + (size_t)s_sel * SLOT, SLOT * (u32)sizeof(fft::cplx), lane0);
+        fft::cplx S[2][2][8];   // [c'][half][k2]
+        u32 u[16];
+#pragma unroll
+        for (int e = 0; e < 32; ++e) S[e >> 4][(e >> 3) & 1][e & 7] = {0.0, 0.0};
+#pragma unroll 1
+        for (int r = 0; r < 2 * L; ++r) {
+            const int lane = fft_lane_id(lane0);
+            const int c = r >= L ? 1 : 0, lvl = r - c * L;
+            if (lvl == 0) fft::diff16<G>(lane, s_rot, acc_lds + c * NTT_N, u);
+            fft::cplx a[8];
+            fft::digits8<G>(lvl, u, a);
+            const u32 row_off = (u32)r * 4u * (u32)fft::M;
+            const u32 koff = (u32)lane * 16u;
+            fft::cplx k0[4], k1[4];
+#pragma unroll
+            for (int pc = 0; pc < 4; ++pc) k0[pc] = keys.at_lane(koff, row_off, pc, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            fft_forward_lf(lane, a, LU, s_lf2, s_lf3, xb);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                fft::cplx (&cur)[4] = (q & 1) ? k1 : k0;
+                fft::cplx (&nxt)[4] = (q & 1) ? k0 : k1;
+                __builtin_amdgcn_sched_barrier(0);   // as in cmux_fft_kernel: hoisted, a row's 32 values do not fit
+                if (q + 1 < 8) {
+#pragma unroll
+                    for (int pc = 0; pc < 4; ++pc) nxt[pc] = keys.at_lane(koff, row_off, pc, q + 1);
+                }
+#pragma unroll
+                for (int pc = 0; pc < 4; ++pc) fft::cmac<false>(S[pc >> 1][pc & 1][q], a[q], cur[pc]);
+            }
+        }
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+            const int lane = fft_lane_id(lane0);
+            u32 lo[16];
+            fft_inverse2(lane, S[cc][0], S[cc][1], U, s_t1 + lane, s_t2 + (lane & 7), xb);
+            if (CHECK) {
+                const double e0 = fft::round_err8(S[cc][0]), e1 = fft::round_err8(S[cc][1]);
+                worst = e0 > worst ? e0 : worst;
+                worst = e1 > worst ? e1 : worst;
+            }
+            fft::round16(S[cc][0], lo);
+            fft::acc_update16(lane, S[cc][1], lo, acc_lds + cc * NTT_N);
         }
         set_prio<0>();
         lds_sync();

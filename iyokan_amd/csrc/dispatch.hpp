@@ -230,5 +230,10 @@ constexpr int cb_fft_grid(long count, int cus)
     return (int)(count < (long)cus ? count : (long)cus);
 }
 
+// ---- the fused rotate chain of a ROM read (cmux_fft.hpp: cmux_rotate_chain_kernel) ----------------------------------------------
+// One wave per job, ROT_WAVES jobs per workgroup, like every kernel of cmux_fft.hpp; the last workgroup may be partial.  0 where there
+// is nothing to launch.
+constexpr long cmux_rotate_chain_grid(long count) { return count <= 0 ? 0 : (count + ROT_WAVES - 1) / ROT_WAVES; }
+
 }  // namespace dispatch
 }  // namespace iyk

@@ -730,6 +730,48 @@ void cmux_chain(const CmuxChainJob& j, const fft::cplx* trgsw, u32* T)
     ALL_LANES fft::cmux_store_acc(lane, acc.data(), T + (size_t)j.out * (2 * NTT_N));
 }
 
+// lane-by-lane run of cmux_fft.hpp::cmux_rotate_chain_kernel for one job, in place on the TRLWE rows T (same phase functions, same order)
+template <class G>
+void cmux_rotate_chain(const CmuxRotChainJob& j, const CmuxRotStep* list, const fft::cplx* trgsw, u32* T)
+{
+    constexpr int L = G::L;
+    std::vector<u32> acc(2 * NTT_N);
+    std::vector<fft::cplx> xbuf(fft::XCHG_BYTES / sizeof(fft::cplx));
+    fft::cplx* xb = xbuf.data();
+    static thread_local fft::cplx S[2][2][64][8], a[64][8];
+    static thread_local u32 u[64][16], lo[64][16];
+    ALL_LANES fft::cmux_load_acc(lane, T + (size_t)j.src * (2 * NTT_N), acc.data());
+    for (int s = 0; s < j.steps; ++s) {
+        const CmuxRotStep& step = list[j.first + s];
+        const fft::cplx* slot = trgsw + (size_t)step.sel * fft::trgsw_slot_cplx<G>();
+        ALL_LANES for (int e = 0; e < 32; ++e) S[e >> 4][(e >> 3) & 1][lane][e & 7] = {0.0, 0.0};
+        for (int r = 0; r < 2 * L; ++r) {
+            const int c = r >= L ? 1 : 0, lvl = r - c * L;
+            if (lvl == 0) ALL_LANES fft::diff16<G>(lane, (u32)step.rot, acc.data() + c * NTT_N, u[lane]);
+            ALL_LANES fft::digits8<G>(lvl, u[lane], a[lane]);
+            fft_forward_lf_wave(a, xb);
+            const u32 row_off = (u32)r * 4u * (u32)fft::M;
+            ALL_LANES
+            {
+                const fft::Keys keys(slot, 0, lane);
+                for (int q = 0; q < 8; ++q)
+                    for (int pc = 0; pc < 4; ++pc) fft::cmac<false>(S[pc >> 1][pc & 1][lane][q], a[lane][q], keys.at(row_off, pc, q));
+            }
+        }
+        for (int cc = 0; cc < 2; ++cc) {
+            fft_inverse2_wave(S[cc][0], S[cc][1], xb);
+            ALL_LANES
+            {
+                const double e0 = fft::round_err8(S[cc][0][lane]), e1 = fft::round_err8(S[cc][1][lane]);
+                g_fft_worst = std::max(g_fft_worst, std::max(e0, e1));
+                fft::round16(S[cc][0][lane], lo[lane]);
+            }
+            ALL_LANES fft::acc_update16(lane, S[cc][1][lane], lo[lane], acc.data() + cc * NTT_N);
+        }
+    }
+    ALL_LANES fft::cmux_store_acc(lane, acc.data(), T + (size_t)j.out * (2 * NTT_N));
+}
+
 // one inverse transform of one wave (kernels_fft.hpp::fft_inverse1)
 void fft_inverse1_wave(fft::cplx (*a)[8], fft::cplx* xb)
 {
@@ -993,6 +1035,26 @@ int emu_cmux_chain(int set, uint32_t* trlwe, uint64_t rows, const double* trgsw_
         if (set == 0) cmux_chain<fft::Gadget<3, 6>>(j, k, trlwe);
         else cmux_chain<fft::Gadget<2, 10>>(j, k, trlwe);
     }
+    return 0;
+}
+/* cmux_fft.hpp::cmux_rotate_chain_kernel: ONE job — acc = T[src]; `steps` rotate-form CMUXes with the pairs (sel[j], rot[j]); T[out] = acc
+ * — in place on `rows` TRLWE rows.  set and trgsw_fft as for emu_cmux_fft; the rounding distances feed iyk_emul_fft_round_error like the
+ * chain's.  -1: unknown set, steps outside [1, 32], a rot outside [0, 2N) or an index outside its store (nothing is written). */
+int iyk_emul_cmux_rotate_chain(int set, uint32_t* trlwe, uint64_t rows, const double* trgsw_fft, uint64_t sels, int32_t steps, const int32_t* sel,
+                               const int32_t* rot, int32_t src, int32_t out)
+{
+    if (set != 0 && set != 1) return -1;
+    if (steps < 1 || steps > CMUX_ROT_CHAIN_MAX_STEPS) return -1;
+    if (src < 0 || (uint64_t)src >= rows || out < 0 || (uint64_t)out >= rows) return -1;
+    std::vector<CmuxRotStep> list((size_t)steps);
+    for (int32_t j = 0; j < steps; ++j) {
+        if (sel[j] < 0 || (uint64_t)sel[j] >= sels || rot[j] < 0 || rot[j] >= 2 * NTT_N) return -1;
+        list[(size_t)j] = CmuxRotStep{sel[j], rot[j]};
+    }
+    const CmuxRotChainJob j{0, steps, src, out};
+    const fft::cplx* k = reinterpret_cast<const fft::cplx*>(trgsw_fft);
+    if (set == 0) cmux_rotate_chain<fft::Gadget<3, 6>>(j, list.data(), k, trlwe);
+    else cmux_rotate_chain<fft::Gadget<2, 10>>(j, list.data(), k, trlwe);
     return 0;
 }
 /* kernels.hpp::sample_extract_index_kernel for one TRLWE: N + 1 words of the TLWE lvl1 at coefficient index h < N */
@@ -1666,6 +1728,19 @@ int iyk_emul_check_cmux_chain_batch(uint64_t trgsw_slots, uint64_t trlwe_slots, 
     if (!r) o.list(jobs);
     return o.finish(r);
 }
+/* lists: the jobs {first, steps, src, out}, the steps {sel, rot} */
+int iyk_emul_check_cmux_rotate_chain_batch(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* steps, const int32_t* sel,
+                                           const int32_t* rot, const int32_t* src, const int32_t* out, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    std::vector<CmuxRotChainJob> jobs;
+    std::vector<CmuxRotStep> list;
+    const args::Refusal r = args::cmux_rotate_chain_args(trgsw_slots, trlwe_slots, count, steps, sel, rot, src, out, jobs, list);
+    if (!r) o.list(jobs), o.list(list);
+    return o.finish(r);
+}
+/* dispatch::cmux_rotate_chain_grid */
+int64_t iyk_emul_cmux_rotate_chain_grid(int64_t count) { return (int64_t)dispatch::cmux_rotate_chain_grid((long)count); }
 int iyk_emul_check_trlwe_add_batch(uint64_t trlwe_slots, uint64_t count, const int32_t* a, const int32_t* b, const int32_t* out, IYK_CHECK_OUT)
 {
     IYK_CHECK_OUT_INIT;

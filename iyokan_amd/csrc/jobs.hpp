@@ -44,6 +44,15 @@ struct CmuxChainJob {
     int32_t src, mem, out;
 };
 
+// acc = T[src]; steps rotate-form CMUXes acc += S[sel] [.] ((X^rot - 1) acc) with the (sel, rot) pairs first .. first + steps - 1 of the
+// batch's step list (CmuxRotStep, uploaded behind the jobs); T[out] = acc (cmux_fft.hpp: cmux_rotate_chain_kernel)
+struct CmuxRotChainJob {
+    int32_t first, steps, src, out;
+};
+struct CmuxRotStep {
+    int32_t sel, rot;
+};
+
 // private key switch of lvl2 TLWE `in` into TRLWE row `out` with the key's function c (privks.hpp)
 struct PrivksJob {
     int32_t in, c, out;
@@ -59,8 +68,10 @@ struct CbJob {
 
 static_assert(sizeof(RotJob) == 20 && sizeof(KsJob) == 16 && sizeof(EwJob) == 12 && sizeof(TrlweAddJob) == 12, "job layout is the upload format");
 static_assert(sizeof(CmuxJob) == 20 && sizeof(CmuxChainJob) == 24 && sizeof(PrivksJob) == 12 && sizeof(CbJob) == 24, "job layout is the upload format");
+static_assert(sizeof(CmuxRotChainJob) == 16 && sizeof(CmuxRotStep) == 8, "job layout is the upload format");
 
 static constexpr int CMUX_CHAIN_MAX_STEPS = 32;       // the bits of CmuxChainJob::pattern
+static constexpr int CMUX_ROT_CHAIN_MAX_STEPS = 32;   // steps of one CmuxRotChainJob: count * 32 steps bound the step list's 32-bit index
 static constexpr uint32_t CB_MAX_N0 = 2047;           // n + 1 mod-switched words fit the LDS abar array of cb_rotate_kernel
 static constexpr uint32_t PRIVKS_MAX_N_IN = 1u << 16;
 static constexpr uint32_t ABAR_STRIDE = 1024;         // words per job in a stream's mod-switched rotation inputs (n + 1 <= 768 used)

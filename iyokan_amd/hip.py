@@ -43,6 +43,7 @@ EXPORTS = [
     "iyk_hip_trgsw_from_rows",
     "iyk_hip_bk2_key_create", "iyk_hip_bk2_key_upload", "iyk_hip_bk2_key_free", "iyk_hip_bk2_key_bytes", "iyk_hip_cb_rotate_batch",
     "iyk_hip_circuit_bootstrap_batch", "iyk_hip_cb_rotate_form", "iyk_hip_bk2_key_create_form", "iyk_hip_bk2_key_form",
+    "iyk_hip_cmux_rotate_chain_batch",
 ]
 
 
@@ -97,6 +98,7 @@ def lib():
         L.iyk_hip_trgsw_upload.argtypes = [_vp, _vp, u64, u64, u64, _u32p]
         L.iyk_hip_cmux_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p, _i32p]
         L.iyk_hip_cmux_chain_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _u32p, _i32p, _i32p, _i32p]
+        L.iyk_hip_cmux_rotate_chain_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p, _i32p]
         L.iyk_hip_trlwe_add_batch.argtypes = [_vp, _vp, u64, u64, _i32p, _i32p, _i32p, ctypes.c_uint32]
         u32 = ctypes.c_uint32
         L.iyk_hip_privks_key_create.argtypes = [ctypes.c_int, u32, u32, u32, ctypes.POINTER(_vp)]
@@ -605,6 +607,22 @@ class Stream:
         p = lambda a: a.ctypes.data_as(_i32p)
         _check(lib().iyk_hip_cmux_chain_batch(self.h, trgsw.ptr, trgsw.slots, trlwe.ptr, trlwe.slots, len(sel0), p(sel0), p(steps),
                                               pattern.ctypes.data_as(_u32p), p(src), p(mem), p(out)), "iyk_hip_cmux_chain_batch")
+
+    def cmux_rotate_chain_batch(self, trgsw, trlwe, steps, sel, rot, src, out):
+        """len(steps) independent chains of rotate-form CMUXes on rows of a Trlwe store, asynchronous (the lower half of one ROM read
+        per job): acc = T[src]; for j < steps[g]: acc = acc + S[sel_j] [.] ((X^rot_j - 1) acc); T[out] = acc.  sel and rot hold the jobs'
+        steps one after the other, sum(steps) entries.  Word for word what steps[g] dependent cmux_batch rotate jobs give.  A job may
+        write over its own src and jobs may share src; no out may be the src / out of another job of the batch."""
+        steps, sel, rot, src, out = map(_i32, (steps, sel, rot, src, out))
+        assert len(steps) == len(src) == len(out) and len(sel) == len(rot)
+        # the library reads the entries of the jobs in front of the first steps[g] it refuses, never more: they must be there
+        bad = np.flatnonzero((steps < 1) | (steps > 32))
+        need = int(steps[: bad[0] if len(bad) else len(steps)].sum())
+        if need > len(sel) or (not len(bad) and need != len(sel)):
+            raise ValueError(f"sel and rot hold {len(sel)} steps, the jobs state {need}")
+        p = lambda a: a.ctypes.data_as(_i32p)
+        _check(lib().iyk_hip_cmux_rotate_chain_batch(self.h, trgsw.ptr, trgsw.slots, trlwe.ptr, trlwe.slots, len(steps), p(steps), p(sel),
+                                                     p(rot), p(src), p(out)), "iyk_hip_cmux_rotate_chain_batch")
 
     def trlwe_add_batch(self, trlwe, a, b, out, b0_offset=0):
         """T[out] = T[a] + T[b] mod 2^32 on rows of a Trlwe store, b0_offset added to coefficient 0 of the b polynomial (the tail of

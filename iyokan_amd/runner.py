@@ -167,9 +167,11 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
     `packet`: the encrypted request (TFHEPacket) whose TRLWE forms `rom` / `ram` fill the memories; `decrypt_ram(rows) -> bits`
     (client.decrypt_ram_trlwe of the caller's keys) reads the result packet's RAM images out of Ram.cells().
     The 80-bit set is refused unless words_only=True: there the restatement of the circuit bootstrapping itself misreads ROM bits
-    (DESIGN.md section 6d), so only words may be compared, never decryptions."""
+    (DESIGN.md section 6d), so only words may be compared, never decryptions.
+    rom_fused=True: the rotate tail of every ROM read is ONE Stream.cmux_rotate_chain_batch (Rom.read(fused=True)): the same words."""
 
-    def __init__(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packet=None, decrypt_ram=None, words_only=False):
+    def __init__(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packet=None, decrypt_ram=None, words_only=False,
+                 rom_fused=False):
         from . import cmux, hip
         from .params import params_80bit
 
@@ -188,6 +190,7 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         be = executor.be
         self.stream, self.arena, self.ports = be.stream, be._arena, list(system.ports)
         self.bk2, self.privks_key, self.packet, self.decrypt_ram = bk2, privks_key, packet, decrypt_ram
+        self.rom_fused = bool(rom_fused)
         N, l, per = int(p.N), int(p.l), int(p.trgsw_rows)
         widest = max(pt.addr_width for pt in self.ports)
         self.tlwe2 = hip.Tlwe2(hip.Bk2Key.N2, widest * l, self.stream.gpu_index)
@@ -214,7 +217,7 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         self.stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, self._slots(pt.addr), [1] * pt.addr_width, self.tlwe2,
                                             0, self.scratch, mem.trgsw, 0)
         if pt.kind == "rom":
-            mem.read(None, self.arena, self._slots(pt.rdata).reshape(1, -1), resident=True)
+            mem.read(None, self.arena, self._slots(pt.rdata).reshape(1, -1), resident=True, fused=self.rom_fused)
         else:
             mem.read_port(self.arena, self._slots(pt.rdata))
 

@@ -7,7 +7,7 @@ the kernels' time does not depend on the words.  Wall time per clock is tick() +
 synchronisations.  The split is taken in a second pass that synchronises after every part of a port (rotation, private key switch +
 selector assembly, read tree + extraction, write-back + refresh) and after the gate levels, so its parts add up to more than the wall time.
 
-    python tools/cmux_system_measure.py [--clocks 3] > profiles/cmux_system_ab.txt"""
+    python tools/cmux_system_measure.py [--clocks 3] [--rom-fused] > profiles/cmux_system_ab.txt"""
 import argparse
 import os
 import sys
@@ -64,7 +64,7 @@ class SplitEngine(runner.CmuxCipherEngine):
         cmux.selectors_from_tlwe2(self.stream, self.privks_key, self.tlwe2, 0, pt.addr_width, self.scratch, mem.trgsw, 0)
         self._lap("private key switch + selectors")
         if pt.kind == "rom":
-            mem.read(None, self.arena, self._slots(pt.rdata).reshape(1, -1), resident=True)
+            mem.read(None, self.arena, self._slots(pt.rdata).reshape(1, -1), resident=True, fused=self.rom_fused)
         else:
             mem.read_port(self.arena, self._slots(pt.rdata))
         self._lap("read tree + extraction")
@@ -75,7 +75,7 @@ class SplitEngine(runner.CmuxCipherEngine):
         self._lap("write-back + refresh")
 
 
-def engine(keys, sysm, kind, bk2=None, pk=None):
+def engine(keys, sysm, kind, bk2=None, pk=None, rom_fused=False):
     import torch
 
     plan = FrontierPlan(sysm.nl, 1, stages=sysm.stages)
@@ -85,7 +85,7 @@ def engine(keys, sysm, kind, bk2=None, pk=None):
     if kind == "mux":
         return runner.CipherEngine(ex, enc, dec, zero), be, plan
     cls = SplitEngine if kind == "split" else runner.CmuxCipherEngine
-    return cls(sysm, ex, enc, dec, zero, bk2, pk), be, plan
+    return cls(sysm, ex, enc, dec, zero, bk2, pk, rom_fused=rom_fused), be, plan
 
 
 def clocks(eng, be, sysm, n):
@@ -109,6 +109,9 @@ def main():
     ap.add_argument("--clocks", type=int, default=3)
     ap.add_argument("--bk2-form", choices=sorted(hip.Bk2Key.FORMS), default="ntt",
                     help="the lvl2 bootstrapping key's form: ntt = the integer key, fft = the FP64 key (cb_rotate_fft_kernel)")
+    ap.add_argument("--rom-fused", action="store_true",
+                    help="the rotate tail of every ROM read as ONE cmux_rotate_chain_batch (Rom.read(fused=True)) instead of one cmux_batch per step")
+    ap.add_argument("--small-only", action="store_true", help="the small ROM + RAM system alone (the one with a ROM)")
     args = ap.parse_args()
     keys = client.keygen(params_128bit(), seed=1)
     hip.initialize(keys, device_ids=(0,))
@@ -123,25 +126,26 @@ def main():
     for first in range(0, pk.rows, 8192):
         pk.upload(st, first, window[:min(8192, pk.rows - first)])
     st.sync()
-    print(f"build {hip.build_id()}; {args.clocks} clocks per figure; 128-bit set; bk2 n = {bk2.n} form {bk2.form}, private key n_in = 2048, t = 10, basebit = 3")
+    print(f"build {hip.build_id()}; {args.clocks} clocks per figure; 128-bit set; bk2 n = {bk2.n} form {bk2.form}, private key n_in = 2048, t = 10, basebit = 3; "
+          f"ROM rotate tail {'fused (one cmux_rotate_chain_batch)' if args.rom_fused else 'unfused (one cmux_batch per step)'}")
     tmp = tempfile.mkdtemp()
     systems = [("small: ROM 3-bit address x 4 bits, RAM 2-bit address x 2 bits, 12 gates", cases.write_blueprint(tmp)),
                ("ram-addr8bit: RAM 8-bit address x 8 bits", os.path.join(ROOT, "tests", "golden", "reftest", "config-toml", "ram-addr8bit.toml"))]
-    for title, path in systems:
+    for title, path in systems[:1] if args.small_only else systems:
         print(f"\n== {title}")
         lowered, ported = load_blueprint(path), load_blueprint(path, cmux_memories=True)
         eng, be, plan = engine(keys, lowered, "mux")
         ms = clocks(eng, be, lowered, args.clocks)
         print(f"lowered MUX form : {ms:9.2f} ms per clock   ({lowered.nl.rotations()} rotations, {len(plan.levels)} levels)")
         be.close()
-        eng, be, plan = engine(keys, ported, "cmux", bk2, pk)
+        eng, be, plan = engine(keys, ported, "cmux", bk2, pk, args.rom_fused)
         ms = clocks(eng, be, ported, args.clocks)
         rot = sum(pt.addr_width for pt in ported.ports) * int(keys.params.l)
         print(f"CMUX memories    : {ms:9.2f} ms per clock   ({ported.nl.rotations()} gate rotations, {len(plan.levels)} levels, "
               f"{len(ported.ports)} ports, {rot} lvl2 rotations in {len(ported.ports)} batches)")
         eng.free()
         be.close()
-        eng, be, _ = engine(keys, ported, "split", bk2, pk)
+        eng, be, _ = engine(keys, ported, "split", bk2, pk, args.rom_fused)
         clocks(eng, be, ported, 0)
         for k in eng.ms:
             eng.ms[k] = 0.0
