@@ -323,6 +323,20 @@ int iyk_hip_cmux_chain_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t t
 int iyk_hip_cmux_rotate_chain_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe,
                                     uint64_t trlwe_slots, uint64_t count, const int32_t* steps, const int32_t* sel,
                                     const int32_t* rot, const int32_t* src, const int32_t* out);
+/* `count` independent CMUX read trees, asynchronous on st: up to four levels of the upper half (UROMUX / RAMUX) of one memory read per
+ * job.  Job g, with n = levels[g], halves the 2^n candidate rows T[first[g] .. first[g] + 2^n) n times:
+ *     level b < n, i < 2^(n-1-b):   candidate i = candidate 2 i + S[sel0[g] + b] [.] (candidate 2 i + 1 - candidate 2 i)
+ *     T[out] = the one candidate left
+ * i.e. level b is the cmux jobs (sel0 + b, in0 = candidate 2 i, in1 = candidate 2 i + 1) of one iyk_hip_cmux_batch.  Replaces n
+ * levels of the loops of TaskTFHEppROMUX's UROMUX and TaskTFHEppRAMUX (/root/reference/src/iyokan_tfhepp.hpp:262-271,425-443: CMUXFFT
+ * over pairs of rows, one address bit per level; the RAM's loop keeps its results in place at a doubling stride, as this kernel does).  One kernel, one workgroup per job; the rows between the levels stay in the
+ * workgroup's LDS and nothing but T[out] is written; word for word what levels[g] successive iyk_hip_cmux_batch launches give (the
+ * product is exact).  The four arrays are host arrays, copied before return.  Checked on every call: 1 <= levels <= 4, selector slots
+ * sel0 .. sel0 + levels - 1 in [0, trgsw_slots), the leaves and out in [0, trlwe_slots), and no out[g] is a leaf or the out of ANOTHER
+ * job — a job may write over one of its own leaves, and jobs may share leaves.  A violation is IYK_ERR_INVALID and nothing is staged
+ * or launched; IYK_ERR_STATE off the FFT path.  With IYK_HIP_DEBUG=1 the kernel feeds iyk_hip_fft_round_error. */
+int iyk_hip_cmux_tree_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
+                            uint64_t count, const int32_t* sel0, const int32_t* levels, const int32_t* first, const int32_t* out);
 /* T[out] = T[a] + T[b] mod 2^32 per job, with b0_offset added to coefficient 0 of the b polynomial; asynchronous on st, host
  * arrays copied before return.  The tail of TFHEpp::HomMUXwoSE<Lvl01> (TaskTFHEppGateMUXWoSE, /root/reference/src/iyokan_tfhepp.hpp:
  * 500-508): with a, b the rows of the two blind rotations iyk_hip_bootstrap_trlwe_batch(cs + c1 - mu) and (-cs + c0 - mu) and

@@ -1,5 +1,5 @@
-"""CMUX memories on the GPU: the read tree of a ROM over TRLWE rows (Stream.cmux_batch + index extraction; the rotate tail optionally as
-one fused Stream.cmux_rotate_chain_batch), and a RAM — read tree,
+"""CMUX memories on the GPU: the read tree of a ROM over TRLWE rows (Stream.cmux_batch + index extraction; optionally the upper levels as
+one fused Stream.cmux_tree_batch per four levels and the rotate tail as one fused Stream.cmux_rotate_chain_batch), and a RAM — read tree,
 MUXwoSE, one fused chain of CMUXes per cell (Stream.cmux_chain_batch) and the refresh of every cell.
 
 Replaces the reference's TaskTFHEppROMUX (UROMUX + LROMUX, /root/reference/src/iyokan_tfhepp.hpp:238-300) followed by one
@@ -81,6 +81,37 @@ def rom_rotate_chain(plan):
     out = tail[-1].out
     assert all(j.out == out for j in tail) and all(j.in0 == out for j in tail[1:])
     return RotateChain(len(tail), tuple(j.bit for j in tail), tuple(j.rot for j in tail), tail[0].in0, out)
+
+
+# One job of Stream.cmux_tree_batch, in plan rows: the 2^levels leaves first .. are halved `levels` times, level b selected by address
+# bit bit0 + b; row out is the one left.
+TreeJob = namedtuple("TreeJob", "bit0 levels first out")
+TREE_MAX_LEVELS = 4
+
+
+def rom_tree_jobs(plan):
+    """The upper levels of a rom_read_plan (the two-row launches in front of the rotate tail) cut into groups of at most
+    TREE_MAX_LEVELS levels, each group ONE cmux_tree_batch: [(jobs, region)], jobs a list of TreeJob that are independent of each other,
+    region the scratch region (0 or 1) the group writes, None for the last group, whose one job writes the result row.  A group's
+    leaves are the candidates in front of its first level — the data rows, then the outs of the group before, which are consecutive rows
+    of one region — so the plan's two regions suffice, alternating per group.  Empty where the plan has no upper tree."""
+    upper = [jobs for jobs in plan if jobs[0].in1 >= 0]
+    assert upper == plan[: len(upper)]
+    if not upper:
+        return []
+    D = 2 * len(upper[0])
+    assert upper[0][0].in0 == 0 and len(upper[-1]) == 1
+    result = upper[-1][0].out
+    region = [D, D + D // 2]   # rom_read_plan's two scratch regions
+    groups, first, lo, g = [], 0, 0, 0
+    while lo < len(upper):
+        levels = min(TREE_MAX_LEVELS, len(upper) - lo)
+        count = len(upper[lo + levels - 1])
+        last = lo + levels == len(upper)
+        base = result if last else region[g & 1]
+        groups.append(([TreeJob(upper[lo][0].bit, levels, first + (i << levels), base + i) for i in range(count)], None if last else g & 1))
+        first, lo, g = base, lo + levels, g + 1
+    return groups
 
 
 def selectors_from_tlwe2(stream, key, tlwe2, first, addr_width, trlwe_scratch, trgsw, first_slot=0):
@@ -187,11 +218,21 @@ class Rom:
             out.append(self.row(r, chain.out))
         return self.launches(reads)[: len(self.plan) - chain.steps], (steps, sel, rot, src, out)
 
-    def read(self, addr_trgsw, arena, out_slots, resident=False, fused=False):
+    def tree_launches(self, reads):
+        """The cmux_tree_batch argument lists (sel0, levels, first, out) of the upper tree of `reads` simultaneous reads, one tuple per
+        group of rom_tree_jobs: they replace the first sum(levels) tuples of launches(reads)."""
+        out = []
+        for jobs, _ in rom_tree_jobs(self.plan):
+            rows = [(r * self.addr_width + j.bit0, j.levels, self.row(r, j.first), self.row(r, j.out)) for r in range(reads) for j in jobs]
+            out.append(tuple(zip(*rows)))
+        return out
+
+    def read(self, addr_trgsw, arena, out_slots, resident=False, fused=False, fused_tree=False):
         """addr_trgsw: u32 [R][addr_width][(k+1) l][k+1][N] (client.encrypt_trgsw of every read's address bits, bit 0 first);
         out_slots: [R][word_bits] arena slots.  Asynchronous on the stream.  resident=True: the selectors are in self.trgsw already
         (slot read * addr_width + bit, e.g. from selectors_from_tlwe2 on this stream): addr_trgsw is ignored and nothing is uploaded.
-        fused=True sends the rotate tail of all reads as ONE cmux_rotate_chain_batch instead of one cmux_batch per step: the same words."""
+        fused=True sends the rotate tail of all reads as ONE cmux_rotate_chain_batch instead of one cmux_batch per step, fused_tree=True
+        the upper tree as ONE cmux_tree_batch per four levels instead of one cmux_batch per level: the same words either way."""
         if resident:
             out_slots = np.asarray(out_slots, dtype=np.int32).reshape(-1, self.word_bits)
             reads = out_slots.shape[0]
@@ -204,6 +245,11 @@ class Rom:
         if not resident:
             self.trgsw.upload(self.stream, 0, sel)
         upper, chain = self.launches_fused(reads) if fused else (self.launches(reads), None)
+        if fused_tree:
+            trees = self.tree_launches(reads)
+            for args in trees:
+                self.stream.cmux_tree_batch(self.trgsw, self.trlwe, *args)
+            upper = upper[sum(args[1][0] for args in trees):]   # what is left of `upper` is the unfused rotate tail
         for args in upper:
             self.stream.cmux_batch(self.trgsw, self.trlwe, *args)
         if chain is not None:
@@ -298,21 +344,31 @@ class Ram:
             out.append(tuple(zip(*rows)))
         return out
 
+    def tree_launches(self):
+        """The cmux_tree_batch argument lists (sel0, levels, first, out) of the read tree, all planes' jobs of a group of rom_tree_jobs in
+        one launch: together they replace read_launches()."""
+        out = []
+        for jobs, _ in rom_tree_jobs(self.plan):
+            rows = [(j.bit0, j.levels, self.row(d, j.first), self.row(d, j.out)) for d in range(self.data_width) for j in jobs]
+            out.append(tuple(zip(*rows)))
+        return out
+
     def write_jobs(self):
         """One ChainJob per cell of every plane, in place on the cell rows, from the plane's written TRLWE."""
         C = self.cells_per_plane
         return [j for d in range(self.data_width) for j in ram_write_jobs(self.addr_width, self.mux_rows(d)[0], d * C)]
 
-    def clock(self, addr_trgsw, arena, wren_slot, wdata_slots, rdata_slots, fused=True, resident=False):
+    def clock(self, addr_trgsw, arena, wren_slot, wdata_slots, rdata_slots, fused=True, resident=False, fused_tree=False):
         """One clock of the reference's RAM network, asynchronous on the stream.  addr_trgsw: u32 [addr_width][(k+1) l][k+1][N]
         (client.encrypt_trgsw of the address bits, bit 0 first); arena holds the TLWEs of wren (one slot) and wdata (data_width
         slots) and receives rdata (data_width slots, the addressed word BEFORE the write).  fused=False sends the write-back as
         addr_width cmux_batch launches instead of one cmux_chain_batch: the same words.  resident=True: the addr_width selectors are in
-        self.trgsw already (e.g. from selectors_from_tlwe2 on this stream): addr_trgsw is ignored and nothing is uploaded."""
+        self.trgsw already (e.g. from selectors_from_tlwe2 on this stream): addr_trgsw is ignored and nothing is uploaded.
+        fused_tree=True sends the read tree as one cmux_tree_batch per four levels (read_port): the same words."""
         self._slots(wdata_slots, rdata_slots)   # both refused before anything is uploaded or enqueued
         if not resident:
             self.trgsw.upload(self.stream, 0, np.ascontiguousarray(addr_trgsw, dtype=np.uint32).reshape(self.addr_width, self.trgsw.words))
-        self.read_port(arena, rdata_slots)
+        self.read_port(arena, rdata_slots, fused_tree)
         self.write_port(arena, wren_slot, wdata_slots, rdata_slots, fused)
 
     def _slots(self, *lists):
@@ -321,15 +377,20 @@ class Ram:
             raise ValueError(f"expected {self.data_width} wdata and {self.data_width} rdata slots")
         return out
 
-    def read_port(self, arena, rdata_slots):
+    def read_port(self, arena, rdata_slots, fused_tree=False):
         """The read half of a clock (steps 1, 2: RAMUX, SEI(0) + key switch -> rdata) with the selectors that are resident in
         self.trgsw.  Inside a netlist rdata feeds the logic that computes wren / wdata of the same clock, so the two halves are
-        enqueued apart: read_port, the gates, write_port.  Together they enqueue what clock(resident=True) enqueues."""
+        enqueued apart: read_port, the gates, write_port.  Together they enqueue what clock(resident=True) enqueues.
+        fused_tree=True sends the tree as ONE cmux_tree_batch per four levels instead of one cmux_batch per level: the same words."""
         st, w = self.stream, self.data_width
         rdata_slots, = self._slots(rdata_slots)
         # 1, 2: RAMUX, SEI(0) + key switch -> rdata
-        for args in self.read_launches():
-            st.cmux_batch(self.trgsw, self.trlwe, *args)
+        if fused_tree:
+            for args in self.tree_launches():
+                st.cmux_tree_batch(self.trgsw, self.trlwe, *args)
+        else:
+            for args in self.read_launches():
+                st.cmux_batch(self.trgsw, self.trlwe, *args)
         result = [self.row(d, self.layout.result) for d in range(w)]
         st.sample_extract_index_keyswitch_batch(self.trlwe, result, np.zeros(w, dtype=np.int32), rdata_slots, arena)
 

@@ -253,6 +253,37 @@ inline Refusal cmux_rotate_chain_args(uint64_t trgsw_slots, uint64_t trlwe_slots
     return ACCEPT;
 }
 
+// iyk_hip_cmux_tree_batch, O(count * 2^levels).  Job g reads its 2^levels[g] leaves first[g] .. and writes out[g] alone (every row in
+// between stays in the workgroup's LDS).  A job may write over one of its OWN leaves — the workgroup has read them all before wave 0
+// stores — and jobs may share leaves, as the reads of one ROM all start from its data rows; no out is a leaf or the out of ANOTHER job.
+// Named like cmux_rotate_chain_args and for its reason: newer than the record tests/test_batch_args.py holds the check_* functions
+// against; tests/test_cmux_tree_emulation.py has every refusal text below against a set that reaches it.
+inline Refusal cmux_tree_args(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* sel0, const int32_t* levels,
+                              const int32_t* first, const int32_t* out, std::vector<CmuxTreeJob>& jobs)
+{
+    if (count > MAX_ROW_BATCH) return invalid("batch too large");
+    if (trgsw_slots > MAX_TRGSW_SLOTS || trlwe_slots > MAX_STORE_ROWS) return invalid("store larger than an allocation can be");
+    jobs.resize(count);
+    for (uint64_t g = 0; g < count; ++g) {
+        if (levels[g] < 1 || levels[g] > CMUX_TREE_MAX_LEVELS) return invalid("levels outside [1, 4]");
+        if (!slot_ok(sel0[g], trgsw_slots) || (uint64_t)sel0[g] + (uint64_t)levels[g] > trgsw_slots)
+            return invalid("selector index outside the selector store");
+        if (!slot_ok(first[g], trlwe_slots) || (uint64_t)first[g] + (1ull << levels[g]) > trlwe_slots || !slot_ok(out[g], trlwe_slots))
+            return invalid("TRLWE index outside the buffer");
+        jobs[g] = CmuxTreeJob{sel0[g], levels[g], first[g], out[g]};
+    }
+    if (find_clash(count, out) == CLASH_TWO_WRITERS) return invalid("two jobs of one batch write the same TRLWE row");
+    std::unordered_map<int32_t, uint64_t> writer;   // out row -> its job
+    writer.reserve(count * 2);
+    for (uint64_t g = 0; g < count; ++g) writer.emplace(out[g], g);
+    for (uint64_t g = 0; g < count; ++g)
+        for (int32_t k = 0; k < (1 << levels[g]); ++k) {
+            const auto w = writer.find(first[g] + k);
+            if (w != writer.end() && w->second != g) return invalid("a job reads a TRLWE row that another job of the batch writes");
+        }
+    return ACCEPT;
+}
+
 // iyk_hip_trlwe_add_batch
 inline Refusal check_trlwe_add_batch(uint64_t trlwe_slots, uint64_t count, const int32_t* a, const int32_t* b, const int32_t* out,
                                      std::vector<TrlweAddJob>& jobs)

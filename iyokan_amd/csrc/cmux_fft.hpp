@@ -16,7 +16,7 @@
 // (/root/reference/src/iyokan_tfhepp.hpp:267,282-291,426-443,627); TFHEpp's product is an inexact FP64 FFT, this one is exact.
 #pragma once
 #include "blind_rotate_fft.hpp"
-#include "jobs.hpp"   // CmuxJob, CmuxChainJob, CMUX_CHAIN_MAX_STEPS, CmuxRotChainJob, CmuxRotStep
+#include "jobs.hpp"   // CmuxJob, CmuxChainJob, CMUX_CHAIN_MAX_STEPS, CmuxRotChainJob, CmuxRotStep, CmuxTreeJob
 
 namespace iyk {
 
@@ -410,6 +410,129 @@ __global__ __launch_bounds__(64 * BR_WAVES, 2) void cmux_rotate_chain_kernel(con
         atomicMax(max_err_bits, b);
     }
     if (live) fft::cmux_store_acc(lane0, acc_lds, trlwe + (size_t)j_out * (2 * NTT_N));
+}
+
+// A CMUX read tree per WORKGROUP (CmuxTreeJob): up to CMUX_TREE_MAX_LEVELS = log2(2 BR_WAVES) levels of the upper half of a ROM / RAM
+// read, UROMUX of TaskTFHEppROMUX and TaskTFHEppRAMUX (/root/reference/src/iyokan_tfhepp.hpp:267,426-443: CMUXFFT over pairs of
+// candidate rows, one address bit per level).  Unlike the three kernels above a workgroup, not a wave, owns a job.
+//   level 0:       wave w < 2^(levels-1) is cmux_fft_kernel's job (sel0, in0 = T[first + 2 w], in1 = T[first + 2 w + 1]); the result
+//                  stays in the wave's accumulator s_acc[w].
+//   level b >= 1:  the waves with w % 2^b == 0 go on: in0 = the wave's own accumulator, in1 = the accumulator of wave w + 2^(b-1), read
+//                  from LDS (cmux_diff16 on an LDS source), selector slot sel0 + b; the result stays in s_acc[w].
+// Wave w + 2^(b-1) took part in level b - 1 and takes part in no later one: at level b nobody writes what another wave reads, and a
+// wave reads its partner's words only after the workgroup barrier that follows level b - 1.  The barriers stand between the levels,
+// outside every branch on the wave number, so all 8 waves reach each of them — the waves a short tree never uses and the ones that have
+// dropped out included.  No word leaves the workgroup between the levels; wave 0 stores T[out] after the last one.  The same workgroup
+// shape, LDS map, row loop and per-step descriptor on the slot's own base as cmux_fft_kernel, and the words of `levels` successive
+// cmux_fft_kernel launches: the product is exact.
+template <class G, bool CHECK>
+__global__ __launch_bounds__(64 * BR_WAVES, 2) void cmux_tree_kernel(const CmuxTreeJob* __restrict__ jobs,
+                                                                     const fft::cplx* __restrict__ trgsw, u32* trlwe,
+                                                                     const fft::Consts* __restrict__ Cp,
+                                                                     unsigned long long* __restrict__ max_err_bits)
+{
+    const fft::Consts& C = *Cp;
+    constexpr int L = G::L;
+    extern __shared__ __attribute__((aligned(4096))) unsigned char smem[];
+    fft::cplx* s_t1 = reinterpret_cast<fft::cplx*>(smem);                                   // [k0][lane]
+    u32* s_acc = reinterpret_cast<u32*>(smem + BR_FFT_T1_BYTES);                            // [BR_WAVES][2][NTT_N]
+    fft::cplx* s_xb = reinterpret_cast<fft::cplx*>(smem + BR_FFT_T1_BYTES + (size_t)BR_WAVES * 2 * NTT_N * sizeof(u32));
+    fft::cplx* s_t2 = s_xb + (size_t)BR_WAVES * (fft::XCHG_BYTES / sizeof(fft::cplx));      // [b][a]
+    fft::Lf* s_lf3 = reinterpret_cast<fft::Lf*>(s_t2 + 64);   // [which][lane'']
+    fft::Lf* s_lf2 = s_lf3 + 4 * 64;                           // [which][k0]
+    for (int e = threadIdx.x; e < 8 * 64; e += 64 * BR_WAVES) s_t1[e] = C.t1[e >> 6][e & 63];
+    if (threadIdx.x < 64) s_t2[threadIdx.x] = C.t2t[threadIdx.x >> 3][threadIdx.x & 7];
+    if (threadIdx.x < 4 * 64) s_lf3[threadIdx.x] = C.lf3[threadIdx.x >> 6][threadIdx.x & 63];
+    if (threadIdx.x < 4 * 8) s_lf2[threadIdx.x] = C.lf2[threadIdx.x >> 3][threadIdx.x & 7];
+    __syncthreads();
+
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane0 = threadIdx.x & 63;
+    static_assert((1 << CMUX_TREE_MAX_LEVELS) == 2 * BR_WAVES, "level 0 of the deepest tree is one CMUX per wave");
+    const int job = blockIdx.x;   // the grid is the job count (dispatch.hpp: cmux_tree_grid)
+    // the job's four words are uniform over the workgroup (scalar registers, a provably uniform descriptor, scalar branches per level)
+    const int j_sel0 = __builtin_amdgcn_readfirstlane(jobs[job].sel0), j_levels = __builtin_amdgcn_readfirstlane(jobs[job].levels);
+    const int j_first = __builtin_amdgcn_readfirstlane(jobs[job].first), j_out = __builtin_amdgcn_readfirstlane(jobs[job].out);
+    const bool member = wave < (1 << (j_levels - 1));   // the wave has a CMUX of level 0: a tree of fewer than 4 levels leaves the high waves idle
+
+    u32* acc_lds = s_acc + wave * 2 * NTT_N;
+    fft::cplx* xb = s_xb + (size_t)wave * (fft::XCHG_BYTES / sizeof(fft::cplx));
+    const u32* leaf1 = trlwe + (size_t)(j_first + 2 * wave + 1) * (2 * NTT_N);   // in1 of level 0; read by members only
+    if (member) fft::cmux_load_acc(lane0, trlwe + (size_t)(j_first + 2 * wave) * (2 * NTT_N), acc_lds);
+    lds_sync();
+
+    constexpr u32 SLOT = fft::trgsw_slot_cplx<G>();
+    fft::Twist U = C.u;
+    asm volatile("" : "+s"(U.c1), "+s"(U.s1), "+s"(U.c2), "+s"(U.s2), "+s"(U.c3), "+s"(U.s3));
+    fft::LfU LU = C.lu;
+    asm volatile("" : "+s"(LU.t2), "+s"(LU.c2), "+s"(LU.t1), "+s"(LU.c1), "+s"(LU.t1w), "+s"(LU.c1w));
+
+    double worst = 0.0;
+#pragma unroll 1
+    for (int b = 0; b < j_levels; ++b) {
+        if (member && (wave & ((1 << b) - 1)) == 0) {   // wave-uniform: no barrier inside
+            const u32* partner = s_acc + (wave + ((1 << b) >> 1)) * 2 * NTT_N;   // in1 of level b >= 1: a wave that has dropped out
+            const fft::Keys keys(trgsw + (size_t)(j_sel0 + b) * SLOT, SLOT * (u32)sizeof(fft::cplx), lane0);
+            fft::cplx S[2][2][8];   // [c'][half][k2]
+            u32 u[16];
+#pragma unroll
+            for (int e = 0; e < 32; ++e) S[e >> 4][(e >> 3) & 1][e & 7] = {0.0, 0.0};
+#pragma unroll 1
+            for (int r = 0; r < 2 * L; ++r) {
+                const int lane = fft_lane_id(lane0);
+                const int c = r >= L ? 1 : 0, lvl = r - c * L;
+                if (lvl == 0) {
+                    if (b == 0) fft::cmux_diff16<G>(lane, leaf1 + c * NTT_N, acc_lds + c * NTT_N, u);
+                    else fft::cmux_diff16<G>(lane, partner + c * NTT_N, acc_lds + c * NTT_N, u);
+                }
+                fft::cplx a[8];
+                fft::digits8<G>(lvl, u, a);
+                const u32 row_off = (u32)r * 4u * (u32)fft::M;
+                const u32 koff = (u32)lane * 16u;
+                fft::cplx k0[4], k1[4];
+#pragma unroll
+                for (int pc = 0; pc < 4; ++pc) k0[pc] = keys.at_lane(koff, row_off, pc, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                fft_forward_lf(lane, a, LU, s_lf2, s_lf3, xb);
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    fft::cplx (&cur)[4] = (q & 1) ? k1 : k0;
+                    fft::cplx (&nxt)[4] = (q & 1) ? k0 : k1;
+                    __builtin_amdgcn_sched_barrier(0);   // as in cmux_fft_kernel: hoisted, a row's 32 values do not fit
+                    if (q + 1 < 8) {
+#pragma unroll
+                        for (int pc = 0; pc < 4; ++pc) nxt[pc] = keys.at_lane(koff, row_off, pc, q + 1);
+                    }
+#pragma unroll
+                    for (int pc = 0; pc < 4; ++pc) fft::cmac<false>(S[pc >> 1][pc & 1][q], a[q], cur[pc]);
+                }
+            }
+#pragma unroll
+            for (int cc = 0; cc < 2; ++cc) {
+                const int lane = fft_lane_id(lane0);
+                u32 lo[16];
+                fft_inverse2(lane, S[cc][0], S[cc][1], U, s_t1 + lane, s_t2 + (lane & 7), xb);
+                if (CHECK) {
+                    const double e0 = fft::round_err8(S[cc][0]), e1 = fft::round_err8(S[cc][1]);
+                    worst = e0 > worst ? e0 : worst;
+                    worst = e1 > worst ? e1 : worst;
+                }
+                fft::round16(S[cc][0], lo);
+                fft::acc_update16(lane, S[cc][1], lo, acc_lds + cc * NTT_N);
+            }
+            set_prio<0>();
+        }
+        // between two levels: the level's accumulators are written before a wave of the next level reads its partner's.  Every wave of
+        // the workgroup comes here, b and j_levels are the same for all of them.
+        if (b + 1 < j_levels) __syncthreads();
+    }
+    lds_sync();
+    if (CHECK && max_err_bits) {   // non-negative doubles order like their bit patterns
+        unsigned long long bits;
+        __builtin_memcpy(&bits, &worst, 8);
+        atomicMax(max_err_bits, bits);
+    }
+    if (wave == 0) fft::cmux_store_acc(lane0, acc_lds, trlwe + (size_t)j_out * (2 * NTT_N));
 }
 #endif
 

@@ -235,5 +235,10 @@ constexpr int cb_fft_grid(long count, int cus)
 // is nothing to launch.
 constexpr long cmux_rotate_chain_grid(long count) { return count <= 0 ? 0 : (count + ROT_WAVES - 1) / ROT_WAVES; }
 
+// ---- the fused read tree of a ROM / RAM (cmux_fft.hpp: cmux_tree_kernel) ---------------------------------------------------------
+// One WORKGROUP per job, unlike the kernels above: its ROT_WAVES waves are the up to 2^(4-1) CMUXes of the tree's first level.  0 where
+// there is nothing to launch.
+constexpr long cmux_tree_grid(long count) { return count <= 0 ? 0 : count; }
+
 }  // namespace dispatch
 }  // namespace iyk

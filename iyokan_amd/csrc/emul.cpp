@@ -772,6 +772,55 @@ void cmux_rotate_chain(const CmuxRotChainJob& j, const CmuxRotStep* list, const 
     ALL_LANES fft::cmux_store_acc(lane, acc.data(), T + (size_t)j.out * (2 * NTT_N));
 }
 
+// lane-by-lane run of cmux_fft.hpp::cmux_tree_kernel for one job, in place on the TRLWE rows T (same phase functions, same order): the
+// workgroup's accumulators s_acc[ROT_WAVES][2][N] as the kernel keeps them, level by level — what the barrier between two levels orders
+// — and inside a level wave by wave: an active wave writes its own accumulator and reads one that no wave of the level writes.
+template <class G>
+void cmux_tree(const CmuxTreeJob& j, const fft::cplx* trgsw, u32* T)
+{
+    constexpr int L = G::L;
+    std::vector<u32> s_acc((size_t)dispatch::ROT_WAVES * 2 * NTT_N);
+    std::vector<fft::cplx> xbuf(fft::XCHG_BYTES / sizeof(fft::cplx));
+    fft::cplx* xb = xbuf.data();
+    static thread_local fft::cplx S[2][2][64][8], a[64][8];
+    static thread_local u32 u[64][16], lo[64][16];
+    const int members = 1 << (j.levels - 1);
+    for (int w = 0; w < members; ++w) ALL_LANES fft::cmux_load_acc(lane, T + (size_t)(j.first + 2 * w) * (2 * NTT_N), s_acc.data() + (size_t)w * 2 * NTT_N);
+    for (int b = 0; b < j.levels; ++b) {
+        for (int w = 0; w < members; ++w) {
+            if (w & ((1 << b) - 1)) continue;
+            u32* acc = s_acc.data() + (size_t)w * 2 * NTT_N;
+            const u32* in1 = b == 0 ? T + (size_t)(j.first + 2 * w + 1) * (2 * NTT_N) : s_acc.data() + (size_t)(w + ((1 << b) >> 1)) * 2 * NTT_N;
+            const fft::cplx* slot = trgsw + (size_t)(j.sel0 + b) * fft::trgsw_slot_cplx<G>();
+            ALL_LANES for (int e = 0; e < 32; ++e) S[e >> 4][(e >> 3) & 1][lane][e & 7] = {0.0, 0.0};
+            for (int r = 0; r < 2 * L; ++r) {
+                const int c = r >= L ? 1 : 0, lvl = r - c * L;
+                if (lvl == 0) ALL_LANES fft::cmux_diff16<G>(lane, in1 + c * NTT_N, acc + c * NTT_N, u[lane]);
+                ALL_LANES fft::digits8<G>(lvl, u[lane], a[lane]);
+                fft_forward_lf_wave(a, xb);
+                const u32 row_off = (u32)r * 4u * (u32)fft::M;
+                ALL_LANES
+                {
+                    const fft::Keys keys(slot, 0, lane);
+                    for (int q = 0; q < 8; ++q)
+                        for (int pc = 0; pc < 4; ++pc) fft::cmac<false>(S[pc >> 1][pc & 1][lane][q], a[lane][q], keys.at(row_off, pc, q));
+                }
+            }
+            for (int cc = 0; cc < 2; ++cc) {
+                fft_inverse2_wave(S[cc][0], S[cc][1], xb);
+                ALL_LANES
+                {
+                    const double e0 = fft::round_err8(S[cc][0][lane]), e1 = fft::round_err8(S[cc][1][lane]);
+                    g_fft_worst = std::max(g_fft_worst, std::max(e0, e1));
+                    fft::round16(S[cc][0][lane], lo[lane]);
+                }
+                ALL_LANES fft::acc_update16(lane, S[cc][1][lane], lo[lane], acc + cc * NTT_N);
+            }
+        }
+    }
+    ALL_LANES fft::cmux_store_acc(lane, s_acc.data(), T + (size_t)j.out * (2 * NTT_N));
+}
+
 // one inverse transform of one wave (kernels_fft.hpp::fft_inverse1)
 void fft_inverse1_wave(fft::cplx (*a)[8], fft::cplx* xb)
 {
@@ -1055,6 +1104,22 @@ int iyk_emul_cmux_rotate_chain(int set, uint32_t* trlwe, uint64_t rows, const do
     const fft::cplx* k = reinterpret_cast<const fft::cplx*>(trgsw_fft);
     if (set == 0) cmux_rotate_chain<fft::Gadget<3, 6>>(j, list.data(), k, trlwe);
     else cmux_rotate_chain<fft::Gadget<2, 10>>(j, list.data(), k, trlwe);
+    return 0;
+}
+/* cmux_fft.hpp::cmux_tree_kernel: ONE job — the 2^levels leaves T[first ..] halved `levels` times with selector slots sel0 .. sel0 +
+ * levels - 1, T[out] = the row left — in place on `rows` TRLWE rows.  set and trgsw_fft as for emu_cmux_fft; the rounding distances feed
+ * iyk_emul_fft_round_error like the chains'.  -1: unknown set, levels outside [1, 4] or an index outside its store (nothing is written). */
+int iyk_emul_cmux_tree(int set, uint32_t* trlwe, uint64_t rows, const double* trgsw_fft, uint64_t sels, int32_t sel0, int32_t levels,
+                       int32_t first, int32_t out)
+{
+    if (set != 0 && set != 1) return -1;
+    if (levels < 1 || levels > CMUX_TREE_MAX_LEVELS) return -1;
+    if (sel0 < 0 || (uint64_t)sel0 + (uint64_t)levels > sels) return -1;
+    if (first < 0 || (uint64_t)first + (1ull << levels) > rows || out < 0 || (uint64_t)out >= rows) return -1;
+    const CmuxTreeJob j{sel0, levels, first, out};
+    const fft::cplx* k = reinterpret_cast<const fft::cplx*>(trgsw_fft);
+    if (set == 0) cmux_tree<fft::Gadget<3, 6>>(j, k, trlwe);
+    else cmux_tree<fft::Gadget<2, 10>>(j, k, trlwe);
     return 0;
 }
 /* kernels.hpp::sample_extract_index_kernel for one TRLWE: N + 1 words of the TLWE lvl1 at coefficient index h < N */
@@ -1741,6 +1806,18 @@ int iyk_emul_check_cmux_rotate_chain_batch(uint64_t trgsw_slots, uint64_t trlwe_
 }
 /* dispatch::cmux_rotate_chain_grid */
 int64_t iyk_emul_cmux_rotate_chain_grid(int64_t count) { return (int64_t)dispatch::cmux_rotate_chain_grid((long)count); }
+/* list: the jobs {sel0, levels, first, out} */
+int iyk_emul_check_cmux_tree_batch(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* sel0, const int32_t* levels,
+                                   const int32_t* first, const int32_t* out, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    std::vector<CmuxTreeJob> jobs;
+    const args::Refusal r = args::cmux_tree_args(trgsw_slots, trlwe_slots, count, sel0, levels, first, out, jobs);
+    if (!r) o.list(jobs);
+    return o.finish(r);
+}
+/* dispatch::cmux_tree_grid */
+int64_t iyk_emul_cmux_tree_grid(int64_t count) { return (int64_t)dispatch::cmux_tree_grid((long)count); }
 int iyk_emul_check_trlwe_add_batch(uint64_t trlwe_slots, uint64_t count, const int32_t* a, const int32_t* b, const int32_t* out, IYK_CHECK_OUT)
 {
     IYK_CHECK_OUT_INIT;

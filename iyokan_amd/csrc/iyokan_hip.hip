@@ -655,7 +655,9 @@ int set_fft_attrs()
     if ((rc = set_lds(cmux_chain_kernel<GD, false>, BR_FFT_LDS_BYTES))) return rc;
     if ((rc = set_lds(cmux_chain_kernel<GD, true>, BR_FFT_LDS_BYTES))) return rc;
     if ((rc = set_lds(cmux_rotate_chain_kernel<GD, false>, BR_FFT_LDS_BYTES))) return rc;
-    return set_lds(cmux_rotate_chain_kernel<GD, true>, BR_FFT_LDS_BYTES);
+    if ((rc = set_lds(cmux_rotate_chain_kernel<GD, true>, BR_FFT_LDS_BYTES))) return rc;
+    if ((rc = set_lds(cmux_tree_kernel<GD, false>, BR_FFT_LDS_BYTES))) return rc;
+    return set_lds(cmux_tree_kernel<GD, true>, BR_FFT_LDS_BYTES);
 }
 int set_kernel_attrs(const iyk_params& p, bool use_fp, int split, bool* cb_lat_granted, bool* cb_fft_granted)
 {
@@ -2197,6 +2199,33 @@ int iyk_hip_cmux_rotate_chain_batch(iyk_hip_stream* st, const void* d_trgsw, uin
         hipLaunchKernelGGL(kern, dim3((unsigned)cmux_rotate_chain_grid((long)count)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s,
                            (const CmuxRotChainJob*)d[0], (int)count, (const CmuxRotStep*)d[1], (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c,
                            D.fft_err);
+        HIP_TRY(hipGetLastError());
+        return (int)IYK_OK;
+    });
+    if (rc) return rc;
+    return release_stage(st);
+    IYK_API_END
+}
+
+int iyk_hip_cmux_tree_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
+                            uint64_t count, const int32_t* sel0, const int32_t* levels, const int32_t* first, const int32_t* out)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_cmux_tree_batch")) return rc;
+    if (!st || !d_trgsw || !d_trlwe || !sel0 || !levels || !first || !out) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    std::vector<CmuxTreeJob> jobs;
+    if (const args::Refusal r = args::cmux_tree_args(trgsw_slots, trlwe_slots, count, sel0, levels, first, out, jobs)) return refuse(r);
+    char* d[1];
+    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxTreeJob)}}, d))) return rc;
+    const Device& D = G.devs[st->gpu];
+    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
+        typedef decltype(gd) GD;
+        auto kern = G.debug ? cmux_tree_kernel<GD, true> : cmux_tree_kernel<GD, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)cmux_tree_grid((long)count)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s,
+                           (const CmuxTreeJob*)d[0], (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
         HIP_TRY(hipGetLastError());
         return (int)IYK_OK;
     });

@@ -53,6 +53,12 @@ struct CmuxRotStep {
     int32_t sel, rot;
 };
 
+// A CMUX read tree of 2^levels leaves T[first ..]: level b < levels halves the candidates with selector slot sel0 + b — job i of a level is
+// the CMUX (in0 = candidate 2 i, in1 = candidate 2 i + 1) — and T[out] is the one row left (cmux_fft.hpp: cmux_tree_kernel)
+struct CmuxTreeJob {
+    int32_t sel0, levels, first, out;
+};
+
 // private key switch of lvl2 TLWE `in` into TRLWE row `out` with the key's function c (privks.hpp)
 struct PrivksJob {
     int32_t in, c, out;
@@ -69,9 +75,11 @@ struct CbJob {
 static_assert(sizeof(RotJob) == 20 && sizeof(KsJob) == 16 && sizeof(EwJob) == 12 && sizeof(TrlweAddJob) == 12, "job layout is the upload format");
 static_assert(sizeof(CmuxJob) == 20 && sizeof(CmuxChainJob) == 24 && sizeof(PrivksJob) == 12 && sizeof(CbJob) == 24, "job layout is the upload format");
 static_assert(sizeof(CmuxRotChainJob) == 16 && sizeof(CmuxRotStep) == 8, "job layout is the upload format");
+static_assert(sizeof(CmuxTreeJob) == 16, "job layout is the upload format");
 
 static constexpr int CMUX_CHAIN_MAX_STEPS = 32;       // the bits of CmuxChainJob::pattern
 static constexpr int CMUX_ROT_CHAIN_MAX_STEPS = 32;   // steps of one CmuxRotChainJob: count * 32 steps bound the step list's 32-bit index
+static constexpr int CMUX_TREE_MAX_LEVELS = 4;        // log2(2 BR_WAVES): level 0 of one CmuxTreeJob is one two-row CMUX per wave of a workgroup
 static constexpr uint32_t CB_MAX_N0 = 2047;           // n + 1 mod-switched words fit the LDS abar array of cb_rotate_kernel
 static constexpr uint32_t PRIVKS_MAX_N_IN = 1u << 16;
 static constexpr uint32_t ABAR_STRIDE = 1024;         // words per job in a stream's mod-switched rotation inputs (n + 1 <= 768 used)

@@ -43,7 +43,7 @@ EXPORTS = [
     "iyk_hip_trgsw_from_rows",
     "iyk_hip_bk2_key_create", "iyk_hip_bk2_key_upload", "iyk_hip_bk2_key_free", "iyk_hip_bk2_key_bytes", "iyk_hip_cb_rotate_batch",
     "iyk_hip_circuit_bootstrap_batch", "iyk_hip_cb_rotate_form", "iyk_hip_bk2_key_create_form", "iyk_hip_bk2_key_form",
-    "iyk_hip_cmux_rotate_chain_batch",
+    "iyk_hip_cmux_rotate_chain_batch", "iyk_hip_cmux_tree_batch",
 ]
 
 
@@ -99,6 +99,7 @@ def lib():
         L.iyk_hip_cmux_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p, _i32p]
         L.iyk_hip_cmux_chain_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _u32p, _i32p, _i32p, _i32p]
         L.iyk_hip_cmux_rotate_chain_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p, _i32p]
+        L.iyk_hip_cmux_tree_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p]
         L.iyk_hip_trlwe_add_batch.argtypes = [_vp, _vp, u64, u64, _i32p, _i32p, _i32p, ctypes.c_uint32]
         u32 = ctypes.c_uint32
         L.iyk_hip_privks_key_create.argtypes = [ctypes.c_int, u32, u32, u32, ctypes.POINTER(_vp)]
@@ -623,6 +624,18 @@ class Stream:
         p = lambda a: a.ctypes.data_as(_i32p)
         _check(lib().iyk_hip_cmux_rotate_chain_batch(self.h, trgsw.ptr, trgsw.slots, trlwe.ptr, trlwe.slots, len(steps), p(steps), p(sel),
                                                      p(rot), p(src), p(out)), "iyk_hip_cmux_rotate_chain_batch")
+
+    def cmux_tree_batch(self, trgsw, trlwe, sel0, levels, first, out):
+        """len(sel0) independent CMUX read trees on rows of a Trlwe store, asynchronous (up to four levels of the upper half of one memory
+        read per job): the 2^levels[g] leaves T[first[g] ..] are halved levels[g] times — level b takes selector slot sel0[g] + b, and job i
+        of a level is the CMUX (in0 = candidate 2 i, in1 = candidate 2 i + 1) — and T[out[g]] is the row left.  Word for word what
+        levels[g] dependent cmux_batch launches give; nothing but out is written.  A job may write over one of its own leaves and jobs
+        may share leaves; no out may be a leaf or the out of another job of the batch."""
+        sel0, levels, first, out = map(_i32, (sel0, levels, first, out))
+        assert len(sel0) == len(levels) == len(first) == len(out)
+        p = lambda a: a.ctypes.data_as(_i32p)
+        _check(lib().iyk_hip_cmux_tree_batch(self.h, trgsw.ptr, trgsw.slots, trlwe.ptr, trlwe.slots, len(sel0), p(sel0), p(levels),
+                                             p(first), p(out)), "iyk_hip_cmux_tree_batch")
 
     def trlwe_add_batch(self, trlwe, a, b, out, b0_offset=0):
         """T[out] = T[a] + T[b] mod 2^32 on rows of a Trlwe store, b0_offset added to coefficient 0 of the b polynomial (the tail of

@@ -168,10 +168,11 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
     (client.decrypt_ram_trlwe of the caller's keys) reads the result packet's RAM images out of Ram.cells().
     The 80-bit set is refused unless words_only=True: there the restatement of the circuit bootstrapping itself misreads ROM bits
     (DESIGN.md section 6d), so only words may be compared, never decryptions.
-    rom_fused=True: the rotate tail of every ROM read is ONE Stream.cmux_rotate_chain_batch (Rom.read(fused=True)): the same words."""
+    rom_fused=True: the rotate tail of every ROM read is ONE Stream.cmux_rotate_chain_batch (Rom.read(fused=True)): the same words.
+    tree_fused=True: the read tree of every ROM and RAM port is ONE Stream.cmux_tree_batch per four levels (fused_tree=True): the same words."""
 
     def __init__(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packet=None, decrypt_ram=None, words_only=False,
-                 rom_fused=False):
+                 rom_fused=False, tree_fused=False):
         from . import cmux, hip
         from .params import params_80bit
 
@@ -190,7 +191,7 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         be = executor.be
         self.stream, self.arena, self.ports = be.stream, be._arena, list(system.ports)
         self.bk2, self.privks_key, self.packet, self.decrypt_ram = bk2, privks_key, packet, decrypt_ram
-        self.rom_fused = bool(rom_fused)
+        self.rom_fused, self.tree_fused = bool(rom_fused), bool(tree_fused)
         N, l, per = int(p.N), int(p.l), int(p.trgsw_rows)
         widest = max(pt.addr_width for pt in self.ports)
         self.tlwe2 = hip.Tlwe2(hip.Bk2Key.N2, widest * l, self.stream.gpu_index)
@@ -217,9 +218,10 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         self.stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, self._slots(pt.addr), [1] * pt.addr_width, self.tlwe2,
                                             0, self.scratch, mem.trgsw, 0)
         if pt.kind == "rom":
-            mem.read(None, self.arena, self._slots(pt.rdata).reshape(1, -1), resident=True, fused=self.rom_fused)
+            mem.read(None, self.arena, self._slots(pt.rdata).reshape(1, -1), resident=True, fused=self.rom_fused,
+                     fused_tree=self.tree_fused)
         else:
-            mem.read_port(self.arena, self._slots(pt.rdata))
+            mem.read_port(self.arena, self._slots(pt.rdata), self.tree_fused)
 
     def _port_write(self, pt):
         self.mem[pt.name].write_port(self.arena, int(self._slots(pt.wren)[0]), self._slots(pt.wdata), self._slots(pt.rdata))
