@@ -563,6 +563,18 @@ int iyk_hip_resident_key_bytes(uint64_t* out);
 int iyk_hip_bk2_key_create_form(int gpu_index, uint32_t n, uint32_t l2, uint32_t Bgbit2, int form, void** out);
 int iyk_hip_bk2_key_form(const void* key, int* form_out);
 
+/* Order one stream behind another on the device: everything enqueued on `st` after this call starts only once everything enqueued on
+ * `other` BEFORE this call has finished.  An event is recorded on `other` and `st` waits for it; the host never blocks, and `other` is
+ * not held up.  The event is one of a few `st` owns from its creation to iyk_hip_stream_destroy, used round-robin — a wait keeps the
+ * record it was enqueued behind, so any number of waits may follow each other and nothing is created per call.  (A gate of
+ * iyk_hip_gate_host that is still parked in a coalesced batch is not yet enqueued on `other` and is not waited for.)
+ * What it is for: work that the next launches of one stream do not read — cmux.Ram's refresh of every cell — goes to a second stream
+ * and is ordered back in front of its first reader ("refresh aside").
+ * IYK_ERR_INVALID, with nothing enqueued on either stream and the reason in iyk_hip_last_error: a null stream, st == other, streams
+ * on different GPUs, streams of different replicas of one GPU (a replica's stores and keys are its own).  The check is
+ * args::stream_wait_args of csrc/batch_args.hpp.  No upstream counterpart: cuFHE's streams meet only on the host. */
+int iyk_hip_stream_wait_stream(iyk_hip_stream* st, iyk_hip_stream* other);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,12 +161,31 @@ def selectors_from_tlwe0(stream, bk2, privks_key, arena, addr_slots, tlwe2, firs
     selectors_from_tlwe2(stream, privks_key, tlwe2, first, len(addr_slots), trlwe_scratch, trgsw, first_slot)
 
 
+def _selector_store(trgsw, sel_base, need):
+    """Refuses (ValueError) a selector store and base slot that cannot hold `need` selectors; trgsw=None: the memory's own store, base 0."""
+    sel_base = int(sel_base)
+    if trgsw is None:
+        if sel_base != 0:
+            raise ValueError("sel_base needs the selector store it is a slot of (trgsw=...)")
+        return 0
+    if trgsw.slots < need:
+        raise ValueError(f"{need} selector slots needed, the store has {trgsw.slots}")
+    if sel_base < 0 or sel_base + need > trgsw.slots:
+        raise ValueError(f"selector slots {sel_base} .. {sel_base + need - 1} are outside the store's {trgsw.slots}")
+    return sel_base
+
+
 class Rom:
     """A ROM of TRLWE rows on one GPU.  read() runs rom_read_plan for R independent reads at once: the jobs of all reads at one
     level go into ONE cmux_batch, each read with its own scratch rows and its own addr_width selectors; then bit i of every read's
-    word is extracted at coefficient index i and key-switched into an arena slot."""
+    word is extracted at coefficient index i and key-switched into an arena slot.
+    trgsw, sel_base: a selector store the caller owns and the first of the addr_width * max_reads slots this ROM uses in it (read r, bit b
+    at sel_base + r * addr_width + b); every job list names those slots, uploads go there, and free() leaves the store alone.  Without
+    them the ROM allocates and frees a store of its own, slots from 0."""
 
-    def __init__(self, stream, data_trlwe, addr_width, log2_word_bits, max_reads=1):
+    sel_base, own_trgsw = 0, True   # of a ROM with a selector store of its own
+
+    def __init__(self, stream, data_trlwe, addr_width, log2_word_bits, max_reads=1, trgsw=None, sel_base=0):
         from . import hip
 
         p = hip.current_params()
@@ -180,8 +199,10 @@ class Rom:
         if data.shape[0] != self.layout.data_rows:
             raise ValueError(f"expected {self.layout.data_rows} TRLWE rows, got {data.shape[0]}")
         self.max_reads = int(max_reads)
+        self.sel_base = _selector_store(trgsw, sel_base, self.max_reads * self.addr_width)   # refused before anything is allocated
+        self.own_trgsw = trgsw is None
         self.trlwe = hip.Trlwe(self.layout.data_rows + self.max_reads * self.layout.scratch_rows, stream.gpu_index)
-        self.trgsw = hip.Trgsw(self.max_reads * self.addr_width, stream.gpu_index)
+        self.trgsw = hip.Trgsw(self.max_reads * self.addr_width, stream.gpu_index) if self.own_trgsw else trgsw
         self.trlwe.upload(stream, 0, data)
 
     def row(self, read, plan_row):
@@ -196,7 +217,7 @@ class Rom:
             cols = [[], [], [], [], []]
             for r in range(reads):
                 for j in jobs:
-                    vals = (r * self.addr_width + j.bit, self.row(r, j.in0), -1 if j.in1 < 0 else self.row(r, j.in1), j.rot,
+                    vals = (self.sel_base + r * self.addr_width + j.bit, self.row(r, j.in0), -1 if j.in1 < 0 else self.row(r, j.in1), j.rot,
                             self.row(r, j.out))
                     for c, v in zip(cols, vals):
                         c.append(v)
@@ -212,7 +233,7 @@ class Rom:
         steps, sel, rot, src, out = [], [], [], [], []
         for r in range(reads):
             steps.append(chain.steps)
-            sel.extend(r * self.addr_width + b for b in chain.bits)
+            sel.extend(self.sel_base + r * self.addr_width + b for b in chain.bits)
             rot.extend(chain.rots)
             src.append(self.row(r, chain.src))
             out.append(self.row(r, chain.out))
@@ -223,14 +244,15 @@ class Rom:
         group of rom_tree_jobs: they replace the first sum(levels) tuples of launches(reads)."""
         out = []
         for jobs, _ in rom_tree_jobs(self.plan):
-            rows = [(r * self.addr_width + j.bit0, j.levels, self.row(r, j.first), self.row(r, j.out)) for r in range(reads) for j in jobs]
+            rows = [(self.sel_base + r * self.addr_width + j.bit0, j.levels, self.row(r, j.first), self.row(r, j.out))
+                    for r in range(reads) for j in jobs]
             out.append(tuple(zip(*rows)))
         return out
 
     def read(self, addr_trgsw, arena, out_slots, resident=False, fused=False, fused_tree=False):
         """addr_trgsw: u32 [R][addr_width][(k+1) l][k+1][N] (client.encrypt_trgsw of every read's address bits, bit 0 first);
         out_slots: [R][word_bits] arena slots.  Asynchronous on the stream.  resident=True: the selectors are in self.trgsw already
-        (slot read * addr_width + bit, e.g. from selectors_from_tlwe2 on this stream): addr_trgsw is ignored and nothing is uploaded.
+        (slot sel_base + read * addr_width + bit, e.g. from selectors_from_tlwe2 on this stream): addr_trgsw is ignored and nothing is uploaded.
         fused=True sends the rotate tail of all reads as ONE cmux_rotate_chain_batch instead of one cmux_batch per step, fused_tree=True
         the upper tree as ONE cmux_tree_batch per four levels instead of one cmux_batch per level: the same words either way."""
         if resident:
@@ -243,7 +265,7 @@ class Rom:
         if reads > self.max_reads:
             raise ValueError(f"{reads} reads, sized for {self.max_reads}")
         if not resident:
-            self.trgsw.upload(self.stream, 0, sel)
+            self.trgsw.upload(self.stream, self.sel_base, sel)
         upper, chain = self.launches_fused(reads) if fused else (self.launches(reads), None)
         if fused_tree:
             trees = self.tree_launches(reads)
@@ -260,7 +282,8 @@ class Rom:
 
     def free(self):
         self.trlwe.free()
-        self.trgsw.free()
+        if self.own_trgsw:
+            self.trgsw.free()
 
 
 # ---- RAM ----------------------------------------------------------------------------------------------------------------------
@@ -305,9 +328,27 @@ class Ram:
     """A RAM of 2^addr_width words of data_width bits on one GPU, one TRLWE per bit (the bit at coefficient 0), as the reference
     keeps it.  One Trlwe store holds the data_width bit planes of 2^addr_width cell rows, then per plane the read tree's scratch
     rows and two rows for MUXwoSE, then one accumulator row per cell for the unfused write-back; one Trgsw store holds the
-    addr_width selectors of the current clock; a private arena holds the TLWEs between the write-back and the refresh."""
+    addr_width selectors of the current clock; a private arena holds the TLWEs between the write-back and the refresh.
+    trgsw, sel_base: a selector store the caller owns and the first of the addr_width slots this RAM uses in it (bit b at sel_base + b);
+    every job list names those slots, uploads go there, and free() leaves the store alone.  Without them the RAM allocates and frees a
+    store of its own, slots from 0.
 
-    def __init__(self, stream, cells_trlwe, addr_width, data_width):
+    Refresh aside (write_port(refresh_stream=...)).  The refresh of every cell — steps 5 and 6 — is what the NEXT read tree needs and
+    nothing in front of it, so it may run on a second stream beside whatever the main stream does until then.  The two sides of the wait:
+        refresh side   the cell rows (read by the extraction, written by the rotation back), the RAM's private arena, and the
+                       refresh stream's own rotation / key-switch scratch
+        main side      between write_port and the next read_port a staged engine runs the DFF copies, the gates of the next clock's
+                       first stage and its circuit bootstrapping: the engine's arena, its lvl2 store, its TRLWE scratch rows and the
+                       selector store
+    The two lists share nothing; that is the whole argument.  It is held at the edges by three waits on the device, none on the host:
+    the refresh stream waits for the main stream behind the chain (the extraction reads what the chain wrote), and read_port, write_port,
+    cells() and free() — every path that reads or overwrites a cell row or the private arena — first make the main stream wait for a
+    pending refresh (order_refresh()).  Whoever else touches the cell rows on the main stream (an upload into them) calls
+    order_refresh() first.  The words are those of the one-stream form.  Measured on one MI355X: DESIGN.md section 6e."""
+
+    sel_base, own_trgsw, pending_refresh = 0, True, None   # of a RAM with a selector store of its own and its refresh on its own stream
+
+    def __init__(self, stream, cells_trlwe, addr_width, data_width, trgsw=None, sel_base=0):
         from . import hip
 
         p = hip.current_params()
@@ -321,8 +362,11 @@ class Ram:
         self.ncells = self.data_width * C
         self.plane_scratch = self.layout.scratch_rows + 2
         self.acc0 = self.ncells + self.data_width * self.plane_scratch
+        self.sel_base = _selector_store(trgsw, sel_base, self.addr_width)   # refused before anything is allocated
+        self.own_trgsw = trgsw is None
+        self.pending_refresh = None   # the stream a refresh was sent to that the main stream is not ordered behind yet
         self.trlwe = hip.Trlwe(self.acc0 + self.ncells, stream.gpu_index)
-        self.trgsw = hip.Trgsw(self.addr_width, stream.gpu_index)
+        self.trgsw = hip.Trgsw(self.addr_width, stream.gpu_index) if self.own_trgsw else trgsw
         self.arena = hip.Arena(self.ncells, stream.gpu_index)
         self.trlwe.upload(stream, 0, data)
 
@@ -340,7 +384,8 @@ class Ram:
         """The cmux_batch argument lists (sel, in0, in1, rot, out) of the read tree, all planes' jobs of a level in one launch."""
         out = []
         for jobs in self.plan:
-            rows = [(j.bit, self.row(d, j.in0), self.row(d, j.in1), 0, self.row(d, j.out)) for d in range(self.data_width) for j in jobs]
+            rows = [(self.sel_base + j.bit, self.row(d, j.in0), self.row(d, j.in1), 0, self.row(d, j.out))
+                    for d in range(self.data_width) for j in jobs]
             out.append(tuple(zip(*rows)))
         return out
 
@@ -349,14 +394,14 @@ class Ram:
         one launch: together they replace read_launches()."""
         out = []
         for jobs, _ in rom_tree_jobs(self.plan):
-            rows = [(j.bit0, j.levels, self.row(d, j.first), self.row(d, j.out)) for d in range(self.data_width) for j in jobs]
+            rows = [(self.sel_base + j.bit0, j.levels, self.row(d, j.first), self.row(d, j.out)) for d in range(self.data_width) for j in jobs]
             out.append(tuple(zip(*rows)))
         return out
 
     def write_jobs(self):
         """One ChainJob per cell of every plane, in place on the cell rows, from the plane's written TRLWE."""
         C = self.cells_per_plane
-        return [j for d in range(self.data_width) for j in ram_write_jobs(self.addr_width, self.mux_rows(d)[0], d * C)]
+        return [j for d in range(self.data_width) for j in ram_write_jobs(self.addr_width, self.mux_rows(d)[0], d * C, self.sel_base)]
 
     def clock(self, addr_trgsw, arena, wren_slot, wdata_slots, rdata_slots, fused=True, resident=False, fused_tree=False):
         """One clock of the reference's RAM network, asynchronous on the stream.  addr_trgsw: u32 [addr_width][(k+1) l][k+1][N]
@@ -367,7 +412,8 @@ class Ram:
         fused_tree=True sends the read tree as one cmux_tree_batch per four levels (read_port): the same words."""
         self._slots(wdata_slots, rdata_slots)   # both refused before anything is uploaded or enqueued
         if not resident:
-            self.trgsw.upload(self.stream, 0, np.ascontiguousarray(addr_trgsw, dtype=np.uint32).reshape(self.addr_width, self.trgsw.words))
+            self.trgsw.upload(self.stream, self.sel_base,
+                              np.ascontiguousarray(addr_trgsw, dtype=np.uint32).reshape(self.addr_width, self.trgsw.words))
         self.read_port(arena, rdata_slots, fused_tree)
         self.write_port(arena, wren_slot, wdata_slots, rdata_slots, fused)
 
@@ -377,6 +423,13 @@ class Ram:
             raise ValueError(f"expected {self.data_width} wdata and {self.data_width} rdata slots")
         return out
 
+    def order_refresh(self):
+        """Orders the main stream behind a refresh that is pending on another stream (write_port(refresh_stream=...)): one wait on the
+        device, nothing on the host.  Nothing pending: nothing enqueued."""
+        if self.pending_refresh is not None:
+            self.stream.wait_stream(self.pending_refresh)
+            self.pending_refresh = None
+
     def read_port(self, arena, rdata_slots, fused_tree=False):
         """The read half of a clock (steps 1, 2: RAMUX, SEI(0) + key switch -> rdata) with the selectors that are resident in
         self.trgsw.  Inside a netlist rdata feeds the logic that computes wren / wdata of the same clock, so the two halves are
@@ -384,6 +437,7 @@ class Ram:
         fused_tree=True sends the tree as ONE cmux_tree_batch per four levels instead of one cmux_batch per level: the same words."""
         st, w = self.stream, self.data_width
         rdata_slots, = self._slots(rdata_slots)
+        self.order_refresh()   # the tree reads the cell rows
         # 1, 2: RAMUX, SEI(0) + key switch -> rdata
         if fused_tree:
             for args in self.tree_launches():
@@ -394,11 +448,17 @@ class Ram:
         result = [self.row(d, self.layout.result) for d in range(w)]
         st.sample_extract_index_keyswitch_batch(self.trlwe, result, np.zeros(w, dtype=np.int32), rdata_slots, arena)
 
-    def write_port(self, arena, wren_slot, wdata_slots, rdata_slots, fused=True):
+    def write_port(self, arena, wren_slot, wdata_slots, rdata_slots, fused=True, refresh_stream=None):
         """The write half of a clock (steps 3 - 6: MUXwoSE, the chain of every cell, extraction, refresh) with the same resident
-        selectors; rdata_slots still hold what read_port put there."""
+        selectors; rdata_slots still hold what read_port put there.
+        refresh_stream: a second hip.Stream of the same GPU.  Steps 3 and 4 stay on self.stream, refresh_stream waits for them on the
+        device, steps 5 and 6 go to refresh_stream, and the RAM remembers that its refresh is pending there (the class docstring has the
+        buffers of either side).  The same words."""
         st, w = self.stream, self.data_width
         wdata_slots, rdata_slots = self._slots(wdata_slots, rdata_slots)
+        if refresh_stream is st:
+            raise ValueError("refresh_stream is the RAM's own stream: leave it out")
+        self.order_refresh()   # the chain reads and writes the cell rows
         # 3: HomMUXwoSE: BlindRotate(wren + wdata - mu) + BlindRotate(-wren + rdata - mu), + mu at coefficient 0 of b
         m1, m0 = zip(*(self.mux_rows(d) for d in range(w)))
         minus_mu = np.full(2 * w, (-self.mu) & 0xFFFFFFFF, dtype=np.uint32)
@@ -415,15 +475,22 @@ class Ram:
                 st.cmux_batch(self.trgsw, self.trlwe, *zip(*(c[s] for c in steps)))
         # 5, 6: SEI(0) + key switch of every cell, then the blind rotation back into the cell's row
         cells = np.arange(self.ncells, dtype=np.int32)
+        if refresh_stream is not None:
+            refresh_stream.wait_stream(st)
+            st = refresh_stream
+            self.pending_refresh = refresh_stream
         st.sample_extract_index_keyswitch_batch(self.trlwe, cells, np.zeros(self.ncells, dtype=np.int32), cells, self.arena)
         st.bootstrap_trlwe_batch(self.arena, cells, np.full(self.ncells, -1), np.ones(self.ncells), np.zeros(self.ncells),
                                  np.zeros(self.ncells, dtype=np.uint32), self.trlwe.ptr, trlwe_slots=self.trlwe.slots, trlwe_out=cells)
 
     def cells(self):
-        """The cell rows: u32 [data_width][2^addr_width][2N] (synchronises the stream)."""
+        """The cell rows: u32 [data_width][2^addr_width][2N] (synchronises the stream, behind a pending refresh)."""
+        self.order_refresh()
         return self.trlwe.download(self.stream, 0, self.ncells).reshape(self.data_width, self.cells_per_plane, 2 * self.N)
 
     def free(self):
+        self.order_refresh()   # nothing is freed under a refresh that still runs
         self.trlwe.free()
-        self.trgsw.free()
+        if self.own_trgsw:
+            self.trgsw.free()
         self.arena.free()

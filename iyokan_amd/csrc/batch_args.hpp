@@ -405,5 +405,21 @@ inline Refusal check_circuit_bootstrap_batch(const iyk_params& p, uint32_t bk2_n
     return check_trgsw_from_rows(p, trgsw_slots, trlwe_slots, bits, o.sel.data(), o.rows.data());
 }
 
+// ---- streams ----------------------------------------------------------------------------------------------------------------------
+
+// iyk_hip_stream_wait_stream(st, other): st waits for what `other` holds now.  *_replica: iyk_hip_stream::gpu, the index into
+// iyk_hip_init's device list; *_ordinal: the HIP device behind it (two replicas may share one) — the caller reads both from non-null
+// handles only and passes anything for a null one.  Replicas are told apart even on one device: a replica's stores, keys and transform
+// constants are its own, and nothing one replica enqueues reads another's.  Not named check_*, for cmux_rotate_chain_args' reason;
+// tests/test_cmux_stage_cb.py holds every refusal below.
+inline Refusal stream_wait_args(const void* st, const void* other, int st_replica, int other_replica, int st_ordinal, int other_ordinal)
+{
+    if (!st || !other) return invalid("null stream");
+    if (st == other) return invalid("a stream cannot wait for itself");
+    if (st_ordinal != other_ordinal) return invalid("the two streams are on different GPUs");
+    if (st_replica != other_replica) return invalid("the two streams belong to different replicas");
+    return ACCEPT;
+}
+
 }  // namespace args
 }  // namespace iyk

@@ -1862,4 +1862,11 @@ int iyk_emul_check_circuit_bootstrap_batch(const iyk_params* p, uint32_t bk2_n, 
     if (!r) o.list(l.rot), o.list(l.privks), o.list(l.rows), o.list(l.sel);
     return o.finish(r);
 }
+/* args::stream_wait_args; st, other: the handles as integers (0 = null).  No job list. */
+int iyk_emul_stream_wait_args(uint64_t st, uint64_t other, int st_replica, int other_replica, int st_ordinal, int other_ordinal, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    return o.finish(args::stream_wait_args((const void*)(uintptr_t)st, (const void*)(uintptr_t)other, st_replica, other_replica, st_ordinal,
+                                           other_ordinal));
+}
 }

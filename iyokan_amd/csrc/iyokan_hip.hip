@@ -194,6 +194,9 @@ struct Global {
 // Eight, not two, since round 4: in an in-process multi-GPU run every destination stream takes one slot per SOURCE replica and
 // frontier (iyk_hip_arena_sync_slots_multi), and with two slots the host blocked from the third replica on.
 constexpr int STAGE_RING = 8;
+// Events per stream for iyk_hip_stream_wait_stream.  A wait holds the record it was enqueued behind, so recording an event again does
+// not disturb the waits already enqueued on it; four only keeps neighbouring waits on events of their own.
+constexpr int WAIT_RING = 4;
 
 struct iyk_hip_stream {
     int gpu = 0;
@@ -207,6 +210,8 @@ struct iyk_hip_stream {
     int stage_sel = 0;
     hipEvent_t stage_free[STAGE_RING] = {};  // work reading slot k done
     hipEvent_t xfer = nullptr, xfer2 = nullptr;  // cross-stream hand-offs of iyk_hip_arena_sync_slots
+    hipEvent_t wait_ev[WAIT_RING] = {};  // iyk_hip_stream_wait_stream: recorded on the OTHER stream, waited for by this one, round-robin
+    int wait_sel = 0;
     // blind-rotation outputs (TLWE lvl1), one row per rotation job
     u32* d_sel = nullptr;   // iyk_hip_trgsw_from_rows: the gathered torus rows of the selectors of one call, sel_cap selectors
     size_t sel_cap = 0;
@@ -724,6 +729,8 @@ void destroy_stream_resources(iyk_hip_stream* st)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : {st->xfer, st->xfer2})
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : st->wait_ev)
+        if (e) (void)hipEventDestroy(e);
     if (st->log_on) {
         for (hipEvent_t e : st->log_events) (void)hipEventDestroy(e);
     }
@@ -936,10 +943,11 @@ int stream_new(int gpu_index, void* wrap, bool do_wrap, iyk_hip_stream** out)
         e = hipStreamCreateWithFlags(&st->s, hipStreamNonBlocking);
         st->owned = (e == hipSuccess);
     }
-    hipEvent_t* plain[STAGE_RING + 2];
+    hipEvent_t* plain[STAGE_RING + 2 + WAIT_RING];
     for (int k = 0; k < STAGE_RING; ++k) plain[k] = &st->stage_free[k];
     plain[STAGE_RING] = &st->xfer;
     plain[STAGE_RING + 1] = &st->xfer2;
+    for (int k = 0; k < WAIT_RING; ++k) plain[STAGE_RING + 2 + k] = &st->wait_ev[k];
     for (hipEvent_t* ev : plain)
         if (e == hipSuccess) {
             what = "hipEventCreateWithFlags";
@@ -1415,6 +1423,24 @@ int iyk_hip_stream_sync(iyk_hip_stream* st)
     }
     HIP_TRY(hipStreamSynchronize(st->s));
     deliver_gate_result(st);
+    return IYK_OK;
+    IYK_API_END
+}
+
+int iyk_hip_stream_wait_stream(iyk_hip_stream* st, iyk_hip_stream* other)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    const int nd = (int)G.devs.size();
+    auto ordinal = [&](const iyk_hip_stream* s) { return s && s->gpu >= 0 && s->gpu < nd ? G.devs[s->gpu].ordinal : -1; };
+    if (const args::Refusal r = args::stream_wait_args(st, other, st ? st->gpu : -1, other ? other->gpu : -1, ordinal(st), ordinal(other)))
+        return refuse(r);
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    hipEvent_t ev = st->wait_ev[st->wait_sel];
+    st->wait_sel = (st->wait_sel + 1) % WAIT_RING;
+    HIP_TRY(hipEventRecord(ev, other->s));
+    HIP_TRY(hipStreamWaitEvent(st->s, ev, 0));
     return IYK_OK;
     IYK_API_END
 }

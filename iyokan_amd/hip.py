@@ -43,7 +43,7 @@ EXPORTS = [
     "iyk_hip_trgsw_from_rows",
     "iyk_hip_bk2_key_create", "iyk_hip_bk2_key_upload", "iyk_hip_bk2_key_free", "iyk_hip_bk2_key_bytes", "iyk_hip_cb_rotate_batch",
     "iyk_hip_circuit_bootstrap_batch", "iyk_hip_cb_rotate_form", "iyk_hip_bk2_key_create_form", "iyk_hip_bk2_key_form",
-    "iyk_hip_cmux_rotate_chain_batch", "iyk_hip_cmux_tree_batch",
+    "iyk_hip_cmux_rotate_chain_batch", "iyk_hip_cmux_tree_batch", "iyk_hip_stream_wait_stream",
 ]
 
 
@@ -71,6 +71,7 @@ def lib():
         L.iyk_hip_stream_wrap.argtypes = [ctypes.c_int, _vp, ctypes.POINTER(_vp)]
         for f in ("iyk_hip_stream_destroy", "iyk_hip_stream_query", "iyk_hip_stream_sync", "iyk_hip_stream_gpu"):
             getattr(L, f).argtypes = [_vp]
+        L.iyk_hip_stream_wait_stream.argtypes = [_vp, _vp]
         u64 = ctypes.c_uint64
         L.iyk_hip_arena_alloc.argtypes = [ctypes.c_int, u64, ctypes.POINTER(_vp)]
         L.iyk_hip_arena_free.argtypes = [ctypes.c_int, _vp]
@@ -473,6 +474,12 @@ class Stream:
 
     def sync(self):
         _check(lib().iyk_hip_stream_sync(self.h), "iyk_hip_stream_sync")
+
+    def wait_stream(self, other):
+        """What is enqueued on this stream from now on starts once everything enqueued on `other` (a Stream of the same GPU and
+        replica) so far has finished: an event recorded there, waited for here, on the device.  The host does not block.  A refusal
+        (IykHipError: the same stream, another GPU or replica, a destroyed stream) enqueues nothing."""
+        _check(lib().iyk_hip_stream_wait_stream(self.h, other.h), "iyk_hip_stream_wait_stream")
 
     def upload(self, arena, first_slot, host):
         host = np.ascontiguousarray(host, dtype=np.uint32).reshape(-1, arena.n1)

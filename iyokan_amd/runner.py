@@ -169,10 +169,19 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
     The 80-bit set is refused unless words_only=True: there the restatement of the circuit bootstrapping itself misreads ROM bits
     (DESIGN.md section 6d), so only words may be compared, never decryptions.
     rom_fused=True: the rotate tail of every ROM read is ONE Stream.cmux_rotate_chain_batch (Rom.read(fused=True)): the same words.
-    tree_fused=True: the read tree of every ROM and RAM port is ONE Stream.cmux_tree_batch per four levels (fused_tree=True): the same words."""
+    tree_fused=True: the read tree of every ROM and RAM port is ONE Stream.cmux_tree_batch per four levels (fused_tree=True): the same words.
+    stage_cb=True: ONE Stream.circuit_bootstrap_batch per STAGE instead of one per port.  The engine owns one selector store; every port
+    has its base slot in it (cmux.Rom / cmux.Ram(trgsw=, sel_base=)), the ports of a stage next to each other in port order, so the
+    stage's batch takes the concatenated address slots of its ports and writes the selectors from the stage's first base slot on.  The
+    lvl2 store and the TRLWE scratch are sized for the widest stage.  A rotation batch costs the same up to 256 rotations
+    (DESIGN.md section 6d), so every further port of a stage is free.  The same words.
+    refresh_aside=True: every RAM's refresh runs on ONE second stream of the engine (Ram.write_port(refresh_stream=...), whose class
+    docstring has the argument), beside the next clock's DFF copies, first-stage gates and circuit bootstrapping; each RAM orders itself
+    back in front of its next read, write, cells() or free(), and load_ram in front of its upload.  The same words.
+    Both are off by default; DESIGN.md section 6e has what either measured."""
 
     def __init__(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packet=None, decrypt_ram=None, words_only=False,
-                 rom_fused=False, tree_fused=False):
+                 rom_fused=False, tree_fused=False, stage_cb=False, refresh_aside=False):
         from . import cmux, hip
         from .params import params_80bit
 
@@ -191,23 +200,63 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         be = executor.be
         self.stream, self.arena, self.ports = be.stream, be._arena, list(system.ports)
         self.bk2, self.privks_key, self.packet, self.decrypt_ram = bk2, privks_key, packet, decrypt_ram
-        self.rom_fused, self.tree_fused = bool(rom_fused), bool(tree_fused)
+        self.rom_fused, self.tree_fused, self.stage_cb = bool(rom_fused), bool(tree_fused), bool(stage_cb)
         N, l, per = int(p.N), int(p.l), int(p.trgsw_rows)
-        widest = max(pt.addr_width for pt in self.ports)
+        widest = self._cb_bits()
         self.tlwe2 = hip.Tlwe2(hip.Bk2Key.N2, widest * l, self.stream.gpu_index)
         self.scratch = hip.Trlwe(widest * per, self.stream.gpu_index)
+        self.sel_base = self._assign_bases() if self.stage_cb else {}
+        self.trgsw = hip.Trgsw(sum(pt.addr_width for pt in self.ports), self.stream.gpu_index) if self.stage_cb else None
+        self.refresh_stream = hip.Stream(self.stream.gpu_index) if refresh_aside else None   # one per engine, whatever the number of RAMs
         self.mem = {}
         for pt in self.ports:
+            shared = {"trgsw": self.trgsw, "sel_base": self.sel_base[pt.name]} if self.stage_cb else {}
             if pt.kind == "rom":
                 log2w = pt.data_width.bit_length() - 1
                 if 1 << log2w != pt.data_width or pt.data_width > N:
                     raise ValueError(f"ROM {pt.name!r}: a word of {pt.data_width} bits is no power of two up to N")
                 rows = cmux.rom_layout(pt.addr_width, log2w, N).data_rows
-                self.mem[pt.name] = cmux.Rom(self.stream, np.zeros((rows, 2 * N), dtype=np.uint32), pt.addr_width, log2w)
+                self.mem[pt.name] = cmux.Rom(self.stream, np.zeros((rows, 2 * N), dtype=np.uint32), pt.addr_width, log2w, **shared)
             else:
                 zero = np.zeros((pt.data_width << pt.addr_width, 2 * N), dtype=np.uint32)
                 zero[:, N] = (-int(p.mu)) & 0xFFFFFFFF          # trivial TRLWEs of bit 0, as the DFFs start as trivial 0
-                self.mem[pt.name] = cmux.Ram(self.stream, zero, pt.addr_width, pt.data_width)
+                self.mem[pt.name] = cmux.Ram(self.stream, zero, pt.addr_width, pt.data_width, **shared)
+
+    def _stage_ports(self, s):
+        """The ports of stage s in the order their address bits are concatenated in the stage's batch: port order."""
+        return [pt for pt in self.ports if pt.stage == s]
+
+    def _cb_bits(self):
+        """Address bits of the widest circuit bootstrapping batch: the widest stage with stage_cb, else the widest port."""
+        if not self.stage_cb:
+            return max(pt.addr_width for pt in self.ports)
+        return max(sum(pt.addr_width for pt in self.ports if pt.stage == s) for s in {pt.stage for pt in self.ports})
+
+    def _assign_bases(self):
+        """{port name: first selector slot}: stage by stage, inside a stage in port order, a ROM and a RAM addr_width slots each (the
+        engine reads one word per clock) — the ports of a stage are contiguous, in the order of _stage_ports."""
+        bases, nxt = {}, 0
+        for s in sorted({pt.stage for pt in self.ports}):
+            for pt in self.ports:
+                if pt.stage == s:
+                    bases[pt.name] = nxt
+                    nxt += pt.addr_width
+        return bases
+
+    def _stage_first_slot(self, pts):
+        return self.sel_base[pts[0].name]
+
+    def _reads(self, s):
+        if not self.stage_cb:
+            return StagedPorts._reads(self, s)
+        pts = self._stage_ports(s)
+        if not pts:
+            return
+        addr = np.concatenate([self._slots(pt.addr) for pt in pts])
+        self.stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, addr, [1] * len(addr), self.tlwe2, 0, self.scratch,
+                                            self.trgsw, self._stage_first_slot(pts))
+        for pt in pts:
+            self._port_tree(pt)
 
     def _slots(self, nodes):
         slot = self.ex.plan.slot
@@ -217,6 +266,10 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         mem = self.mem[pt.name]
         self.stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, self._slots(pt.addr), [1] * pt.addr_width, self.tlwe2,
                                             0, self.scratch, mem.trgsw, 0)
+        self._port_tree(pt)
+
+    def _port_tree(self, pt):
+        mem = self.mem[pt.name]
         if pt.kind == "rom":
             mem.read(None, self.arena, self._slots(pt.rdata).reshape(1, -1), resident=True, fused=self.rom_fused,
                      fused_tree=self.tree_fused)
@@ -224,7 +277,8 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
             mem.read_port(self.arena, self._slots(pt.rdata), self.tree_fused)
 
     def _port_write(self, pt):
-        self.mem[pt.name].write_port(self.arena, int(self._slots(pt.wren)[0]), self._slots(pt.wdata), self._slots(pt.rdata))
+        aside = {} if self.refresh_stream is None else {"refresh_stream": self.refresh_stream}
+        self.mem[pt.name].write_port(self.arena, int(self._slots(pt.wren)[0]), self._slots(pt.wdata), self._slots(pt.rdata), **aside)
 
     def _rows(self, table, name):
         if self.packet is None:
@@ -245,6 +299,7 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
             rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 2 * ram.N)
             if rows.shape[0] != ram.ncells:
                 raise ValueError("Invalid request packet: wrong length of RAM")
+            ram.order_refresh()   # the upload overwrites the cell rows on the main stream
             # the packet's order is address * width + bit, the store's one plane of 2^addr_width cells per bit
             ram.trlwe.upload(self.stream, 0, rows.reshape(ram.cells_per_plane, ram.data_width, -1).transpose(1, 0, 2))
 
@@ -261,6 +316,11 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
     def free(self):
         for m in self.mem.values():
             m.free()
+        if self.trgsw is not None:
+            self.trgsw.free()
+        if self.refresh_stream is not None:
+            self.refresh_stream.destroy()
+            self.refresh_stream = None
         self.tlwe2.free()
         self.scratch.free()
 
