@@ -198,6 +198,21 @@ int iyk_hip_gate_batch(iyk_hip_stream* st, uint32_t* d_arena, uint64_t arena_slo
                        const int32_t* ops, const int32_t* in0, const int32_t* in1, const int32_t* in2,
                        const int32_t* out);
 
+/* The same gates on `lanes` copies of one circuit's arena image at once: K request packets of one circuit under one evaluation
+ * key.  Lane r is the slots [r * lane_stride, (r + 1) * lane_stride) of the arena; the descriptors are those of ONE lane, every
+ * index in [0, lane_stride), and stand for gate g of every lane, each lane at its own offset.  One lane's job lists are staged,
+ * a kernel writes the lists of all lanes on the device (csrc/lane_jobs.hpp), and the launches of
+ * iyk_hip_gate_batch run them as ONE batch of count * lanes gates: the kernels and launch shapes a flat batch of that many gates gets,
+ * the same words per lane as iyk_hip_gate_batch on that lane alone.  Lanes cannot touch each other: every index a lane's gates read
+ * or write lies in the lane's own slots.  Slots of a lane that no gate writes, and slots behind the last lane, are not touched.
+ * Checked before anything is staged (IYK_ERR_INVALID, nothing enqueued): everything iyk_hip_gate_batch checks, with lane_stride in
+ * the place of arena_slots; lanes and lane_stride not 0; lanes * lane_stride <= arena_slots and <= 2^31; count * lanes <= 2^30;
+ * at most 2^31 - 1 rotations.  IYK_HIP_DEBUG=1 verifies the independence contract on one lane, which is every lane's.
+ * lanes == 1 enqueues exactly what iyk_hip_gate_batch enqueues. */
+int iyk_hip_gate_batch_lanes(iyk_hip_stream* st, uint32_t* d_arena, uint64_t arena_slots, uint64_t count,
+                             const int32_t* ops, const int32_t* in0, const int32_t* in1, const int32_t* in2,
+                             const int32_t* out, uint64_t lanes, uint64_t lane_stride);
+
 /* One gate on HOST ciphertexts, same shape as cufhe::Nand(out, in0, in1, st): H2D of the
  * inputs, kernels, D2H of the result, all ordered on `st`; poll with iyk_hip_stream_query.
  * The inputs are copied before the call returns.  `out` must stay valid until the stream is idle and is WRITTEN when

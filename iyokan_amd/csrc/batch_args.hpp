@@ -145,6 +145,32 @@ inline Refusal check_gate_batch(const iyk_params& p, bool debug, uint64_t arena_
     return ACCEPT;
 }
 
+// iyk_hip_gate_batch_lanes: `lanes` copies of one circuit's arena image in one arena, lane r in slots [r * lane_stride, (r + 1) *
+// lane_stride); the descriptors are ONE lane's and stand for every lane, each at its own offset (lane_jobs.hpp).  The lists built are
+// those of ONE lane: check_gate_batch with lane_stride in the place of arena_slots, so every index of a job lies inside one lane — and
+// that is the whole proof that lanes do not touch each other, and why the debug independence check stays O(count): what holds inside
+// lane 0 holds inside lane r, shifted.  What the expansion multiplies is bounded here, before anything is staged: slots (an index
+// is an int32_t), jobs, rotation rows.  A refusal leaves the three lists empty.
+// Not named check_*, for cmux_rotate_chain_args' reason below; tests/test_lane_jobs.py holds every refusal.
+inline Refusal gate_batch_lanes_args(const iyk_params& p, bool debug, uint64_t arena_slots, uint64_t count, const int32_t* ops, const int32_t* in0,
+                                     const int32_t* in1, const int32_t* in2, const int32_t* out, uint64_t lanes, uint64_t lane_stride,
+                                     std::vector<RotJob>& rot, std::vector<KsJob>& ks, std::vector<EwJob>& ew)
+{
+    auto checked = [&]() -> Refusal {
+        if (lanes == 0) return invalid("lanes is zero");
+        if (lane_stride == 0) return invalid("lane stride is zero");
+        if (lanes > arena_slots / lane_stride) return invalid("lanes x lane stride slots do not fit the arena");   // no product: lanes may be 2^40
+        if (lanes * lane_stride > (1ull << 31)) return invalid("lanes x lane stride beyond the 2^31 slots an index can name");
+        if (count > MAX_GATE_BATCH || lanes > MAX_GATE_BATCH || count * lanes > MAX_GATE_BATCH) return invalid("batch too large: count x lanes");
+        if (Refusal r = check_gate_batch(p, debug, lane_stride, count, ops, in0, in1, in2, out, rot, ks, ew)) return r;
+        if ((uint64_t)rot.size() * lanes > (uint64_t)INT32_MAX) return invalid("batch too large: more than 2^31 - 1 rotations");
+        return ACCEPT;
+    };
+    const Refusal r = checked();
+    if (r) rot.clear(), ks.clear(), ew.clear();
+    return r;
+}
+
 // rotate_only, the body of iyk_hip_blind_rotate_batch (out_index null, out_rows 0) and iyk_hip_bootstrap_trlwe_batch
 inline Refusal check_rotate_only(uint64_t arena_slots, uint64_t count, const int32_t* ia, const int32_t* ib, const int32_t* sa, const int32_t* sb,
                                  const uint32_t* off, uint64_t out_rows, const int32_t* out_index, std::vector<RotJob>& rot)

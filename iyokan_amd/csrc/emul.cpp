@@ -1870,3 +1870,6 @@ int iyk_emul_stream_wait_args(uint64_t st, uint64_t other, int st_replica, int o
                                            other_ordinal));
 }
 }
+
+/* ---- lane_jobs.hpp: K request packets of one circuit as one batch — iyk_emul_gate_batch_lanes_args, iyk_emul_lane_jobs, iyk_emul_lane_dispatch */
+#include "lane_emul.hpp"

@@ -49,6 +49,7 @@
 #include "cb_rotate.hpp"
 #include "cb_rotate_lat.hpp"
 #include "cb_rotate_fft.hpp"
+#include "lane_jobs.hpp"
 
 using namespace iyk;
 using namespace iyk::dispatch;
@@ -219,6 +220,8 @@ struct iyk_hip_stream {
     uint64_t ks_mat_seen = 0;   // Device::ks_mat_id of the key-switch operand this stream is already ordered behind (ensure_ks_matrix)
     u32* d_abar = nullptr;  // mod-switched rotation inputs, one row of ABAR_STRIDE words per job
     size_t rot_cap = 0;
+    char* d_lane = nullptr;   // iyk_hip_gate_batch_lanes: the job lists of all lanes, written by lane_jobs_kernel (lane_jobs.hpp)
+    size_t lane_cap = 0;      // bytes
     // timing of the most recent batch
     hipEvent_t ev_br0 = nullptr, ev_br1 = nullptr, ev_ks1 = nullptr;
     bool timing_valid = false, timing_has_ks = false;
@@ -316,6 +319,21 @@ int ensure_rot(iyk_hip_stream* st, size_t jobs)
     HIP_TRY(hipMalloc((void**)&st->d_rot, cap * (NTT_N + 1) * sizeof(u32)));
     HIP_TRY(hipMalloc((void**)&st->d_abar, cap * ABAR_STRIDE * sizeof(u32)));
     st->rot_cap = cap;
+    return IYK_OK;
+}
+
+// The expanded job lists of a lane batch.  Grows like the rotation buffer: before the batch's first launch and behind a stream
+// synchronise, so never under a queued batch that still reads the old allocation.
+int ensure_lane(iyk_hip_stream* st, size_t bytes)
+{
+    if (bytes <= st->lane_cap) return IYK_OK;
+    HIP_TRY(hipStreamSynchronize(st->s));
+    if (st->d_lane) HIP_TRY(hipFree(st->d_lane));
+    st->d_lane = nullptr;
+    st->lane_cap = 0;
+    const size_t cap = bytes + bytes / 2 + 4096;   // ensure_rot's growth
+    HIP_TRY(hipMalloc((void**)&st->d_lane, cap));
+    st->lane_cap = cap;
     return IYK_OK;
 }
 
@@ -722,6 +740,7 @@ void destroy_stream_resources(iyk_hip_stream* st)
     if (st->d_stage) (void)hipFree(st->d_stage);
     if (st->d_rot) (void)hipFree(st->d_rot);
     if (st->d_abar) (void)hipFree(st->d_abar);
+    if (st->d_lane) (void)hipFree(st->d_lane);
     if (st->d_sel) (void)hipFree(st->d_sel);
     if (st->d_scratch) (void)hipFree(st->d_scratch);
     if (st->h_gate) (void)hipHostFree(st->h_gate);
@@ -1691,6 +1710,62 @@ int iyk_hip_gate_batch(iyk_hip_stream* st, uint32_t* d_arena, uint64_t arena_slo
             return rc;
         HIP_TRY(hipEventRecord(st->ev_br1, st->s));
         if ((rc = launch_keyswitch(st, d_arena, (const KsJob*)d[1], (int)ks.size()))) return rc;
+        HIP_TRY(hipEventRecord(st->ev_ks1, st->s));
+        st->timing_valid = true;
+        st->timing_has_ks = true;
+    }
+    return IYK_OK;
+    IYK_API_END
+}
+
+// iyk_hip_gate_batch for `lanes` copies of one circuit's arena image, lane r in slots [r * lane_stride, (r + 1) * lane_stride): the
+// descriptors are one lane's.  One lane's lists are staged, lane_jobs_kernel writes the lists of all lanes into the stream's d_lane
+// (lane-major), and the elementwise, rotation and key-switch launches of iyk_hip_gate_batch run them as ONE batch of count x lanes
+// jobs — kernel and grid chosen for that total.  lanes == 1: the staged lists are the batch, nothing is expanded.
+int iyk_hip_gate_batch_lanes(iyk_hip_stream* st, uint32_t* d_arena, uint64_t arena_slots, uint64_t count, const int32_t* ops,
+                             const int32_t* in0, const int32_t* in1, const int32_t* in2, const int32_t* out, uint64_t lanes,
+                             uint64_t lane_stride)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    if (!st || !d_arena) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    if (!ops || !in0 || !in1 || !in2 || !out) return fail(IYK_ERR_INVALID, "null descriptor array");
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    const iyk_params& p = G.p;
+    std::vector<RotJob> rot;
+    std::vector<KsJob> ks;
+    std::vector<EwJob> ew;
+    if (const args::Refusal r = args::gate_batch_lanes_args(p, G.debug, arena_slots, count, ops, in0, in1, in2, out, lanes, lane_stride, rot, ks, ew))
+        return refuse(r);
+    const size_t nrot = rot.size() * lanes, nks = ks.size() * lanes, new_ = ew.size() * lanes;   // of all lanes
+    const LaneScratch ls = lane_scratch(rot.size(), ks.size(), ew.size(), lanes);
+    if ((rc = ensure_rot(st, nrot))) return rc;
+    if (lanes > 1 && (rc = ensure_lane(st, ls.bytes))) return rc;
+    char* d[3];   // the last part is not padded
+    if ((rc = stage_put(st, {{rot.data(), rot.size() * sizeof(RotJob)}, {ks.data(), ks.size() * sizeof(KsJob)}, {ew.data(), ew.size() * sizeof(EwJob)}}, d)))
+        return rc;
+    if ((rc = release_stage(st))) return rc;
+    if (lanes > 1) {
+        const LaneLists L{(const RotJob*)d[0], (const KsJob*)d[1], (const EwJob*)d[2], (RotJob*)st->d_lane, (KsJob*)(st->d_lane + ls.ks_off),
+                          (EwJob*)(st->d_lane + ls.ew_off), (uint32_t)rot.size(), (uint32_t)ks.size(), (uint32_t)ew.size(), (uint32_t)lanes,
+                          (uint32_t)lane_stride};
+        hipLaunchKernelGGL(lane_jobs_kernel, dim3(lane_jobs_grid(lane_jobs_total(L))), dim3(LANE_JOBS_THREADS), 0, st->s, L);
+        HIP_TRY(hipGetLastError());
+        d[0] = (char*)L.rot, d[1] = (char*)L.ks, d[2] = (char*)L.ew;
+    }
+
+    if (new_) {
+        hipLaunchKernelGGL(elementwise_kernel, dim3((unsigned)new_), dim3(256), 0, st->s, d_arena, (const EwJob*)d[2], p.n, p.mu);
+        HIP_TRY(hipGetLastError());
+    }
+    st->timing_valid = false;
+    if (nrot) {
+        if ((rc = begin_timing(st))) return rc;
+        if ((rc = launch_blind_rotate(st, d_arena, (const RotJob*)d[0], (int)nrot, RotOut{st->d_rot, nullptr, 0}))) return rc;
+        HIP_TRY(hipEventRecord(st->ev_br1, st->s));
+        if ((rc = launch_keyswitch(st, d_arena, (const KsJob*)d[1], (int)nks))) return rc;
         HIP_TRY(hipEventRecord(st->ev_ks1, st->s));
         st->timing_valid = true;
         st->timing_has_ks = true;

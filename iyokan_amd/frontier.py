@@ -617,16 +617,40 @@ class FrontierPlan:
                 "max_rank_gates_per_level": [L["B"] for L in self.levels]}
 
 
-class PlainBitBackend:
-    """Bits instead of ciphertexts: arena = torch.uint8 [slots, 1] on CPU.  Test support."""
+def _check_lanes(lanes):
+    if not isinstance(lanes, (int, np.integer)) or lanes < 1:
+        raise ValueError(f"lanes = {lanes!r}: a backend has one lane or more")
 
-    def __init__(self, num_slots):
+
+def _lane_slots(be, slots, lane):
+    """slots of one lane's image -> slots of the backend's arena: + lane * lane_stride.  A slot outside the image, and a lane the
+    backend does not have, are refused: lane r owns [r * lane_stride, (r + 1) * lane_stride) and nothing else."""
+    if not 0 <= lane < be.lanes:
+        raise ValueError(f"lane {lane} of a backend with {be.lanes}")
+    s = np.asarray(slots, dtype=np.int64)
+    if s.size and (s.min() < 0 or s.max() >= be.lane_stride):
+        raise ValueError(f"slot outside the lane's {be.lane_stride} slots")
+    return s + lane * be.lane_stride
+
+
+class PlainBitBackend:
+    """Bits instead of ciphertexts: arena = torch.uint8 [slots, 1] on CPU.  Test support.
+    lanes > 1: that many copies of the circuit's image in one arena, lane r in slots [r * num_slots, (r + 1) * num_slots); a gate
+    batch runs on every lane, the descriptors are one lane's (the bits twin of HipBackend(lanes=))."""
+
+    def __init__(self, num_slots, lanes=1):
         import torch
 
-        self.arena = torch.zeros((num_slots, 1), dtype=torch.uint8)
+        _check_lanes(lanes)
+        self.lanes, self.lane_stride = lanes, num_slots
+        self.arena = torch.zeros((lanes * num_slots, 1), dtype=torch.uint8)
 
     def gate_batch(self, ops, in0, in1, in2, out):
-        a = self.arena.numpy()[:, 0]
+        for r in range(self.lanes):
+            self._lane_batch(self.arena.numpy()[r * self.lane_stride:(r + 1) * self.lane_stride, 0], ops, in0, in1, in2, out)
+
+    @staticmethod
+    def _lane_batch(a, ops, in0, in1, in2, out):
         v0 = a[np.maximum(in0, 0)]
         v1 = a[np.maximum(in1, 0)]
         v2 = a[np.maximum(in2, 0)]
@@ -642,17 +666,17 @@ class PlainBitBackend:
                 res[m] = table[name][m]
         a[out] = res
 
-    def write(self, slot, value):
-        self.arena[slot, 0] = int(np.asarray(value).reshape(-1)[0])
+    def write(self, slot, value, lane=0):
+        self.arena[int(_lane_slots(self, slot, lane)), 0] = int(np.asarray(value).reshape(-1)[0])
 
-    def write_many(self, slots, values):
-        self.arena.numpy()[np.asarray(slots, dtype=np.int64), 0] = np.asarray(values, dtype=np.uint8).reshape(len(slots))
+    def write_many(self, slots, values, lane=0):
+        self.arena.numpy()[_lane_slots(self, slots, lane), 0] = np.asarray(values, dtype=np.uint8).reshape(len(slots))
 
-    def read(self, slot):
-        return int(self.arena[slot, 0])
+    def read(self, slot, lane=0):
+        return int(self.arena[int(_lane_slots(self, slot, lane)), 0])
 
-    def read_many(self, slots):
-        return [self.read(s_) for s_ in slots]
+    def read_many(self, slots, lane=0):
+        return [self.read(s_, lane) for s_ in slots]
 
     def sync(self):
         pass
@@ -660,15 +684,19 @@ class PlainBitBackend:
 
 class HipBackend:
     """Ciphertexts in HBM: arena = torch.int32 [slots, n+1] on the rank's GPU, kernels through the
-    C ABI on torch's current stream (so RCCL collectives issued by torch.distributed order with them)."""
+    C ABI on torch's current stream (so RCCL collectives issued by torch.distributed order with them).
+    lanes > 1: that many copies of the circuit's image in one arena, lane r in slots [r * num_slots, (r + 1) * num_slots); a gate batch
+    is ONE Stream.gate_batch(lanes=, lane_stride=num_slots) — one lane's descriptors, count x lanes gates on the GPU."""
 
-    def __init__(self, num_slots, params, device):
+    def __init__(self, num_slots, params, device, lanes=1):
         import torch
 
         from . import hip
 
+        _check_lanes(lanes)
         self.torch, self.hip = torch, hip
-        self.arena = torch.zeros((num_slots, params.n + 1), dtype=torch.int32, device=device)
+        self.lanes, self.lane_stride = lanes, num_slots
+        self.arena = torch.zeros((lanes * num_slots, params.n + 1), dtype=torch.int32, device=device)
         self._tstream = torch.cuda.Stream(device=device)
         torch.cuda.synchronize(device)
         self.stream = hip.Stream(0, hip_stream=self._tstream.cuda_stream)
@@ -677,28 +705,31 @@ class HipBackend:
 
     def gate_batch(self, ops, in0, in1, in2, out):
         if len(ops):
-            self.stream.gate_batch(self._arena, ops, in0, in1, in2, out)
+            if self.lanes == 1:
+                self.stream.gate_batch(self._arena, ops, in0, in1, in2, out)
+            else:
+                self.stream.gate_batch(self._arena, ops, in0, in1, in2, out, lanes=self.lanes, lane_stride=self.lane_stride)
 
-    def write(self, slot, tlwe):
+    def write(self, slot, tlwe, lane=0):
         t = self.torch.from_numpy(np.ascontiguousarray(tlwe, dtype=np.uint32).view(np.int32))
         with self.torch.cuda.stream(self._tstream):
-            self.arena[slot].copy_(t)
+            self.arena[int(_lane_slots(self, slot, lane))].copy_(t)
         self._tstream.synchronize()
 
-    def write_many(self, slots, tlwe_rows):
+    def write_many(self, slots, tlwe_rows, lane=0):
         rows = np.ascontiguousarray(tlwe_rows, dtype=np.uint32).reshape(len(slots), -1).view(np.int32)
-        idx = self.torch.as_tensor(np.asarray(slots, dtype=np.int64), device=self.arena.device)
+        idx = self.torch.as_tensor(_lane_slots(self, slots, lane), device=self.arena.device)
         with self.torch.cuda.stream(self._tstream):
             self.arena[idx] = self.torch.from_numpy(rows).to(self.arena.device)
         self._tstream.synchronize()
 
-    def read(self, slot):
+    def read(self, slot, lane=0):
         self._tstream.synchronize()
-        return self.arena[slot].cpu().numpy().view(np.uint32)
+        return self.arena[int(_lane_slots(self, slot, lane))].cpu().numpy().view(np.uint32)
 
-    def read_many(self, slots):
+    def read_many(self, slots, lane=0):
         self._tstream.synchronize()
-        idx = self.torch.as_tensor(np.asarray(slots, dtype=np.int64), device=self.arena.device)
+        idx = self.torch.as_tensor(_lane_slots(self, slots, lane), device=self.arena.device)
         return self.arena[idx].cpu().numpy().view(np.uint32)
 
     def sync(self):
@@ -711,21 +742,24 @@ class HipBackend:
 class FrontierExecutor:
     def __init__(self, plan, backend, rank=0, world=1, dist=None):
         assert plan.world == world
+        if getattr(backend, "lanes", 1) > 1 and world > 1:
+            raise ValueError("lanes > 1 with world > 1: the level exchange lists are per slot of ONE image — lanes over several GPUs are not built")
         self.plan, self.be, self.rank, self.world, self.dist = plan, backend, rank, world, dist
         self.collectives = 0
 
     # ---- host-visible ports (TaskMem::set/get) -------------------------------------------
-    def set_input(self, port, bit, value):
-        self.be.write(self.plan.slot[self.plan.nl.inputs[(port, bit)]], value)
+    # lane: which copy of the image on a backend with lanes (0 on every other: backends without lanes take no such argument)
+    def set_input(self, port, bit, value, lane=0):
+        self.set_node(self.plan.nl.inputs[(port, bit)], value, lane)
 
-    def get_output(self, port, bit):
-        return self.be.read(self.plan.slot[self.plan.nl.outputs[(port, bit)]])
+    def get_output(self, port, bit, lane=0):
+        return self.get_node(self.plan.nl.outputs[(port, bit)], lane)
 
-    def set_node(self, node, value):
-        self.be.write(self.plan.slot[node], value)
+    def set_node(self, node, value, lane=0):
+        self.be.write(self.plan.slot[node], value, **_lane_kw(lane))
 
-    def get_node(self, node):
-        return self.be.read(self.plan.slot[node])
+    def get_node(self, node, lane=0):
+        return self.be.read(self.plan.slot[node], **_lane_kw(lane))
 
     # ---- one combinational evaluation -------------------------------------------------------
     def run(self, after_stage=None):
@@ -779,6 +813,10 @@ class FrontierExecutor:
 
     def sync(self):
         self.be.sync()
+
+
+def _lane_kw(lane):
+    return {"lane": lane} if lane else {}
 
 
 class _null:

@@ -44,6 +44,7 @@ EXPORTS = [
     "iyk_hip_bk2_key_create", "iyk_hip_bk2_key_upload", "iyk_hip_bk2_key_free", "iyk_hip_bk2_key_bytes", "iyk_hip_cb_rotate_batch",
     "iyk_hip_circuit_bootstrap_batch", "iyk_hip_cb_rotate_form", "iyk_hip_bk2_key_create_form", "iyk_hip_bk2_key_form",
     "iyk_hip_cmux_rotate_chain_batch", "iyk_hip_cmux_tree_batch", "iyk_hip_stream_wait_stream",
+    "iyk_hip_gate_batch_lanes",
 ]
 
 
@@ -89,6 +90,8 @@ def lib():
         L.iyk_hip_trlwe_upload.argtypes = [_vp, _vp, u64, u64, u64, _u32p]
         L.iyk_hip_trlwe_download.argtypes = [_vp, _vp, u64, u64, u64, _u32p]
         L.iyk_hip_gate_batch.argtypes = [_vp, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p, _i32p]
+        if hasattr(L, "iyk_hip_gate_batch_lanes"):   # a library from before the entry point still loads: Stream.gate_batch raises on lanes
+            L.iyk_hip_gate_batch_lanes.argtypes = [_vp, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p, _i32p, u64, u64]
         L.iyk_hip_gate_host.argtypes = [_vp, ctypes.c_int, _u32p, _u32p, _u32p, _u32p]
         L.iyk_hip_blind_rotate_batch.argtypes = [_vp, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p, _u32p, _vp]
         L.iyk_hip_bootstrap_trlwe_batch.argtypes = [_vp, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p, _u32p, _vp, u64, _i32p]
@@ -534,14 +537,24 @@ class Stream:
         _check(lib().iyk_hip_arena_sync_slots_multi(self.h, src_arena.ptr, src_arena.slots, n, sts, ptrs, caps, len(slots),
                                                     slots.ctypes.data_as(_i32p)), "iyk_hip_arena_sync_slots_multi")
 
-    def gate_batch(self, arena, ops, in0, in1, in2, out):
-        """`len(ops)` independent gates on arena slots; asynchronous (poll query() / sync())."""
+    def gate_batch(self, arena, ops, in0, in1, in2, out, lanes=1, lane_stride=None):
+        """`len(ops)` independent gates on arena slots; asynchronous (poll query() / sync()).
+        lanes / lane_stride given: the gates on `lanes` copies of the circuit's arena image, lane r in slots [r * lane_stride,
+        (r + 1) * lane_stride) — the descriptors are ONE lane's (iyk_hip_gate_batch_lanes; lane_stride None: arena.slots // lanes)."""
         ops, in0, in1, in2, out = map(_i32, (ops, in0, in1, in2, out))
         n = len(ops)
         assert len(in0) == len(in1) == len(in2) == len(out) == n
         p = lambda a: a.ctypes.data_as(_i32p)
-        _check(lib().iyk_hip_gate_batch(self.h, arena.ptr, arena.slots, n, p(ops), p(in0), p(in1), p(in2), p(out)),
-               "iyk_hip_gate_batch")
+        if lanes == 1 and lane_stride is None:
+            _check(lib().iyk_hip_gate_batch(self.h, arena.ptr, arena.slots, n, p(ops), p(in0), p(in1), p(in2), p(out)),
+                   "iyk_hip_gate_batch")
+            return
+        if not hasattr(lib(), "iyk_hip_gate_batch_lanes"):
+            raise IykHipError(f"{LIB_PATH} has no iyk_hip_gate_batch_lanes: it was built before lane batches — rebuild it")
+        if lane_stride is None:
+            lane_stride = arena.slots // lanes if lanes > 0 else 0
+        _check(lib().iyk_hip_gate_batch_lanes(self.h, arena.ptr, arena.slots, n, p(ops), p(in0), p(in1), p(in2), p(out), int(lanes),
+                                              int(lane_stride)), "iyk_hip_gate_batch_lanes")
 
     def gate_host(self, op, in0=None, in1=None, in2=None):
         """cufhe::Nand(out, in0, in1, st) shape: host in, host out (synchronised here)."""

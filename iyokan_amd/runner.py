@@ -27,47 +27,65 @@ from .packet import PlainPacket
 
 
 class PlainEngine:
-    def __init__(self, nl):
-        self.nl = nl
-        self.sim = N.PlainSimulator(nl)
+    """lanes: that many independent copies of the circuit's state (run_packets: one request each); run / tick clock them all."""
 
-    def set_nodes(self, nids, bits):
+    def __init__(self, nl, lanes=1):
+        if lanes < 1:
+            raise ValueError(f"lanes = {lanes!r}: an engine has one lane or more")
+        self.nl, self.lanes = nl, lanes
+        self.sims = [N.PlainSimulator(nl) for _ in range(lanes)]
+        self.sim = self.sims[0]
+
+    def set_nodes(self, nids, bits, lane=0):
         for nid, v in zip(nids, bits):
-            self.sim.val[nid] = v
+            self.sims[lane].val[nid] = v
 
-    def get_nodes(self, nids):
-        return [self.sim.node_value(i) for i in nids]
+    def get_nodes(self, nids, lane=0):
+        return [self.sims[lane].node_value(i) for i in nids]
 
     def run(self):
-        self.sim.evaluate()
+        for sim in self.sims:
+            sim.evaluate()
 
     def tick(self):
-        self.sim.tick()
+        for sim in self.sims:
+            sim.tick()
 
 
 class CipherEngine:
     """A FrontierExecutor (ciphertext slots) seen as a bit engine: `encrypt(bits) -> rows`,
     `decrypt(rows) -> bits`.  State cells start as trivial 0 like TaskCUFHEGateDFF's constructor
-    (/root/reference/src/iyokan_cufhe.hpp:108-133)."""
+    (/root/reference/src/iyokan_cufhe.hpp:108-133).
+    lanes: the copies of the circuit's image the executor's backend holds (HipBackend / PlainBitBackend(lanes=)); None: whatever
+    the backend has.  run / tick clock all lanes at once — every level ONE batch of count x lanes gates — and set_nodes / get_nodes
+    address one lane.  The plan is the single-lane plan."""
 
-    def __init__(self, executor, encrypt, decrypt, zero_row):
+    def __init__(self, executor, encrypt, decrypt, zero_row, lanes=None):
         self.ex, self.encrypt, self.decrypt = executor, encrypt, decrypt
         self.nl = executor.plan.nl
+        have = getattr(executor.be, "lanes", 1)
+        if lanes is not None and lanes != have:
+            raise ValueError(f"lanes = {lanes!r}, but the executor's backend holds {have}: give the backend the lane count")
+        self.lanes = have
         plan = executor.plan
         cells = list(plan.dffs) + list(plan.sources)   # state cells and not-yet-driven inputs read as 0
-        if cells:
-            executor.be.write_many([plan.slot[i] for i in cells], np.tile(zero_row, (len(cells), 1)))
+        for lane in range(self.lanes if cells else 0):
+            executor.be.write_many([plan.slot[i] for i in cells], np.tile(zero_row, (len(cells), 1)), **self._lane(lane))
 
-    def set_nodes(self, nids, bits):
+    @staticmethod
+    def _lane(lane):
+        return {"lane": lane} if lane else {}   # a backend without lanes takes no such argument
+
+    def set_nodes(self, nids, bits, lane=0):
         if len(nids):
             slot = self.ex.plan.slot
-            self.ex.be.write_many([slot[i] for i in nids], self.encrypt([int(b) for b in bits]))
+            self.ex.be.write_many([slot[i] for i in nids], self.encrypt([int(b) for b in bits]), **self._lane(lane))
 
-    def get_nodes(self, nids):
+    def get_nodes(self, nids, lane=0):
         if not len(nids):
             return []
         slot = self.ex.plan.slot
-        return [int(b) for b in self.decrypt(self.ex.be.read_many([slot[i] for i in nids]))]
+        return [int(b) for b in self.decrypt(self.ex.be.read_many([slot[i] for i in nids], **self._lane(lane)))]
 
     def run(self):
         self.ex.run()
@@ -178,13 +196,17 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
     refresh_aside=True: every RAM's refresh runs on ONE second stream of the engine (Ram.write_port(refresh_stream=...), whose class
     docstring has the argument), beside the next clock's DFF copies, first-stage gates and circuit bootstrapping; each RAM orders itself
     back in front of its next read, write, cells() or free(), and load_ram in front of its upload.  The same words.
-    Both are off by default; DESIGN.md section 6e has what either measured."""
+    Both are off by default; DESIGN.md section 6e has what either measured.
+    lanes: 1.  The memories hold one request: lanes > 1 (here or on the executor's backend) is a ValueError."""
 
     def __init__(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packet=None, decrypt_ram=None, words_only=False,
-                 rom_fused=False, tree_fused=False, stage_cb=False, refresh_aside=False):
+                 rom_fused=False, tree_fused=False, stage_cb=False, refresh_aside=False, lanes=1):
         from . import cmux, hip
         from .params import params_80bit
 
+        if lanes != 1 or getattr(executor.be, "lanes", 1) != 1:
+            raise ValueError("CMUX memories have no lanes (lanes > 1 is refused): a cmux.Rom / cmux.Ram holds ONE request's rows and "
+                             "selectors — run the lowered (mux-*) form of the system with CipherEngine, or one lane")
         p = hip.current_params()
         p80 = params_80bit()
         if (p.n, p.l, p.Bgbit) == (p80.n, p80.l, p80.Bgbit) and not words_only:
@@ -332,12 +354,77 @@ def _at_width(system, nl, name):
     return nl.port_width(nl.inputs, name)
 
 
+class _Lane:
+    """One lane of a laned engine as the engine run_packet's steps write to and read from.  run / tick do nothing here: the lanes
+    share them, and run_packets calls the engine's own once all lanes have taken a step's writes."""
+
+    def __init__(self, engine, lane):
+        self.engine, self.lane = engine, lane
+
+    def set_nodes(self, nids, bits):
+        self.engine.set_nodes(nids, bits, **({"lane": self.lane} if self.lane else {}))
+
+    def get_nodes(self, nids):
+        return self.engine.get_nodes(nids, **({"lane": self.lane} if self.lane else {}))
+
+
+def _check_request(system, request, cycles):
+    """What run_packet refuses in a request, found before anything runs."""
+    nl = getattr(system, "nl", system)
+    if "reset" in request.bits:
+        raise ValueError("@reset cannot be set by user's input")
+    if cycles < 0 and ("finflag", 0) not in nl.outputs:
+        raise ValueError("the number of cycles is unspecified and the system has no @finflag")
+    for name, cells in getattr(system, "ram", {}).items():
+        image = request.ram.get(name)
+        if image is not None and len(image) != len(cells):
+            raise ValueError("Invalid request packet: wrong length of RAM")
+
+
+def _load_roms(system, engine, request):
+    """ROM contents exist from the start"""
+    for name, cells in getattr(system, "rom", {}).items():
+        image = request.rom.get(name)
+        if image is not None:
+            order = sorted(cells)
+            engine.set_nodes([cells[i] for i in order], [image[i] if i < len(image) else 0 for i in order])
+    for pt in getattr(system, "ports", []):
+        if pt.kind == "rom":
+            engine.load_rom(pt.name, request)
+
+
+def _load_rams(system, engine, request):
+    """setInitialRAM: the request's RAM images, written after the first tick"""
+    for name, cells in getattr(system, "ram", {}).items():
+        image = request.ram.get(name)
+        if image is None:
+            continue
+        if len(image) != len(cells):
+            raise ValueError("Invalid request packet: wrong length of RAM")
+        order = sorted(cells)
+        engine.set_nodes([cells[i] for i in order], [image[i] for i in order])
+    for pt in getattr(system, "ports", []):
+        if pt.kind == "ram":
+            engine.load_ram(pt.name, request)
+
+
+def _set_inputs(system, engine, request, done):
+    """setCircularInputs: the @inputs of cycle `done`"""
+    nl = getattr(system, "nl", system)
+    nids, vals = [], []
+    for (port, bit), nid in nl.inputs.items():
+        stream = request.bits.get(port)
+        if stream:
+            width = _at_width(system, nl, port)
+            nids.append(nid)
+            vals.append(stream[(width * done + bit) % len(stream)])
+    engine.set_nodes(nids, vals)
+
+
 def run_packet(system, request, cycles=None, engine=None, skip_reset=False, on_cycle=None):
     """Run `system` (a `System` from `load_blueprint`, or a bare `Netlist`) on the request packet.
     `cycles`: None -> the packet's own `cycles`, else -1 -> until @finflag.  Returns the result packet."""
     nl = getattr(system, "nl", system)
-    roms = getattr(system, "rom", {})
-    rams = getattr(system, "ram", {})
     ports = getattr(system, "ports", [])
     if engine is None:
         if ports:
@@ -352,14 +439,7 @@ def run_packet(system, request, cycles=None, engine=None, skip_reset=False, on_c
     def get_output(port, bit):
         return engine.get_nodes([nl.outputs[(port, bit)]])[0]
 
-    for name, cells in roms.items():          # ROM contents exist from the start
-        image = request.rom.get(name)
-        if image is not None:
-            order = sorted(cells)
-            engine.set_nodes([cells[i] for i in order], [image[i] if i < len(image) else 0 for i in order])
-    for pt in ports:
-        if pt.kind == "rom":
-            engine.load_rom(pt.name, request)
+    _load_roms(system, engine, request)
 
     if "reset" in request.bits:
         raise ValueError("@reset cannot be set by user's input")
@@ -379,25 +459,8 @@ def run_packet(system, request, cycles=None, engine=None, skip_reset=False, on_c
         if done == 0:
             if negate_reset:
                 set_input("reset", 0, 0)
-            for name, cells in rams.items():
-                image = request.ram.get(name)
-                if image is None:
-                    continue
-                if len(image) != len(cells):
-                    raise ValueError("Invalid request packet: wrong length of RAM")
-                order = sorted(cells)
-                engine.set_nodes([cells[i] for i in order], [image[i] for i in order])
-            for pt in ports:
-                if pt.kind == "ram":
-                    engine.load_ram(pt.name, request)
-        nids, vals = [], []
-        for (port, bit), nid in nl.inputs.items():
-            stream = request.bits.get(port)
-            if stream:
-                width = _at_width(system, nl, port)
-                nids.append(nid)
-                vals.append(stream[(width * done + bit) % len(stream)])
-        engine.set_nodes(nids, vals)
+            _load_rams(system, engine, request)
+        _set_inputs(system, engine, request, done)
         engine.run()
         done += 1
         if on_cycle is not None:
@@ -405,6 +468,53 @@ def run_packet(system, request, cycles=None, engine=None, skip_reset=False, on_c
         if cycles < 0 and get_output("finflag", 0) == 1:
             break
     return result_packet(system, engine, done)
+
+
+def run_packets(system, requests, cycles=None, engine=None, skip_reset=False):
+    """K request packets of one system in ONE run: request r lives in lane r of `engine` (PlainEngine(nl, lanes=K), or a CipherEngine on
+    a backend with lanes=K: every level of every clock is then ONE batch of count x K gates on the GPU).  Lane r goes through
+    run_packet's steps with requests[r] — ROM images, the reset cycle, the cycle-0 RAM images, the circular inputs — and result r is what
+    run_packet(system, requests[r]) returns alone; the lanes share only the clock.
+    So the requests have to agree on what the clock needs: `cycles` (None: each packet's own) is ONE number of cycles, which an
+    until-@finflag run (-1) cannot be — lanes finish on their own clocks; requests that disagree, and what run_packet refuses in any
+    of them, are refused before anything runs.  CMUX memory ports have no lanes (CmuxCipherEngine): run the lowered (mux-*) system."""
+    nl = getattr(system, "nl", system)
+    requests = list(requests)
+    if not requests:
+        raise ValueError("no request packet")
+    if getattr(system, "ports", []):
+        raise ValueError("a system with CMUX memory ports runs one request at a time: CMUX memories have no lanes (use the lowered mux-* form)")
+    each = [cycles if cycles is not None else (r.cycles if r.cycles is not None else -1) for r in requests]
+    if len(set(each)) != 1:
+        raise ValueError(f"the request packets disagree on the number of cycles: {each}")
+    cycles = each[0]
+    if cycles < 0:
+        raise ValueError("lanes share one clock: run_packets needs a number of cycles, not a run until @finflag")
+    for r in requests:
+        _check_request(system, r, cycles)
+    if engine is None:
+        engine = PlainEngine(nl, lanes=len(requests))
+    if getattr(engine, "lanes", 1) != len(requests):
+        raise ValueError(f"{len(requests)} request packets for an engine with {getattr(engine, 'lanes', 1)} lanes")
+    lanes = [_Lane(engine, r) for r in range(len(requests))]
+
+    for lane, request in zip(lanes, requests):
+        _load_roms(system, lane, request)
+    negate_reset = ("reset", 0) in nl.inputs and not skip_reset
+    if negate_reset:
+        for lane in lanes:
+            lane.set_nodes([nl.inputs[("reset", 0)]], [1])
+        engine.run()
+    for done in range(cycles):
+        engine.tick()
+        for lane, request in zip(lanes, requests):
+            if done == 0:
+                if negate_reset:
+                    lane.set_nodes([nl.inputs[("reset", 0)]], [0])
+                _load_rams(system, lane, request)
+            _set_inputs(system, lane, request, done)
+        engine.run()
+    return [result_packet(system, lane, cycles) for lane in lanes]
 
 
 def result_packet(system, engine, cycles):
