@@ -352,6 +352,30 @@ int iyk_hip_cmux_rotate_chain_batch(iyk_hip_stream* st, const void* d_trgsw, uin
  * or launched; IYK_ERR_STATE off the FFT path.  With IYK_HIP_DEBUG=1 the kernel feeds iyk_hip_fft_round_error. */
 int iyk_hip_cmux_tree_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
                             uint64_t count, const int32_t* sel0, const int32_t* levels, const int32_t* first, const int32_t* out);
+/* The four CMUX batches above on `lanes` copies of one memory at once: K request packets of one circuit through one ROM / RAM clock.
+ * Lane r's TRLWE rows are lane 0's + r * row_stride and its selector slots lane 0's + r * sel_stride (a rotate chain's steps: its sel
+ * entries); the arrays are those of ONE lane and stand for job g of every lane.  One lane's list is staged, a kernel writes the lists
+ * of all lanes on the device (csrc/cmux_lane_jobs.hpp, lane-major), and the UNCHANGED kernel of the parent call runs them as ONE
+ * batch of count * lanes jobs, its grid taken from that total: the same words per lane as the parent call on that lane alone.
+ * Checked before anything is staged (IYK_ERR_INVALID, nothing enqueued): everything the parent call checks, on lane 0's list against
+ * the whole stores; lanes not 0, and no stride 0 with lanes > 1; count * lanes <= 2^24; the rows one lane's list reads or writes span
+ * less than row_stride (max - min < row_stride), so no two lanes share a row; the highest row + (lanes - 1) * row_stride < trlwe_slots
+ * and the highest selector slot + (lanes - 1) * sel_stride < trgsw_slots (selector slots are only read: lanes may interleave them);
+ * no index of any lane reaches 2^31; for the rotate chain, sum(steps) * lanes <= 2^31 - 1.  lanes == 1 enqueues exactly what the
+ * parent call enqueues and ignores the strides. */
+int iyk_hip_cmux_batch_lanes(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
+                             uint64_t count, const int32_t* sel, const int32_t* in0, const int32_t* in1, const int32_t* rot,
+                             const int32_t* out, uint32_t lanes, uint64_t sel_stride, uint64_t row_stride);
+int iyk_hip_cmux_chain_batch_lanes(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
+                                   uint64_t count, const int32_t* sel0, const int32_t* steps, const uint32_t* pattern, const int32_t* src,
+                                   const int32_t* mem, const int32_t* out, uint32_t lanes, uint64_t sel_stride, uint64_t row_stride);
+int iyk_hip_cmux_rotate_chain_batch_lanes(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe,
+                                          uint64_t trlwe_slots, uint64_t count, const int32_t* steps, const int32_t* sel,
+                                          const int32_t* rot, const int32_t* src, const int32_t* out, uint32_t lanes, uint64_t sel_stride,
+                                          uint64_t row_stride);
+int iyk_hip_cmux_tree_batch_lanes(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
+                                  uint64_t count, const int32_t* sel0, const int32_t* levels, const int32_t* first, const int32_t* out,
+                                  uint32_t lanes, uint64_t sel_stride, uint64_t row_stride);
 /* T[out] = T[a] + T[b] mod 2^32 per job, with b0_offset added to coefficient 0 of the b polynomial; asynchronous on st, host
  * arrays copied before return.  The tail of TFHEpp::HomMUXwoSE<Lvl01> (TaskTFHEppGateMUXWoSE, /root/reference/src/iyokan_tfhepp.hpp:
  * 500-508): with a, b the rows of the two blind rotations iyk_hip_bootstrap_trlwe_batch(cs + c1 - mu) and (-cs + c0 - mu) and

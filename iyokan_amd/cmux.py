@@ -175,17 +175,60 @@ def _selector_store(trgsw, sel_base, need):
     return sel_base
 
 
+# ---- lanes: K copies of one memory at fixed strides (csrc/cmux_lane_jobs.hpp) --------------------------------
+# A memory's job lists stay ONE lane's.  The four CMUX families go through the Stream.cmux_*_batch calls with lanes / sel_stride /
+# row_stride and are expanded on the device; the flat index arrays of the extraction, MUXwoSE, the add and the refresh are replicated
+# here, lane-major, with one numpy broadcast.
+def lane_flat(a, lanes, stride):
+    """Lane 0's index array for all lanes, lane-major: entry r * len(a) + g is a[g] + r * stride; a negative entry ("none") stays."""
+    a = np.asarray(a, dtype=np.int64).ravel()
+    if lanes == 1:
+        return a
+    return np.where(a < 0, a, np.add.outer(np.arange(lanes, dtype=np.int64) * int(stride), a)).ravel()
+
+
+def lane_tile(a, lanes):
+    """An array of per-job values that are the same in every lane, lane-major."""
+    a = np.asarray(a).ravel()
+    return a if lanes == 1 else np.tile(a, lanes)
+
+
+def _lane_setup(lanes, sel_stride, arena_stride, trgsw, sel_base, sel_need, what):
+    """(lanes, sel_stride, arena_stride) of a memory, refused (ValueError) before anything is allocated: lanes > 1 needs arena_stride, and
+    a caller's selector store must hold the last lane's slots.  sel_stride None: sel_need, the slots one lane uses."""
+    lanes = int(lanes)
+    if lanes < 1:
+        raise ValueError(f"lanes {lanes}: at least one")
+    sel_stride = int(sel_need if sel_stride is None else sel_stride)
+    if lanes > 1:
+        if arena_stride is None:
+            raise ValueError(f"a {what} of {lanes} lanes needs arena_stride: lane r's arena slots are lane 0's + r * arena_stride")
+        if sel_stride < 1 or int(arena_stride) < 1:
+            raise ValueError("sel_stride and arena_stride of a laned memory are at least 1")
+        if trgsw is not None and int(sel_base) + (lanes - 1) * sel_stride + sel_need > trgsw.slots:
+            raise ValueError(f"selector slots up to {int(sel_base) + (lanes - 1) * sel_stride + sel_need - 1} needed for {lanes} lanes, "
+                             f"the store has {trgsw.slots}")
+    return lanes, sel_stride, None if arena_stride is None else int(arena_stride)
+
+
 class Rom:
     """A ROM of TRLWE rows on one GPU.  read() runs rom_read_plan for R independent reads at once: the jobs of all reads at one
     level go into ONE cmux_batch, each read with its own scratch rows and its own addr_width selectors; then bit i of every read's
     word is extracted at coefficient index i and key-switched into an arena slot.
     trgsw, sel_base: a selector store the caller owns and the first of the addr_width * max_reads slots this ROM uses in it (read r, bit b
     at sel_base + r * addr_width + b); every job list names those slots, uploads go there, and free() leaves the store alone.  Without
-    them the ROM allocates and frees a store of its own, slots from 0."""
+    them the ROM allocates and frees a store of its own, slots from 0.
+    lanes=K: K copies of the ROM, one per request packet, in one store: lane r's rows are lane 0's + r * row_stride (row_stride the
+    one-lane store's rows), its selector slots lane 0's + r * sel_stride (default addr_width * max_reads) and its arena slots lane 0's +
+    r * arena_stride.  data_trlwe is one image for every lane or K images, lane-major; upload_lane replaces one lane's.  The job lists
+    stay ONE lane's and every read runs all lanes in the same launches (Stream.cmux_*_batch(lanes=...)): lane r's words are those of a
+    one-lane ROM with lane r's image and selectors."""
 
     sel_base, own_trgsw = 0, True   # of a ROM with a selector store of its own
+    lanes, sel_stride, arena_stride = 1, None, None
 
-    def __init__(self, stream, data_trlwe, addr_width, log2_word_bits, max_reads=1, trgsw=None, sel_base=0):
+    def __init__(self, stream, data_trlwe, addr_width, log2_word_bits, max_reads=1, trgsw=None, sel_base=0, lanes=1, sel_stride=None,
+                 arena_stride=None):
         from . import hip
 
         p = hip.current_params()
@@ -196,14 +239,33 @@ class Rom:
         if not self.plan:
             raise ValueError("a ROM of one word has no read tree")
         data = np.ascontiguousarray(data_trlwe, dtype=np.uint32).reshape(-1, 2 * p.N)
-        if data.shape[0] != self.layout.data_rows:
-            raise ValueError(f"expected {self.layout.data_rows} TRLWE rows, got {data.shape[0]}")
         self.max_reads = int(max_reads)
+        self.lanes, self.sel_stride, self.arena_stride = _lane_setup(lanes, sel_stride, arena_stride, trgsw, sel_base,
+                                                                     self.max_reads * self.addr_width, "ROM")
+        if data.shape[0] not in (self.layout.data_rows, self.lanes * self.layout.data_rows):
+            raise ValueError(f"expected {self.layout.data_rows} TRLWE rows, got {data.shape[0]}")
         self.sel_base = _selector_store(trgsw, sel_base, self.max_reads * self.addr_width)   # refused before anything is allocated
         self.own_trgsw = trgsw is None
-        self.trlwe = hip.Trlwe(self.layout.data_rows + self.max_reads * self.layout.scratch_rows, stream.gpu_index)
-        self.trgsw = hip.Trgsw(self.max_reads * self.addr_width, stream.gpu_index) if self.own_trgsw else trgsw
-        self.trlwe.upload(stream, 0, data)
+        self.row_stride = self.layout.data_rows + self.max_reads * self.layout.scratch_rows   # the one-lane store
+        self.trlwe = hip.Trlwe(self.lanes * self.row_stride, stream.gpu_index)
+        self.trgsw = (hip.Trgsw((self.lanes - 1) * self.sel_stride + self.max_reads * self.addr_width, stream.gpu_index)
+                      if self.own_trgsw else trgsw)
+        images = data.reshape(-1, self.layout.data_rows, 2 * p.N)
+        for lane in range(self.lanes):
+            self.upload_lane(lane, images[lane if len(images) > 1 else 0])
+
+    def _lanes_kw(self):
+        """What the Stream.cmux_*_batch calls get behind ONE lane's lists; one lane: nothing, the call of before lanes."""
+        return {} if self.lanes == 1 else dict(lanes=self.lanes, sel_stride=self.sel_stride, row_stride=self.row_stride)
+
+    def upload_lane(self, lane, data_trlwe):
+        """Lane `lane`'s image: its data rows, at lane * row_stride.  Asynchronous on the stream."""
+        if not 0 <= lane < self.lanes:
+            raise ValueError(f"lane {lane} of {self.lanes}")
+        data = np.ascontiguousarray(data_trlwe, dtype=np.uint32).reshape(-1, 2 * self.N)
+        if data.shape[0] != self.layout.data_rows:
+            raise ValueError(f"expected {self.layout.data_rows} TRLWE rows, got {data.shape[0]}")
+        self.trlwe.upload(self.stream, lane * self.row_stride, data)
 
     def row(self, read, plan_row):
         """Row of the TRLWE store that plan row `plan_row` is for read number `read`."""
@@ -254,31 +316,42 @@ class Rom:
         out_slots: [R][word_bits] arena slots.  Asynchronous on the stream.  resident=True: the selectors are in self.trgsw already
         (slot sel_base + read * addr_width + bit, e.g. from selectors_from_tlwe2 on this stream): addr_trgsw is ignored and nothing is uploaded.
         fused=True sends the rotate tail of all reads as ONE cmux_rotate_chain_batch instead of one cmux_batch per step, fused_tree=True
-        the upper tree as ONE cmux_tree_batch per four levels instead of one cmux_batch per level: the same words either way."""
+        the upper tree as ONE cmux_tree_batch per four levels instead of one cmux_batch per level: the same words either way.
+        lanes > 1: addr_trgsw is [lanes][R][addr_width]..., lane r's selectors uploaded at + r * sel_stride; out_slots stay lane 0's
+        [R][word_bits], lane r's results land at + r * arena_stride."""
+        K = self.lanes
         if resident:
             out_slots = np.asarray(out_slots, dtype=np.int32).reshape(-1, self.word_bits)
             reads = out_slots.shape[0]
         else:
             sel = np.ascontiguousarray(addr_trgsw, dtype=np.uint32).reshape(-1, self.addr_width, self.trgsw.words)
-            reads = sel.shape[0]
+            if sel.shape[0] % K:
+                raise ValueError(f"{sel.shape[0]} addresses for {K} lanes")
+            reads = sel.shape[0] // K
             out_slots = np.asarray(out_slots, dtype=np.int32).reshape(reads, self.word_bits)
         if reads > self.max_reads:
             raise ValueError(f"{reads} reads, sized for {self.max_reads}")
         if not resident:
-            self.trgsw.upload(self.stream, self.sel_base, sel)
+            for lane in range(K):
+                self.trgsw.upload(self.stream, self.sel_base + lane * self.sel_stride, sel[lane * reads:(lane + 1) * reads])
+        kw = self._lanes_kw()
         upper, chain = self.launches_fused(reads) if fused else (self.launches(reads), None)
         if fused_tree:
             trees = self.tree_launches(reads)
             for args in trees:
-                self.stream.cmux_tree_batch(self.trgsw, self.trlwe, *args)
+                self.stream.cmux_tree_batch(self.trgsw, self.trlwe, *args, **kw)
             upper = upper[sum(args[1][0] for args in trees):]   # what is left of `upper` is the unfused rotate tail
         for args in upper:
-            self.stream.cmux_batch(self.trgsw, self.trlwe, *args)
+            self.stream.cmux_batch(self.trgsw, self.trlwe, *args, **kw)
         if chain is not None:
-            self.stream.cmux_rotate_chain_batch(self.trgsw, self.trlwe, *chain)
+            self.stream.cmux_rotate_chain_batch(self.trgsw, self.trlwe, *chain, **kw)
         rows = np.repeat([self.row(r, self.layout.result) for r in range(reads)], self.word_bits)
         coeff = np.tile(np.arange(self.word_bits), reads)
-        self.stream.sample_extract_index_keyswitch_batch(self.trlwe, rows, coeff, out_slots.ravel(), arena)
+        if K == 1:
+            self.stream.sample_extract_index_keyswitch_batch(self.trlwe, rows, coeff, out_slots.ravel(), arena)
+        else:
+            self.stream.sample_extract_index_keyswitch_batch(self.trlwe, lane_flat(rows, K, self.row_stride), lane_tile(coeff, K),
+                                                             lane_flat(out_slots, K, self.arena_stride), arena)
 
     def free(self):
         self.trlwe.free()
@@ -347,8 +420,9 @@ class Ram:
     order_refresh() first.  The words are those of the one-stream form.  Measured on one MI355X: DESIGN.md section 6e."""
 
     sel_base, own_trgsw, pending_refresh = 0, True, None   # of a RAM with a selector store of its own and its refresh on its own stream
+    lanes, sel_stride, arena_stride = 1, None, None
 
-    def __init__(self, stream, cells_trlwe, addr_width, data_width, trgsw=None, sel_base=0):
+    def __init__(self, stream, cells_trlwe, addr_width, data_width, trgsw=None, sel_base=0, lanes=1, sel_stride=None, arena_stride=None):
         from . import hip
 
         p = hip.current_params()
@@ -357,7 +431,8 @@ class Ram:
         self.layout = ram_layout(self.addr_width, p.N)
         self.plan = ram_read_plan(self.addr_width, p.N)
         data = np.ascontiguousarray(cells_trlwe, dtype=np.uint32).reshape(-1, 2 * p.N)
-        if data.shape[0] != self.data_width * C:
+        self.lanes, self.sel_stride, self.arena_stride = _lane_setup(lanes, sel_stride, arena_stride, trgsw, sel_base, self.addr_width, "RAM")
+        if data.shape[0] not in (self.data_width * C, self.lanes * self.data_width * C):
             raise ValueError(f"expected {self.data_width} x {C} TRLWE rows, got {data.shape[0]}")
         self.ncells = self.data_width * C
         self.plane_scratch = self.layout.scratch_rows + 2
@@ -365,10 +440,25 @@ class Ram:
         self.sel_base = _selector_store(trgsw, sel_base, self.addr_width)   # refused before anything is allocated
         self.own_trgsw = trgsw is None
         self.pending_refresh = None   # the stream a refresh was sent to that the main stream is not ordered behind yet
-        self.trlwe = hip.Trlwe(self.acc0 + self.ncells, stream.gpu_index)
-        self.trgsw = hip.Trgsw(self.addr_width, stream.gpu_index) if self.own_trgsw else trgsw
-        self.arena = hip.Arena(self.ncells, stream.gpu_index)
-        self.trlwe.upload(stream, 0, data)
+        self.row_stride = self.acc0 + self.ncells   # the one-lane store
+        self.trlwe = hip.Trlwe(self.lanes * self.row_stride, stream.gpu_index)
+        self.trgsw = hip.Trgsw((self.lanes - 1) * self.sel_stride + self.addr_width, stream.gpu_index) if self.own_trgsw else trgsw
+        self.arena = hip.Arena(self.lanes * self.ncells, stream.gpu_index)   # lane r: slots [r * ncells, (r + 1) * ncells)
+        images = data.reshape(-1, self.ncells, 2 * p.N)
+        for lane in range(self.lanes):
+            self.upload_lane(lane, images[lane if len(images) > 1 else 0])
+
+    _lanes_kw = Rom._lanes_kw
+
+    def upload_lane(self, lane, cells_trlwe):
+        """Lane `lane`'s image: its cell rows, at lane * row_stride, behind a pending refresh.  Asynchronous on the stream."""
+        if not 0 <= lane < self.lanes:
+            raise ValueError(f"lane {lane} of {self.lanes}")
+        data = np.ascontiguousarray(cells_trlwe, dtype=np.uint32).reshape(-1, 2 * self.N)
+        if data.shape[0] != self.ncells:
+            raise ValueError(f"expected {self.data_width} x {self.cells_per_plane} TRLWE rows, got {data.shape[0]}")
+        self.order_refresh()
+        self.trlwe.upload(self.stream, lane * self.row_stride, data)
 
     def row(self, plane, plan_row):
         """Row of the TRLWE store that row `plan_row` of the read plan is for bit plane `plane`."""
@@ -412,8 +502,9 @@ class Ram:
         fused_tree=True sends the read tree as one cmux_tree_batch per four levels (read_port): the same words."""
         self._slots(wdata_slots, rdata_slots)   # both refused before anything is uploaded or enqueued
         if not resident:
-            self.trgsw.upload(self.stream, self.sel_base,
-                              np.ascontiguousarray(addr_trgsw, dtype=np.uint32).reshape(self.addr_width, self.trgsw.words))
+            sel = np.ascontiguousarray(addr_trgsw, dtype=np.uint32).reshape(self.lanes, self.addr_width, self.trgsw.words)
+            for lane in range(self.lanes):   # lanes > 1: addr_trgsw is [lanes][addr_width]..., lane r's selectors at + r * sel_stride
+                self.trgsw.upload(self.stream, self.sel_base + lane * self.sel_stride, sel[lane])
         self.read_port(arena, rdata_slots, fused_tree)
         self.write_port(arena, wren_slot, wdata_slots, rdata_slots, fused)
 
@@ -439,14 +530,19 @@ class Ram:
         rdata_slots, = self._slots(rdata_slots)
         self.order_refresh()   # the tree reads the cell rows
         # 1, 2: RAMUX, SEI(0) + key switch -> rdata
+        K, kw = self.lanes, self._lanes_kw()
         if fused_tree:
             for args in self.tree_launches():
-                st.cmux_tree_batch(self.trgsw, self.trlwe, *args)
+                st.cmux_tree_batch(self.trgsw, self.trlwe, *args, **kw)
         else:
             for args in self.read_launches():
-                st.cmux_batch(self.trgsw, self.trlwe, *args)
+                st.cmux_batch(self.trgsw, self.trlwe, *args, **kw)
         result = [self.row(d, self.layout.result) for d in range(w)]
-        st.sample_extract_index_keyswitch_batch(self.trlwe, result, np.zeros(w, dtype=np.int32), rdata_slots, arena)
+        if K == 1:
+            st.sample_extract_index_keyswitch_batch(self.trlwe, result, np.zeros(w, dtype=np.int32), rdata_slots, arena)
+        else:
+            st.sample_extract_index_keyswitch_batch(self.trlwe, lane_flat(result, K, self.row_stride), np.zeros(K * w, dtype=np.int32),
+                                                    lane_flat(rdata_slots, K, self.arena_stride), arena)
 
     def write_port(self, arena, wren_slot, wdata_slots, rdata_slots, fused=True, refresh_stream=None):
         """The write half of a clock (steps 3 - 6: MUXwoSE, the chain of every cell, extraction, refresh) with the same resident
@@ -460,33 +556,45 @@ class Ram:
             raise ValueError("refresh_stream is the RAM's own stream: leave it out")
         self.order_refresh()   # the chain reads and writes the cell rows
         # 3: HomMUXwoSE: BlindRotate(wren + wdata - mu) + BlindRotate(-wren + rdata - mu), + mu at coefficient 0 of b
+        K, kw, A, R = self.lanes, self._lanes_kw(), self.arena_stride, self.row_stride
         m1, m0 = zip(*(self.mux_rows(d) for d in range(w)))
         minus_mu = np.full(2 * w, (-self.mu) & 0xFFFFFFFF, dtype=np.uint32)
-        st.bootstrap_trlwe_batch(arena, [wren_slot] * (2 * w), np.concatenate([wdata_slots, rdata_slots]), [1] * w + [-1] * w,
-                                 [1] * (2 * w), minus_mu, self.trlwe.ptr, trlwe_slots=self.trlwe.slots, trlwe_out=m1 + m0)
-        st.trlwe_add_batch(self.trlwe, m1, m0, m1, self.mu)
+        if K == 1:
+            st.bootstrap_trlwe_batch(arena, [wren_slot] * (2 * w), np.concatenate([wdata_slots, rdata_slots]), [1] * w + [-1] * w,
+                                     [1] * (2 * w), minus_mu, self.trlwe.ptr, trlwe_slots=self.trlwe.slots, trlwe_out=m1 + m0)
+            st.trlwe_add_batch(self.trlwe, m1, m0, m1, self.mu)
+        else:   # the flat arrays of all lanes, lane-major: slots + r * arena_stride, rows + r * row_stride
+            st.bootstrap_trlwe_batch(arena, lane_flat([wren_slot] * (2 * w), K, A), lane_flat(np.concatenate([wdata_slots, rdata_slots]), K, A),
+                                     lane_tile([1] * w + [-1] * w, K), lane_tile([1] * (2 * w), K), lane_tile(minus_mu, K), self.trlwe.ptr,
+                                     trlwe_slots=self.trlwe.slots, trlwe_out=lane_flat(m1 + m0, K, R))
+            st.trlwe_add_batch(self.trlwe, lane_flat(m1, K, R), lane_flat(m0, K, R), lane_flat(m1, K, R), self.mu)
         # 4: RAMCMUXs of every cell, in place
         jobs = self.write_jobs()
         if fused:
-            st.cmux_chain_batch(self.trgsw, self.trlwe, *zip(*jobs))
+            st.cmux_chain_batch(self.trgsw, self.trlwe, *zip(*jobs), **kw)
         else:
             steps = [chain_steps(j, self.acc0 + g) for g, j in enumerate(jobs)]
             for s in range(self.addr_width):
-                st.cmux_batch(self.trgsw, self.trlwe, *zip(*(c[s] for c in steps)))
+                st.cmux_batch(self.trgsw, self.trlwe, *zip(*(c[s] for c in steps)), **kw)
         # 5, 6: SEI(0) + key switch of every cell, then the blind rotation back into the cell's row
+        n = K * self.ncells
         cells = np.arange(self.ncells, dtype=np.int32)
+        rows = cells if K == 1 else lane_flat(cells, K, R)           # the cell rows of all lanes
+        slots = cells if K == 1 else np.arange(n, dtype=np.int32)    # the private arena: lane r in slots r * ncells ..
         if refresh_stream is not None:
             refresh_stream.wait_stream(st)
             st = refresh_stream
             self.pending_refresh = refresh_stream
-        st.sample_extract_index_keyswitch_batch(self.trlwe, cells, np.zeros(self.ncells, dtype=np.int32), cells, self.arena)
-        st.bootstrap_trlwe_batch(self.arena, cells, np.full(self.ncells, -1), np.ones(self.ncells), np.zeros(self.ncells),
-                                 np.zeros(self.ncells, dtype=np.uint32), self.trlwe.ptr, trlwe_slots=self.trlwe.slots, trlwe_out=cells)
+        st.sample_extract_index_keyswitch_batch(self.trlwe, rows, np.zeros(n, dtype=np.int32), slots, self.arena)
+        st.bootstrap_trlwe_batch(self.arena, slots, np.full(n, -1), np.ones(n), np.zeros(n),
+                                 np.zeros(n, dtype=np.uint32), self.trlwe.ptr, trlwe_slots=self.trlwe.slots, trlwe_out=rows)
 
-    def cells(self):
-        """The cell rows: u32 [data_width][2^addr_width][2N] (synchronises the stream, behind a pending refresh)."""
+    def cells(self, lane=0):
+        """Lane `lane`'s cell rows: u32 [data_width][2^addr_width][2N] (synchronises the stream, behind a pending refresh)."""
+        if not 0 <= lane < self.lanes:
+            raise ValueError(f"lane {lane} of {self.lanes}")
         self.order_refresh()
-        return self.trlwe.download(self.stream, 0, self.ncells).reshape(self.data_width, self.cells_per_plane, 2 * self.N)
+        return self.trlwe.download(self.stream, lane * self.row_stride, self.ncells).reshape(self.data_width, self.cells_per_plane, 2 * self.N)
 
     def free(self):
         self.order_refresh()   # nothing is freed under a refresh that still runs

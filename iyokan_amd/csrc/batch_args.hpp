@@ -310,6 +310,114 @@ inline Refusal cmux_tree_args(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64
     return ACCEPT;
 }
 
+// ---- CMUX memories per lane (iyk_hip_cmux_*_batch_lanes, cmux_lane_jobs.hpp) ----------------------------------------------------
+// `lanes` copies of one memory: lane r's rows are lane 0's + r * row_stride, its selector slots lane 0's + r * sel_stride.  The arrays
+// are ONE lane's.  Each *_lanes_args below, before anything is staged:
+//   (d) refuses lanes == 0, a zero stride with lanes > 1 and count x lanes > MAX_ROW_BATCH (no product before both factors are bounded:
+//       lanes may be 2^31);
+//   (a) runs the parent's check of lane 0's list against the WHOLE stores — indices, independence inside the lane;
+//   (b) the span rule: the rows lane 0's list touches span less than row_stride (max - min < row_stride), so lane r's rows — the same
+//       rows + r * row_stride — are disjoint from those of every other lane: what (a) proved inside lane 0 holds for the whole batch,
+//       and the proof stays O(count) (a tree: O(count) too, its leaves are the range first .. first + 2^levels - 1);
+//   (c) the highest row + (lanes - 1) * row_stride lies inside the TRLWE store and the highest selector slot + (lanes - 1) * sel_stride
+//       inside the selector store, by division; both stores are at most 2^28, so no offset index reaches 2^31 (checked all the same).
+// Selector slots are only read: lanes may interleave them (sel_stride smaller than a list's selector span: the stage-major layout).
+// lanes == 1: the strides are not looked at, the check is the parent's.  A refusal leaves the list(s) empty.
+// Not named check_*, for cmux_rotate_chain_args' reason above; tests/test_cmux_lane_jobs.py holds every refusal.
+struct LaneReach {
+    int64_t row_lo = INT64_MAX, row_hi = -1, sel_hi = -1;   // of one lane's list
+    void row(int64_t i) { row_lo = i < row_lo ? i : row_lo, row_hi = i > row_hi ? i : row_hi; }
+    void sel(int64_t i) { sel_hi = i > sel_hi ? i : sel_hi; }
+};
+inline Refusal cmux_lanes_counts(uint64_t count, uint64_t lanes, uint64_t sel_stride, uint64_t row_stride)
+{
+    if (lanes == 0) return invalid("lanes is zero");
+    if (lanes > 1 && (sel_stride == 0 || row_stride == 0)) return invalid("a stride is zero with more than one lane");
+    if (count > MAX_ROW_BATCH || lanes > MAX_ROW_BATCH || count * lanes > MAX_ROW_BATCH) return invalid("batch too large: count x lanes");
+    return ACCEPT;
+}
+inline Refusal cmux_lanes_reach(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t lanes, uint64_t sel_stride, uint64_t row_stride, const LaneReach& m)
+{
+    if (lanes == 1 || m.row_hi < 0) return ACCEPT;
+    if ((uint64_t)(m.row_hi - m.row_lo) >= row_stride) return invalid("the rows of one lane's jobs span row_stride or more: two lanes would share a row");
+    const uint64_t more = lanes - 1;
+    if (more > (trlwe_slots - 1 - (uint64_t)m.row_hi) / row_stride) return invalid("the last lane's rows lie outside the TRLWE store");
+    if (more > (trgsw_slots - 1 - (uint64_t)m.sel_hi) / sel_stride) return invalid("the last lane's selector slots lie outside the selector store");
+    if (more > ((uint64_t)INT32_MAX - (uint64_t)m.row_hi) / row_stride || more > ((uint64_t)INT32_MAX - (uint64_t)m.sel_hi) / sel_stride)
+        return invalid("an index of the last lane beyond 2^31 - 1");
+    return ACCEPT;
+}
+
+inline Refusal cmux_batch_lanes_args(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* sel, const int32_t* in0,
+                                     const int32_t* in1, const int32_t* rot, const int32_t* out, uint64_t lanes, uint64_t sel_stride,
+                                     uint64_t row_stride, std::vector<CmuxJob>& jobs)
+{
+    auto checked = [&]() -> Refusal {
+        if (Refusal r = cmux_lanes_counts(count, lanes, sel_stride, row_stride)) return r;
+        if (Refusal r = check_cmux_batch(trgsw_slots, trlwe_slots, count, sel, in0, in1, rot, out, jobs)) return r;
+        LaneReach m;
+        for (const CmuxJob& j : jobs) {
+            m.sel(j.sel), m.row(j.in0), m.row(j.out);
+            if (j.in1 >= 0) m.row(j.in1);
+        }
+        return cmux_lanes_reach(trgsw_slots, trlwe_slots, lanes, sel_stride, row_stride, m);
+    };
+    const Refusal r = checked();
+    if (r) jobs.clear();
+    return r;
+}
+
+inline Refusal cmux_chain_batch_lanes_args(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* sel0, const int32_t* steps,
+                                           const uint32_t* pattern, const int32_t* src, const int32_t* mem, const int32_t* out, uint64_t lanes,
+                                           uint64_t sel_stride, uint64_t row_stride, std::vector<CmuxChainJob>& jobs)
+{
+    auto checked = [&]() -> Refusal {
+        if (Refusal r = cmux_lanes_counts(count, lanes, sel_stride, row_stride)) return r;
+        if (Refusal r = check_cmux_chain_batch(trgsw_slots, trlwe_slots, count, sel0, steps, pattern, src, mem, out, jobs)) return r;
+        LaneReach m;
+        for (const CmuxChainJob& j : jobs) m.sel((int64_t)j.sel0 + j.steps - 1), m.row(j.src), m.row(j.mem), m.row(j.out);
+        return cmux_lanes_reach(trgsw_slots, trlwe_slots, lanes, sel_stride, row_stride, m);
+    };
+    const Refusal r = checked();
+    if (r) jobs.clear();
+    return r;
+}
+
+// also: sum(steps) x lanes entries of the expanded step list stay inside the 32-bit CmuxRotChainJob::first
+inline Refusal cmux_rotate_chain_batch_lanes_args(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* steps, const int32_t* sel,
+                                                  const int32_t* rot, const int32_t* src, const int32_t* out, uint64_t lanes, uint64_t sel_stride,
+                                                  uint64_t row_stride, std::vector<CmuxRotChainJob>& jobs, std::vector<CmuxRotStep>& list)
+{
+    auto checked = [&]() -> Refusal {
+        if (Refusal r = cmux_lanes_counts(count, lanes, sel_stride, row_stride)) return r;
+        if (Refusal r = cmux_rotate_chain_args(trgsw_slots, trlwe_slots, count, steps, sel, rot, src, out, jobs, list)) return r;
+        if ((uint64_t)list.size() * lanes > (uint64_t)INT32_MAX) return invalid("batch too large: more than 2^31 - 1 steps");
+        LaneReach m;
+        for (const CmuxRotChainJob& j : jobs) m.row(j.src), m.row(j.out);
+        for (const CmuxRotStep& s : list) m.sel(s.sel);
+        return cmux_lanes_reach(trgsw_slots, trlwe_slots, lanes, sel_stride, row_stride, m);
+    };
+    const Refusal r = checked();
+    if (r) jobs.clear(), list.clear();
+    return r;
+}
+
+inline Refusal cmux_tree_batch_lanes_args(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* sel0, const int32_t* levels,
+                                          const int32_t* first, const int32_t* out, uint64_t lanes, uint64_t sel_stride, uint64_t row_stride,
+                                          std::vector<CmuxTreeJob>& jobs)
+{
+    auto checked = [&]() -> Refusal {
+        if (Refusal r = cmux_lanes_counts(count, lanes, sel_stride, row_stride)) return r;
+        if (Refusal r = cmux_tree_args(trgsw_slots, trlwe_slots, count, sel0, levels, first, out, jobs)) return r;
+        LaneReach m;
+        for (const CmuxTreeJob& j : jobs) m.sel((int64_t)j.sel0 + j.levels - 1), m.row(j.first), m.row((int64_t)j.first + (1 << j.levels) - 1), m.row(j.out);
+        return cmux_lanes_reach(trgsw_slots, trlwe_slots, lanes, sel_stride, row_stride, m);
+    };
+    const Refusal r = checked();
+    if (r) jobs.clear();
+    return r;
+}
+
 // iyk_hip_trlwe_add_batch
 inline Refusal check_trlwe_add_batch(uint64_t trlwe_slots, uint64_t count, const int32_t* a, const int32_t* b, const int32_t* out,
                                      std::vector<TrlweAddJob>& jobs)

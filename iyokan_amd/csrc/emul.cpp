@@ -1873,3 +1873,6 @@ int iyk_emul_stream_wait_args(uint64_t st, uint64_t other, int st_replica, int o
 
 /* ---- lane_jobs.hpp: K request packets of one circuit as one batch — iyk_emul_gate_batch_lanes_args, iyk_emul_lane_jobs, iyk_emul_lane_dispatch */
 #include "lane_emul.hpp"
+
+/* ---- cmux_lane_jobs.hpp: CMUX memories per lane — iyk_emul_cmux_lanes_args, iyk_emul_cmux_lane_jobs */
+#include "cmux_lane_emul.hpp"

@@ -50,6 +50,7 @@
 #include "cb_rotate_lat.hpp"
 #include "cb_rotate_fft.hpp"
 #include "lane_jobs.hpp"
+#include "cmux_lane_jobs.hpp"
 
 using namespace iyk;
 using namespace iyk::dispatch;
@@ -2327,6 +2328,170 @@ int iyk_hip_cmux_tree_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t tr
         auto kern = G.debug ? cmux_tree_kernel<GD, true> : cmux_tree_kernel<GD, false>;
         hipLaunchKernelGGL(kern, dim3((unsigned)cmux_tree_grid((long)count)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s,
                            (const CmuxTreeJob*)d[0], (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
+        HIP_TRY(hipGetLastError());
+        return (int)IYK_OK;
+    });
+    if (rc) return rc;
+    return release_stage(st);
+    IYK_API_END
+}
+
+}  // extern "C"
+
+// ---- CMUX memories per lane (cmux_lane_jobs.hpp) ---------------------------------------------------------------------------------
+// The four entry points below: check (batch_args.hpp: *_lanes_args, nothing staged on a refusal), stage ONE lane's list, expand it on
+// the device into the stream's lane scratch, launch the parent's UNCHANGED kernel on count x lanes jobs, the grid from that total.
+namespace {
+
+// The staged list(s) of one lane -> those of all lanes in st->d_lane, which ensure_lane has sized; jobs / steps: what the kernel reads.
+template <class Job>
+int expand_cmux_lanes(iyk_hip_stream* st, const char* d_job1, const char* d_step1, size_t n, size_t nsteps, uint32_t lanes, uint64_t sel_stride,
+                      uint64_t row_stride, const Job** jobs, const CmuxRotStep** steps)
+{
+    const CmuxLaneScratch ls = cmux_lane_scratch(n, sizeof(Job), nsteps, lanes);
+    const CmuxLaneLists<Job> L{(const Job*)d_job1, (const CmuxRotStep*)d_step1, (Job*)st->d_lane, (CmuxRotStep*)(st->d_lane + ls.step_off),
+                               (uint32_t)n, (uint32_t)nsteps, lanes, (uint32_t)sel_stride, (uint32_t)row_stride};
+    hipLaunchKernelGGL(cmux_lane_jobs_kernel<Job>, dim3(lane_jobs_grid(lane_cmux_total(L))), dim3(LANE_JOBS_THREADS), 0, st->s, L);
+    HIP_TRY(hipGetLastError());
+    *jobs = L.job;
+    if (steps) *steps = L.step;
+    return IYK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int iyk_hip_cmux_batch_lanes(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
+                             uint64_t count, const int32_t* sel, const int32_t* in0, const int32_t* in1, const int32_t* rot,
+                             const int32_t* out, uint32_t lanes, uint64_t sel_stride, uint64_t row_stride)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_cmux_batch_lanes")) return rc;
+    if (!st || !d_trgsw || !d_trlwe || !sel || !in0 || !in1 || !rot || !out) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    std::vector<CmuxJob> jobs;
+    if (const args::Refusal r = args::cmux_batch_lanes_args(trgsw_slots, trlwe_slots, count, sel, in0, in1, rot, out, lanes, sel_stride, row_stride, jobs))
+        return refuse(r);
+    if (lanes > 1 && (rc = ensure_lane(st, cmux_lane_scratch(count, sizeof(CmuxJob), 0, lanes).bytes))) return rc;
+    char* d[1];
+    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxJob)}}, d))) return rc;
+    const CmuxJob* dj = (const CmuxJob*)d[0];
+    if (lanes > 1 && (rc = expand_cmux_lanes<CmuxJob>(st, d[0], nullptr, count, 0, lanes, sel_stride, row_stride, &dj, nullptr))) return rc;
+    const uint64_t total = count * lanes;
+    const Device& D = G.devs[st->gpu];
+    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
+        typedef decltype(gd) GD;
+        auto kern = G.debug ? cmux_fft_kernel<GD, true> : cmux_fft_kernel<GD, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((total + BR_WAVES - 1) / BR_WAVES)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s, dj, (int)total,
+                           (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
+        HIP_TRY(hipGetLastError());
+        return (int)IYK_OK;
+    });
+    if (rc) return rc;
+    return release_stage(st);
+    IYK_API_END
+}
+
+int iyk_hip_cmux_chain_batch_lanes(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
+                                   uint64_t count, const int32_t* sel0, const int32_t* steps, const uint32_t* pattern, const int32_t* src,
+                                   const int32_t* mem, const int32_t* out, uint32_t lanes, uint64_t sel_stride, uint64_t row_stride)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_cmux_chain_batch_lanes")) return rc;
+    if (!st || !d_trgsw || !d_trlwe || !sel0 || !steps || !pattern || !src || !mem || !out) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    std::vector<CmuxChainJob> jobs;
+    if (const args::Refusal r = args::cmux_chain_batch_lanes_args(trgsw_slots, trlwe_slots, count, sel0, steps, pattern, src, mem, out, lanes, sel_stride,
+                                                                  row_stride, jobs))
+        return refuse(r);
+    if (lanes > 1 && (rc = ensure_lane(st, cmux_lane_scratch(count, sizeof(CmuxChainJob), 0, lanes).bytes))) return rc;
+    char* d[1];
+    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxChainJob)}}, d))) return rc;
+    const CmuxChainJob* dj = (const CmuxChainJob*)d[0];
+    if (lanes > 1 && (rc = expand_cmux_lanes<CmuxChainJob>(st, d[0], nullptr, count, 0, lanes, sel_stride, row_stride, &dj, nullptr))) return rc;
+    const uint64_t total = count * lanes;
+    const Device& D = G.devs[st->gpu];
+    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
+        typedef decltype(gd) GD;
+        auto kern = G.debug ? cmux_chain_kernel<GD, true> : cmux_chain_kernel<GD, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((total + BR_WAVES - 1) / BR_WAVES)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s, dj, (int)total,
+                           (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
+        HIP_TRY(hipGetLastError());
+        return (int)IYK_OK;
+    });
+    if (rc) return rc;
+    return release_stage(st);
+    IYK_API_END
+}
+
+int iyk_hip_cmux_rotate_chain_batch_lanes(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe,
+                                          uint64_t trlwe_slots, uint64_t count, const int32_t* steps, const int32_t* sel,
+                                          const int32_t* rot, const int32_t* src, const int32_t* out, uint32_t lanes, uint64_t sel_stride,
+                                          uint64_t row_stride)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_cmux_rotate_chain_batch_lanes")) return rc;
+    if (!st || !d_trgsw || !d_trlwe || !steps || !sel || !rot || !src || !out) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    std::vector<CmuxRotChainJob> jobs;
+    std::vector<CmuxRotStep> list;
+    if (const args::Refusal r = args::cmux_rotate_chain_batch_lanes_args(trgsw_slots, trlwe_slots, count, steps, sel, rot, src, out, lanes, sel_stride,
+                                                                         row_stride, jobs, list))
+        return refuse(r);
+    if (lanes > 1 && (rc = ensure_lane(st, cmux_lane_scratch(count, sizeof(CmuxRotChainJob), list.size(), lanes).bytes))) return rc;
+    char* d[2];
+    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxRotChainJob)}, {list.data(), list.size() * sizeof(CmuxRotStep)}}, d))) return rc;
+    const CmuxRotChainJob* dj = (const CmuxRotChainJob*)d[0];
+    const CmuxRotStep* ds = (const CmuxRotStep*)d[1];
+    if (lanes > 1 && (rc = expand_cmux_lanes<CmuxRotChainJob>(st, d[0], d[1], count, list.size(), lanes, sel_stride, row_stride, &dj, &ds))) return rc;
+    const uint64_t total = count * lanes;
+    const Device& D = G.devs[st->gpu];
+    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
+        typedef decltype(gd) GD;
+        auto kern = G.debug ? cmux_rotate_chain_kernel<GD, true> : cmux_rotate_chain_kernel<GD, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)cmux_rotate_chain_grid((long)total)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s, dj, (int)total, ds,
+                           (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
+        HIP_TRY(hipGetLastError());
+        return (int)IYK_OK;
+    });
+    if (rc) return rc;
+    return release_stage(st);
+    IYK_API_END
+}
+
+int iyk_hip_cmux_tree_batch_lanes(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
+                                  uint64_t count, const int32_t* sel0, const int32_t* levels, const int32_t* first, const int32_t* out,
+                                  uint32_t lanes, uint64_t sel_stride, uint64_t row_stride)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_cmux_tree_batch_lanes")) return rc;
+    if (!st || !d_trgsw || !d_trlwe || !sel0 || !levels || !first || !out) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    std::vector<CmuxTreeJob> jobs;
+    if (const args::Refusal r = args::cmux_tree_batch_lanes_args(trgsw_slots, trlwe_slots, count, sel0, levels, first, out, lanes, sel_stride, row_stride,
+                                                                 jobs))
+        return refuse(r);
+    if (lanes > 1 && (rc = ensure_lane(st, cmux_lane_scratch(count, sizeof(CmuxTreeJob), 0, lanes).bytes))) return rc;
+    char* d[1];
+    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxTreeJob)}}, d))) return rc;
+    const CmuxTreeJob* dj = (const CmuxTreeJob*)d[0];
+    if (lanes > 1 && (rc = expand_cmux_lanes<CmuxTreeJob>(st, d[0], nullptr, count, 0, lanes, sel_stride, row_stride, &dj, nullptr))) return rc;
+    const uint64_t total = count * lanes;
+    const Device& D = G.devs[st->gpu];
+    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
+        typedef decltype(gd) GD;
+        auto kern = G.debug ? cmux_tree_kernel<GD, true> : cmux_tree_kernel<GD, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)cmux_tree_grid((long)total)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s, dj, (const fft::cplx*)d_trgsw,
+                           d_trlwe, &D.fftc->c, D.fft_err);
         HIP_TRY(hipGetLastError());
         return (int)IYK_OK;
     });

@@ -45,7 +45,12 @@ EXPORTS = [
     "iyk_hip_circuit_bootstrap_batch", "iyk_hip_cb_rotate_form", "iyk_hip_bk2_key_create_form", "iyk_hip_bk2_key_form",
     "iyk_hip_cmux_rotate_chain_batch", "iyk_hip_cmux_tree_batch", "iyk_hip_stream_wait_stream",
     "iyk_hip_gate_batch_lanes",
+    "iyk_hip_cmux_batch_lanes", "iyk_hip_cmux_chain_batch_lanes", "iyk_hip_cmux_rotate_chain_batch_lanes", "iyk_hip_cmux_tree_batch_lanes",
 ]
+
+
+CMUX_LANES = ("iyk_hip_cmux_batch_lanes", "iyk_hip_cmux_chain_batch_lanes", "iyk_hip_cmux_rotate_chain_batch_lanes",
+              "iyk_hip_cmux_tree_batch_lanes")
 
 
 class IykHipError(RuntimeError):
@@ -104,6 +109,9 @@ def lib():
         L.iyk_hip_cmux_chain_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _u32p, _i32p, _i32p, _i32p]
         L.iyk_hip_cmux_rotate_chain_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p, _i32p]
         L.iyk_hip_cmux_tree_batch.argtypes = [_vp, _vp, u64, _vp, u64, u64, _i32p, _i32p, _i32p, _i32p]
+        for f in CMUX_LANES:   # a library from before these entry points still loads: the Stream.cmux_*_batch calls raise on lanes
+            if hasattr(L, f):
+                getattr(L, f).argtypes = getattr(L, f[:-len("_lanes")]).argtypes + [ctypes.c_uint32, u64, u64]
         L.iyk_hip_trlwe_add_batch.argtypes = [_vp, _vp, u64, u64, _i32p, _i32p, _i32p, ctypes.c_uint32]
         u32 = ctypes.c_uint32
         L.iyk_hip_privks_key_create.argtypes = [ctypes.c_int, u32, u32, u32, ctypes.POINTER(_vp)]
@@ -607,17 +615,30 @@ class Stream:
                                                                   arena.ptr, arena.slots),
                "iyk_hip_sample_extract_index_keyswitch_batch")
 
-    def cmux_batch(self, trgsw, trlwe, sel, in0, in1, rot, out):
+    def _cmux_call(self, name, trgsw, trlwe, count, arrays, lanes, sel_stride, row_stride):
+        """iyk_hip_<name>, or iyk_hip_<name>_lanes where lanes / strides are given: the arrays are ONE lane's, lane r's selector slots are
+        + r * sel_stride and its rows + r * row_stride (csrc/cmux_lane_jobs.hpp)."""
+        head = (self.h, trgsw.ptr, trgsw.slots, trlwe.ptr, trlwe.slots, count) + tuple(arrays)
+        if lanes == 1 and sel_stride is None and row_stride is None:
+            _check(getattr(lib(), "iyk_hip_" + name)(*head), "iyk_hip_" + name)
+            return
+        f = "iyk_hip_" + name + "_lanes"
+        if not hasattr(lib(), f):
+            raise IykHipError(f"{LIB_PATH} has no {f}: it was built before CMUX memories had lanes — rebuild it")
+        if not 0 <= int(lanes) < 1 << 32:
+            raise ValueError(f"lanes {lanes} outside [0, 2^32)")
+        _check(getattr(lib(), f)(*head, int(lanes), int(sel_stride or 0), int(row_stride or 0)), f)
+
+    def cmux_batch(self, trgsw, trlwe, sel, in0, in1, rot, out, lanes=1, sel_stride=None, row_stride=None):
         """len(sel) independent CMUXes on rows of a Trlwe store, asynchronous: T[out] = T[in0] + S[sel] [.] (T[in1] - T[in0]) where
         in1 >= 0 (a selector of 1 selects in1), T[in0] + S[sel] [.] ((X^rot - 1) T[in0]) where in1 < 0.  A job may write over its
         own inputs; no out may be an input or the out of another job of the batch."""
         sel, in0, in1, rot, out = map(_i32, (sel, in0, in1, rot, out))
         assert len(in0) == len(in1) == len(rot) == len(out) == len(sel)
         p = lambda a: a.ctypes.data_as(_i32p)
-        _check(lib().iyk_hip_cmux_batch(self.h, trgsw.ptr, trgsw.slots, trlwe.ptr, trlwe.slots, len(sel), p(sel), p(in0), p(in1),
-                                        p(rot), p(out)), "iyk_hip_cmux_batch")
+        self._cmux_call("cmux_batch", trgsw, trlwe, len(sel), (p(sel), p(in0), p(in1), p(rot), p(out)), lanes, sel_stride, row_stride)
 
-    def cmux_chain_batch(self, trgsw, trlwe, sel0, steps, pattern, src, mem, out):
+    def cmux_chain_batch(self, trgsw, trlwe, sel0, steps, pattern, src, mem, out, lanes=1, sel_stride=None, row_stride=None):
         """len(sel0) independent chains of CMUXes on rows of a Trlwe store, asynchronous (the RAM write-back of one cell per job):
         acc = T[src]; for j < steps, with S = selector slot sel0 + j: acc = T[mem] + S [.] (acc - T[mem]) where bit j of pattern is 1,
         acc + S [.] (T[mem] - acc) where it is 0; T[out] = acc.  Word for word what `steps` dependent cmux_batch jobs give.  A job may
@@ -626,10 +647,10 @@ class Stream:
         pattern = np.ascontiguousarray(pattern, dtype=np.uint32)
         assert len(steps) == len(pattern) == len(src) == len(mem) == len(out) == len(sel0)
         p = lambda a: a.ctypes.data_as(_i32p)
-        _check(lib().iyk_hip_cmux_chain_batch(self.h, trgsw.ptr, trgsw.slots, trlwe.ptr, trlwe.slots, len(sel0), p(sel0), p(steps),
-                                              pattern.ctypes.data_as(_u32p), p(src), p(mem), p(out)), "iyk_hip_cmux_chain_batch")
+        self._cmux_call("cmux_chain_batch", trgsw, trlwe, len(sel0), (p(sel0), p(steps), pattern.ctypes.data_as(_u32p), p(src), p(mem), p(out)),
+                        lanes, sel_stride, row_stride)
 
-    def cmux_rotate_chain_batch(self, trgsw, trlwe, steps, sel, rot, src, out):
+    def cmux_rotate_chain_batch(self, trgsw, trlwe, steps, sel, rot, src, out, lanes=1, sel_stride=None, row_stride=None):
         """len(steps) independent chains of rotate-form CMUXes on rows of a Trlwe store, asynchronous (the lower half of one ROM read
         per job): acc = T[src]; for j < steps[g]: acc = acc + S[sel_j] [.] ((X^rot_j - 1) acc); T[out] = acc.  sel and rot hold the jobs'
         steps one after the other, sum(steps) entries.  Word for word what steps[g] dependent cmux_batch rotate jobs give.  A job may
@@ -642,10 +663,9 @@ class Stream:
         if need > len(sel) or (not len(bad) and need != len(sel)):
             raise ValueError(f"sel and rot hold {len(sel)} steps, the jobs state {need}")
         p = lambda a: a.ctypes.data_as(_i32p)
-        _check(lib().iyk_hip_cmux_rotate_chain_batch(self.h, trgsw.ptr, trgsw.slots, trlwe.ptr, trlwe.slots, len(steps), p(steps), p(sel),
-                                                     p(rot), p(src), p(out)), "iyk_hip_cmux_rotate_chain_batch")
+        self._cmux_call("cmux_rotate_chain_batch", trgsw, trlwe, len(steps), (p(steps), p(sel), p(rot), p(src), p(out)), lanes, sel_stride, row_stride)
 
-    def cmux_tree_batch(self, trgsw, trlwe, sel0, levels, first, out):
+    def cmux_tree_batch(self, trgsw, trlwe, sel0, levels, first, out, lanes=1, sel_stride=None, row_stride=None):
         """len(sel0) independent CMUX read trees on rows of a Trlwe store, asynchronous (up to four levels of the upper half of one memory
         read per job): the 2^levels[g] leaves T[first[g] ..] are halved levels[g] times — level b takes selector slot sel0[g] + b, and job i
         of a level is the CMUX (in0 = candidate 2 i, in1 = candidate 2 i + 1) — and T[out[g]] is the row left.  Word for word what
@@ -654,8 +674,7 @@ class Stream:
         sel0, levels, first, out = map(_i32, (sel0, levels, first, out))
         assert len(sel0) == len(levels) == len(first) == len(out)
         p = lambda a: a.ctypes.data_as(_i32p)
-        _check(lib().iyk_hip_cmux_tree_batch(self.h, trgsw.ptr, trgsw.slots, trlwe.ptr, trlwe.slots, len(sel0), p(sel0), p(levels),
-                                             p(first), p(out)), "iyk_hip_cmux_tree_batch")
+        self._cmux_call("cmux_tree_batch", trgsw, trlwe, len(sel0), (p(sel0), p(levels), p(first), p(out)), lanes, sel_stride, row_stride)
 
     def trlwe_add_batch(self, trlwe, a, b, out, b0_offset=0):
         """T[out] = T[a] + T[b] mod 2^32 on rows of a Trlwe store, b0_offset added to coefficient 0 of the b polynomial (the tail of

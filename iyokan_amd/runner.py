@@ -25,6 +25,8 @@ import numpy as np
 from . import netlist as N
 from .packet import PlainPacket
 
+MAX_CB_BATCH = 1 << 20   # rotations of one circuit bootstrapping batch (csrc/jobs.hpp)
+
 
 class PlainEngine:
     """lanes: that many independent copies of the circuit's state (run_packets: one request each); run / tick clock them all."""
@@ -125,56 +127,72 @@ def _staged_executor(system, backend_of, balance=True, spread=True, cost=None):
 
 class StagedBitsEngine(StagedPorts):
     """The bits-only twin of CmuxCipherEngine: the staged plan of `system` on a PlainBitBackend, every memory port an array of bits
-    read and written in the clear.  What it checks is the ORDER — stages, read before write, write before commit."""
+    read and written in the clear.  What it checks is the ORDER — stages, read before write, write before commit.
+    lanes: that many copies of the circuit's image (PlainBitBackend(lanes=)) and of every memory, one request each (run_packets): a
+    port's read and write run lane by lane, the lanes share the clock only."""
 
-    def __init__(self, system, balance=True, spread=True):
+    port_lanes = True   # run_packets: the memory ports of this engine have lanes
+
+    def __init__(self, system, balance=True, spread=True, lanes=1):
         from . import frontier
 
-        self.ex = _staged_executor(system, frontier.PlainBitBackend, balance, spread)
+        if lanes < 1:
+            raise ValueError(f"lanes = {lanes!r}: an engine has one lane or more")
+        self.lanes = lanes
+        self.ex = _staged_executor(system, (lambda n: frontier.PlainBitBackend(n, lanes=lanes)) if lanes > 1 else frontier.PlainBitBackend, balance,
+                                   spread)
         self.nl, self.ports = system.nl, list(system.ports)
-        self.mem = {pt.name: [0] * (pt.data_width << pt.addr_width) for pt in self.ports}
-        self._addr = {}
+        self.mems = [{pt.name: [0] * (pt.data_width << pt.addr_width) for pt in self.ports} for _ in range(lanes)]
+        self.mem = self.mems[0]
+        self._addrs = [{} for _ in range(lanes)]
+        self._addr = self._addrs[0]
 
-    def set_nodes(self, nids, bits):
+    _lane = staticmethod(CipherEngine._lane)
+
+    def set_nodes(self, nids, bits, lane=0):
         if len(nids):
             slot = self.ex.plan.slot
-            self.ex.be.write_many([slot[i] for i in nids], [int(b) for b in bits])
+            self.ex.be.write_many([slot[i] for i in nids], [int(b) for b in bits], **self._lane(lane))
 
-    def get_nodes(self, nids):
+    def get_nodes(self, nids, lane=0):
         slot = self.ex.plan.slot
-        return self.ex.be.read_many([slot[i] for i in nids])
+        return self.ex.be.read_many([slot[i] for i in nids], **self._lane(lane))
 
     def _port_read(self, pt):
         slot, be = self.ex.plan.slot, self.ex.be
-        addr = sum(b << i for i, b in enumerate(be.read_many([slot[a] for a in pt.addr])))
-        self._addr[pt.name] = addr
-        word = self.mem[pt.name][addr * pt.data_width:(addr + 1) * pt.data_width]
-        be.write_many([slot[r] for r in pt.rdata], word)
+        for lane in range(self.lanes):
+            kw = self._lane(lane)
+            addr = sum(b << i for i, b in enumerate(be.read_many([slot[a] for a in pt.addr], **kw)))
+            self._addrs[lane][pt.name] = addr
+            word = self.mems[lane][pt.name][addr * pt.data_width:(addr + 1) * pt.data_width]
+            be.write_many([slot[r] for r in pt.rdata], word, **kw)
 
     def _port_write(self, pt):
         slot, be = self.ex.plan.slot, self.ex.be
-        if pt.name in self._addr and be.read(slot[pt.wren[0]]):
-            addr = self._addr[pt.name]
-            self.mem[pt.name][addr * pt.data_width:(addr + 1) * pt.data_width] = be.read_many([slot[w] for w in pt.wdata])
+        for lane in range(self.lanes):
+            kw = self._lane(lane)
+            if pt.name in self._addrs[lane] and be.read(slot[pt.wren[0]], **kw):
+                addr = self._addrs[lane][pt.name]
+                self.mems[lane][pt.name][addr * pt.data_width:(addr + 1) * pt.data_width] = be.read_many([slot[w] for w in pt.wdata], **kw)
 
-    def _load(self, name, image):
+    def _load(self, name, image, lane):
         if image is not None:
-            cells = self.mem[name]
+            cells = self.mems[lane][name]
             if len(image) > len(cells):
                 raise ValueError(f"Invalid request packet: the image of {name!r} is longer than the memory")
             cells[:len(image)] = [int(b) for b in image]
 
-    def load_rom(self, name, request):
-        self._load(name, request.rom.get(name))
+    def load_rom(self, name, request, lane=0):
+        self._load(name, request.rom.get(name), lane)
 
-    def load_ram(self, name, request):
+    def load_ram(self, name, request, lane=0):
         image = request.ram.get(name)
-        if image is not None and len(image) != len(self.mem[name]):
+        if image is not None and len(image) != len(self.mems[lane][name]):
             raise ValueError("Invalid request packet: wrong length of RAM")
-        self._load(name, image)
+        self._load(name, image, lane)
 
-    def ram_image(self, name):
-        return list(self.mem[name])
+    def ram_image(self, name, lane=0):
+        return list(self.mems[lane][name])
 
 
 class CmuxCipherEngine(StagedPorts, CipherEngine):
@@ -207,6 +225,16 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         if lanes != 1 or getattr(executor.be, "lanes", 1) != 1:
             raise ValueError("CMUX memories have no lanes (lanes > 1 is refused): a cmux.Rom / cmux.Ram holds ONE request's rows and "
                              "selectors — run the lowered (mux-*) form of the system with CipherEngine, or one lane")
+        self._setup(system, executor, encrypt, decrypt, zero_row, bk2, privks_key, [packet], decrypt_ram, words_only, rom_fused, tree_fused,
+                    stage_cb, refresh_aside, 1)
+
+    def _setup(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packets, decrypt_ram, words_only, rom_fused, tree_fused,
+               stage_cb, refresh_aside, K):
+        """The engine for K lanes (CmuxLaneEngine; K = 1: this class).  Lane r's arena slots are lane 0's + r * the backend's lane stride,
+        every memory is a cmux.Rom / cmux.Ram(lanes=K), and the lvl2 store and the TRLWE scratch hold K x the widest batch."""
+        from . import cmux, hip
+        from .params import params_80bit
+
         p = hip.current_params()
         p80 = params_80bit()
         if (p.n, p.l, p.Bgbit) == (p80.n, p80.l, p80.Bgbit) and not words_only:
@@ -221,18 +249,26 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         CipherEngine.__init__(self, executor, encrypt, decrypt, zero_row)
         be = executor.be
         self.stream, self.arena, self.ports = be.stream, be._arena, list(system.ports)
-        self.bk2, self.privks_key, self.packet, self.decrypt_ram = bk2, privks_key, packet, decrypt_ram
+        self.bk2, self.privks_key, self.packets, self.decrypt_ram = bk2, privks_key, list(packets), decrypt_ram
+        self.packet = self.packets[0]
         self.rom_fused, self.tree_fused, self.stage_cb = bool(rom_fused), bool(tree_fused), bool(stage_cb)
+        self.lanes, self.lane_stride = K, int(getattr(be, "lane_stride", 0))
         N, l, per = int(p.N), int(p.l), int(p.trgsw_rows)
-        widest = self._cb_bits()
+        widest = K * self._cb_bits()
+        if widest * l > MAX_CB_BATCH:
+            raise ValueError(f"{K} lanes x {widest // K} address bits x {l} digits: more than the {MAX_CB_BATCH} rotations of one circuit bootstrapping")
         self.tlwe2 = hip.Tlwe2(hip.Bk2Key.N2, widest * l, self.stream.gpu_index)
         self.scratch = hip.Trlwe(widest * per, self.stream.gpu_index)
         self.sel_base = self._assign_bases() if self.stage_cb else {}
-        self.trgsw = hip.Trgsw(sum(pt.addr_width for pt in self.ports), self.stream.gpu_index) if self.stage_cb else None
+        self.trgsw = hip.Trgsw(K * sum(pt.addr_width for pt in self.ports), self.stream.gpu_index) if self.stage_cb else None
         self.refresh_stream = hip.Stream(self.stream.gpu_index) if refresh_aside else None   # one per engine, whatever the number of RAMs
         self.mem = {}
         for pt in self.ports:
             shared = {"trgsw": self.trgsw, "sel_base": self.sel_base[pt.name]} if self.stage_cb else {}
+            if K > 1:   # stage-major selectors: lane r of a port sits + r * (the bits of the port's stage) from lane 0
+                shared.update(lanes=K, arena_stride=self.lane_stride)
+                if self.stage_cb:
+                    shared["sel_stride"] = sum(q.addr_width for q in self._stage_ports(pt.stage))
             if pt.kind == "rom":
                 log2w = pt.data_width.bit_length() - 1
                 if 1 << log2w != pt.data_width or pt.data_width > N:
@@ -255,14 +291,17 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         return max(sum(pt.addr_width for pt in self.ports if pt.stage == s) for s in {pt.stage for pt in self.ports})
 
     def _assign_bases(self):
-        """{port name: first selector slot}: stage by stage, inside a stage in port order, a ROM and a RAM addr_width slots each (the
-        engine reads one word per clock) — the ports of a stage are contiguous, in the order of _stage_ports."""
+        """{port name: first selector slot (lane 0's)}: stage by stage, inside a stage in port order, a ROM and a RAM addr_width slots
+        each (the engine reads one word per clock) — the ports of a stage are contiguous, in the order of _stage_ports.  With lanes the
+        store is stage-major: stage s owns lanes x bits_s contiguous slots, lane r's copy of the stage + r * bits_s from lane 0's."""
         bases, nxt = {}, 0
         for s in sorted({pt.stage for pt in self.ports}):
+            first = nxt
             for pt in self.ports:
                 if pt.stage == s:
                     bases[pt.name] = nxt
                     nxt += pt.addr_width
+            nxt = first + self.lanes * (nxt - first)
         return bases
 
     def _stage_first_slot(self, pts):
@@ -274,7 +313,7 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         pts = self._stage_ports(s)
         if not pts:
             return
-        addr = np.concatenate([self._slots(pt.addr) for pt in pts])
+        addr = self._lane_slots(np.concatenate([self._slots(pt.addr) for pt in pts]))   # lane-major: the stage-major selector slots
         self.stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, addr, [1] * len(addr), self.tlwe2, 0, self.scratch,
                                             self.trgsw, self._stage_first_slot(pts))
         for pt in pts:
@@ -284,9 +323,16 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         slot = self.ex.plan.slot
         return np.array([slot[i] for i in nodes], dtype=np.int32)
 
+    def _lane_slots(self, slots):
+        """lane 0's arena slots for all lanes, lane-major; one lane: as they are"""
+        if self.lanes == 1:
+            return slots
+        return (np.arange(self.lanes, dtype=np.int32)[:, None] * self.lane_stride + slots[None, :]).ravel().astype(np.int32)
+
     def _port_read(self, pt):
         mem = self.mem[pt.name]
-        self.stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, self._slots(pt.addr), [1] * pt.addr_width, self.tlwe2,
+        addr = self._lane_slots(self._slots(pt.addr))   # lane r's selectors land at r * addr_width: the memory's own sel_stride
+        self.stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, addr, [1] * len(addr), self.tlwe2,
                                             0, self.scratch, mem.trgsw, 0)
         self._port_tree(pt)
 
@@ -302,38 +348,41 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         aside = {} if self.refresh_stream is None else {"refresh_stream": self.refresh_stream}
         self.mem[pt.name].write_port(self.arena, int(self._slots(pt.wren)[0]), self._slots(pt.wdata), self._slots(pt.rdata), **aside)
 
-    def _rows(self, table, name):
-        if self.packet is None:
+    def _rows(self, table, name, lane=0):
+        if self.packets[lane] is None:
+            if self.lanes > 1:
+                raise ValueError(f"CmuxLaneEngine needs the encrypted request of lane {lane} (packets=[TFHEPacket, ...]) for its memory images")
             raise ValueError("CmuxCipherEngine needs the encrypted request (packet=TFHEPacket) for its memory images")
-        return getattr(self.packet, table).get(name)
+        return getattr(self.packets[lane], table).get(name)
 
-    def load_rom(self, name, request):
-        rows, rom = self._rows("rom", name), self.mem[name]
+    def load_rom(self, name, request, lane=0):
+        rows, rom = self._rows("rom", name, lane), self.mem[name]
         if rows is not None:
             rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 2 * rom.N)
             if rows.shape[0] > rom.layout.data_rows:
                 raise ValueError(f"Invalid request packet: the image of {name!r} is longer than the memory")
-            rom.trlwe.upload(self.stream, 0, rows)
+            rom.trlwe.upload(self.stream, lane * getattr(rom, "row_stride", 0), rows)
 
-    def load_ram(self, name, request):
-        rows, ram = self._rows("ram", name), self.mem[name]
+    def load_ram(self, name, request, lane=0):
+        rows, ram = self._rows("ram", name, lane), self.mem[name]
         if rows is not None:
             rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 2 * ram.N)
             if rows.shape[0] != ram.ncells:
                 raise ValueError("Invalid request packet: wrong length of RAM")
             ram.order_refresh()   # the upload overwrites the cell rows on the main stream
             # the packet's order is address * width + bit, the store's one plane of 2^addr_width cells per bit
-            ram.trlwe.upload(self.stream, 0, rows.reshape(ram.cells_per_plane, ram.data_width, -1).transpose(1, 0, 2))
+            ram.trlwe.upload(self.stream, lane * getattr(ram, "row_stride", 0),
+                             rows.reshape(ram.cells_per_plane, ram.data_width, -1).transpose(1, 0, 2))
 
-    def ram_rows(self, name):
-        """The cells of a RAM in the packet's order, u32 [2^addr_width * width][2N] (synchronises the stream)."""
-        cells = self.mem[name].cells()
+    def ram_rows(self, name, lane=0):
+        """The cells of a RAM (lane `lane`'s) in the packet's order, u32 [2^addr_width * width][2N] (synchronises the stream)."""
+        cells = self.mem[name].cells(**self._lane(lane))
         return np.ascontiguousarray(cells.transpose(1, 0, 2)).reshape(-1, cells.shape[2])
 
-    def ram_image(self, name):
+    def ram_image(self, name, lane=0):
         if self.decrypt_ram is None:
             raise ValueError("CmuxCipherEngine needs decrypt_ram to read a RAM image")
-        return [int(b) for b in self.decrypt_ram(self.ram_rows(name))]
+        return [int(b) for b in self.decrypt_ram(self.ram_rows(name, lane))]
 
     def free(self):
         for m in self.mem.values():
@@ -345,6 +394,26 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
             self.refresh_stream = None
         self.tlwe2.free()
         self.scratch.free()
+
+
+class CmuxLaneEngine(CmuxCipherEngine):
+    """CmuxCipherEngine for K request packets in one widened clock (run_packets): K = the lanes of the executor's backend
+    (HipBackend(lanes=K)), `packets` = the K encrypted requests.  Every memory is a cmux.Rom / cmux.Ram(lanes=K): lane r's rows, selector
+    slots and arena slots at fixed strides from lane 0's (csrc/cmux_lane_jobs.hpp).  ONE Stream.circuit_bootstrap_batch per port covers the
+    address slots of all K lanes — K x addr_width x l rotations in the batch one lane pays for anyway — and with stage_cb ONE per stage,
+    into a stage-major selector store (_assign_bases).  The flags are CmuxCipherEngine's; lane r's words are those of a one-lane
+    CmuxCipherEngine given request r's ciphertexts.  One GPU."""
+
+    port_lanes = True   # run_packets: the memory ports of this engine have lanes
+
+    def __init__(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packets=None, decrypt_ram=None, words_only=False,
+                 rom_fused=False, tree_fused=False, stage_cb=False, refresh_aside=False):
+        K = getattr(executor.be, "lanes", 1)
+        packets = [None] * K if packets is None else list(packets)
+        if len(packets) != K:
+            raise ValueError(f"{len(packets)} packets for a backend with {K} lanes")
+        self._setup(system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packets, decrypt_ram, words_only, rom_fused, tree_fused,
+                    stage_cb, refresh_aside, K)
 
 
 def _at_width(system, nl, name):
@@ -366,6 +435,15 @@ class _Lane:
 
     def get_nodes(self, nids):
         return self.engine.get_nodes(nids, **({"lane": self.lane} if self.lane else {}))
+
+    def load_rom(self, name, request):
+        self.engine.load_rom(name, request, **({"lane": self.lane} if self.lane else {}))
+
+    def load_ram(self, name, request):
+        self.engine.load_ram(name, request, **({"lane": self.lane} if self.lane else {}))
+
+    def ram_image(self, name):
+        return self.engine.ram_image(name, **({"lane": self.lane} if self.lane else {}))
 
 
 def _check_request(system, request, cycles):
@@ -482,7 +560,7 @@ def run_packets(system, requests, cycles=None, engine=None, skip_reset=False):
     requests = list(requests)
     if not requests:
         raise ValueError("no request packet")
-    if getattr(system, "ports", []):
+    if getattr(system, "ports", []) and not getattr(engine, "port_lanes", False):
         raise ValueError("a system with CMUX memory ports runs one request at a time: CMUX memories have no lanes (use the lowered mux-* form)")
     each = [cycles if cycles is not None else (r.cycles if r.cycles is not None else -1) for r in requests]
     if len(set(each)) != 1:
