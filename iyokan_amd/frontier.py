@@ -543,23 +543,83 @@ def stage_netlist(nl, stages, s):
     return sub
 
 
+def address_cone(nl, stages, pt):
+    """The gates of stage pt.stage that the address of memory port `pt` depends on: the walk backwards from pt.addr stops at DFFs, at
+    sources and at nodes of other stages (OUTPUT wires stand for their driver).  In topological order."""
+    seen, order = set(), []
+    stack = [(a, False) for a in pt.addr]
+    while stack:
+        i, done = stack.pop()
+        if done:
+            order.append(i)
+            continue
+        k = nl.kinds[i]
+        if k == "OUTPUT":
+            stack.append((nl.ins[i][0], False))
+            continue
+        if i in seen or k in ("INPUT", "DFF") or stages[i] != pt.stage:
+            continue
+        seen.add(i)
+        stack.append((i, True))
+        stack.extend((j, False) for j in nl.ins[i])
+    return order
+
+
+def hoist_cones(nl, stages, s, levels, ports):
+    """`levels` (the planned levels of stage s, lists of nodes) with the address cones of the stage's ports moved to the earliest level
+    their inputs allow — every gate, bootstrapped or not, one level behind the latest of its inputs of this stage, as levelise()
+    places it — and {port name: the number of these levels that hold its cone}.  A cone is closed under the stage's predecessors, so
+    the moves need nothing but the cone; a gate outside it keeps its level, which lies behind every cone gate it reads.  The number
+    of levels stays: a level that a cone gate leaves still holds the gate of the stage's longest path."""
+    root = nl.roots()
+    at, ready = {}, {}
+    for pt in ports:
+        if pt.stage != s:
+            continue
+        top = 0
+        for i in address_cone(nl, stages, pt):
+            if i not in at:
+                at[i] = 1 + max([at[root[j]] for j in nl.ins[i] if root[j] in at], default=-1)   # the cone holds all it reads
+            top = max(top, at[i] + 1)
+        ready[pt.name] = top
+    if not at:
+        return levels, ready
+    out = [[i for i in lv if i not in at] for lv in levels]
+    for i in sorted(at, key=lambda i: (at[i], i)):
+        out[at[i]].append(i)
+    assert all(out) and sum(map(len, out)) == sum(map(len, levels))
+    return out, ready
+
+
 class FrontierPlan:
     """Slot assignment + per-level, per-rank gate descriptor arrays.  `balance` (default): gates with slack are placed in
     the level where the kernels' step-shaped cost is lowest (plan_levels; `cost` = make_level_cost(hip.rotation_round()) on
     a GPU other than the 256-CU MI355X the default describes); False: every gate at its earliest level.  `stages` (node -> stage,
     System.stages): the plan is made stage by stage, each from stage_netlist — stage_levels[s] is the range of self.levels that
-    stage s owns (possibly empty), and a memory port of stage s runs after it (FrontierExecutor.run(after_stage))."""
+    stage s owns (possibly empty), and a memory port of stage s runs after it (FrontierExecutor.run(after_stage)).
+    `early` (the system's memory ports, with `stages`): the gates a port's address depends on (address_cone) are moved to the earliest
+    level of their stage (hoist_cones: the slack-moving planners push exactly these late), and port_ready[name] is the number of
+    levels of self.levels, counted from the first, that must be enqueued before the port's address slots are final — the first
+    level of its stage where the address depends on no gate of the stage.  A port may then be read beside the rest of its stage
+    (FrontierExecutor.run(after_level)).  Without `early` the plan is the one of before the argument and has no port_ready."""
 
-    def __init__(self, nl, world=1, balance=True, cost=mi355x_level_cost, spread=True, stages=None):
+    def __init__(self, nl, world=1, balance=True, cost=mi355x_level_cost, spread=True, stages=None, early=None):
         self.nl, self.world = nl, world
+        if early is not None and stages is None:
+            raise ValueError("early= names the memory ports of a staged plan: give stages= too")
         if stages is None:
             levels = plan_levels(nl, world, cost, spread) if balance else nl.levelise()
             self.stage_levels = [range(len(levels))]
         else:
             levels, self.stage_levels = [], []
+            if early is not None:
+                self.port_ready = {}
             for s in range(1 + max(stages)):
                 sub = stage_netlist(nl, stages, s)
                 lv = [x for x in (plan_levels(sub, world, cost, spread) if balance else sub.levelise()) if x]
+                if early is not None:
+                    lv, ready = hoist_cones(nl, stages, s, lv, early)
+                    self.port_ready.update({name: len(levels) + r for name, r in ready.items()})
                 self.stage_levels.append(range(len(levels), len(levels) + len(lv)))
                 levels += lv
         n = nl.num_nodes
@@ -762,19 +822,30 @@ class FrontierExecutor:
         return self.be.read(self.plan.slot[node], **_lane_kw(lane))
 
     # ---- one combinational evaluation -------------------------------------------------------
-    def run(self, after_stage=None):
-        """after_stage(s): called once the levels of stage s are enqueued (a staged plan's memory ports), on the same stream."""
-        if after_stage is None:
-            return self._run_levels(self.plan.levels)
+    def run(self, after_stage=None, after_level=None):
+        """after_stage(s): called once the levels of stage s are enqueued (a staged plan's memory ports), on the same stream.
+        after_level(i): called with i = 0 before the first level and with every further i up to len(plan.levels) once level i - 1 is
+        enqueued (a port whose address is ready there: plan.port_ready) — at a stage's last level in front of after_stage."""
+        if after_level is None:
+            if after_stage is None:
+                return self._run_levels(self.plan.levels)
+            for s, rng in enumerate(self.plan.stage_levels):
+                self._run_levels(self.plan.levels[rng.start:rng.stop])
+                after_stage(s)
+            return
+        after_level(0)
         for s, rng in enumerate(self.plan.stage_levels):
-            self._run_levels(self.plan.levels[rng.start:rng.stop])
-            after_stage(s)
+            self._run_levels(self.plan.levels[rng.start:rng.stop], rng.start, after_level)
+            if after_stage is not None:
+                after_stage(s)
 
-    def _run_levels(self, levels):
+    def _run_levels(self, levels, first=0, after_level=None):
         be, w = self.be, self.world
         ctx = be.torch.cuda.stream(be.torch_stream) if hasattr(be, "torch_stream") else _null()
         with ctx:
-            for L in levels:
+            for k, L in enumerate(levels):
+                if k and after_level is not None:
+                    after_level(first + k)
                 be.gate_batch(*L["ew_desc"])
                 if L["B"] == 0:
                     continue
@@ -790,6 +861,8 @@ class FrontierExecutor:
                     mine = be.arena[lo + self.rank * B: lo + (self.rank + 1) * B]
                     self._all_gather(whole, mine)
                     self.collectives += 1
+            if levels and after_level is not None:
+                after_level(first + len(levels))
 
     def _all_gather(self, whole, mine):
         """RCCL all_gather_into_tensor on the device arena.  Test rigs with ONE GPU run the ranks as processes sharing that

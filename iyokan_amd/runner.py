@@ -100,7 +100,13 @@ class StagedPorts:
     """run / tick of an engine whose FrontierExecutor has a staged plan and whose memories are ports (system.MemPort): in run(),
     after the levels of stage s every port of stage s turns its address slots into read data (_port_read) on the executor's one
     stream; in tick(), every RAM is written back (_port_write) BEFORE the DFF latch / commit copies — wren / wdata may be DFF
-    outputs, which the commit overwrites.  The write uses the address the read saw (the resident selectors)."""
+    outputs, which the commit overwrites.  The write uses the address the read saw (the resident selectors).
+    read_early (with a plan that has port_ready: FrontierPlan(early=ports)): a port is read once the levels its address depends on are
+    enqueued — port_ready of them — not once its whole stage is; the ports that are read together (_read_groups) go out when the
+    last of them is ready.  An engine with streams forks there (_fork) and joins (_join) in front of the next stage's first level
+    and at the end of run(); on one stream both do nothing and only the program order moves."""
+
+    read_early = False
 
     def _reads(self, s):
         for pt in self.ports:
@@ -108,19 +114,61 @@ class StagedPorts:
                 self._port_read(pt)
 
     def run(self):
-        self.ex.run(after_stage=self._reads)
+        if not self.read_early:
+            return self.ex.run(after_stage=self._reads)
+        self._stage, self._enqueued, self._read = 0, 0, set()
+        self.ex.run(after_stage=self._early_stage, after_level=self._early_level)
+        self._join()
 
-    def tick(self):
+    def _ready_level(self, pt):
+        return self.ex.plan.port_ready[pt.name]
+
+    def _read_groups(self, s):
+        """The ports of stage s in the groups that are read together, in port order: here every port alone"""
+        return [[pt] for pt in self.ports if pt.stage == s]
+
+    def _read_group(self, pts):
+        for pt in pts:
+            self._port_read(pt)
+
+    def _fork(self):
+        pass
+
+    def _join(self):
+        pass
+
+    def _early_level(self, i):
+        self._enqueued = i
+        self._read_ready()
+
+    def _early_stage(self, s):
+        self._join()                # nothing of a later stage runs beside a read of this one: it may read the rdata slots
+        self._stage = s + 1
+        self._read_ready()          # a port of the next stage whose address depends on no gate of that stage
+
+    def _read_ready(self):
+        for pts in self._read_groups(self._stage):
+            if pts[0].name not in self._read and max(self._ready_level(pt) for pt in pts) <= self._enqueued:
+                self._read.add(pts[0].name)
+                self._fork()
+                self._read_group(pts)
+
+    def _write_ports(self):
         for pt in self.ports:
             if pt.kind == "ram":
                 self._port_write(pt)
+
+    def tick(self):
+        self._write_ports()
         self.ex.tick()
 
 
-def _staged_executor(system, backend_of, balance=True, spread=True, cost=None):
+def _staged_executor(system, backend_of, balance=True, spread=True, cost=None, read_early=False):
     from . import frontier
 
     kw = {} if cost is None else {"cost": cost}
+    if read_early:
+        kw["early"] = system.ports
     plan = frontier.FrontierPlan(system.nl, 1, balance, spread=spread, stages=system.stages, **kw)
     return frontier.FrontierExecutor(plan, backend_of(plan.num_slots))
 
@@ -129,18 +177,20 @@ class StagedBitsEngine(StagedPorts):
     """The bits-only twin of CmuxCipherEngine: the staged plan of `system` on a PlainBitBackend, every memory port an array of bits
     read and written in the clear.  What it checks is the ORDER — stages, read before write, write before commit.
     lanes: that many copies of the circuit's image (PlainBitBackend(lanes=)) and of every memory, one request each (run_packets): a
-    port's read and write run lane by lane, the lanes share the clock only."""
+    port's read and write run lane by lane, the lanes share the clock only.
+    read_early=True: the plan hoists the address cones (FrontierPlan(early=)) and every port is read at its port_ready level
+    (StagedPorts): the program order CmuxCipherEngine(read_early=True) spreads over two streams."""
 
     port_lanes = True   # run_packets: the memory ports of this engine have lanes
 
-    def __init__(self, system, balance=True, spread=True, lanes=1):
+    def __init__(self, system, balance=True, spread=True, lanes=1, read_early=False):
         from . import frontier
 
         if lanes < 1:
             raise ValueError(f"lanes = {lanes!r}: an engine has one lane or more")
-        self.lanes = lanes
+        self.lanes, self.read_early = lanes, bool(read_early)
         self.ex = _staged_executor(system, (lambda n: frontier.PlainBitBackend(n, lanes=lanes)) if lanes > 1 else frontier.PlainBitBackend, balance,
-                                   spread)
+                                   spread, read_early=self.read_early)
         self.nl, self.ports = system.nl, list(system.ports)
         self.mems = [{pt.name: [0] * (pt.data_width << pt.addr_width) for pt in self.ports} for _ in range(lanes)]
         self.mem = self.mems[0]
@@ -214,11 +264,20 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
     refresh_aside=True: every RAM's refresh runs on ONE second stream of the engine (Ram.write_port(refresh_stream=...), whose class
     docstring has the argument), beside the next clock's DFF copies, first-stage gates and circuit bootstrapping; each RAM orders itself
     back in front of its next read, write, cells() or free(), and load_ram in front of its upload.  The same words.
-    Both are off by default; DESIGN.md section 6e has what either measured.
+    read_early=True (the executor's plan made with FrontierPlan(early=system.ports)): every memory lives on ONE further stream P of the
+    engine and a port is read there as soon as its address is final (plan.port_ready), beside the rest of its stage's gate levels on
+    the executor's stream M: P waits for M at the fork; M waits for P in front of the first level of the next stage and at the end of
+    run().  With stage_cb the stage's one batch goes out when the last of its ports is ready.  tick(): P waits for M, every RAM's
+    write_port on P, M waits for P, then the latch and commit copies.  A read touches the address slots (final at the fork), the rdata
+    slots (read by later stages only), the lvl2 store, the TRLWE scratch, the selector store, the memory's rows, a RAM's private arena
+    and P's own stream scratch — nothing the gate levels of its stage touch.  The same words.  Measured, it
+    pays with rom_fused + tree_fused: a read of more than eight calls makes the host wait for the rotation inside the read (a stream
+    stages eight calls ahead), and the gate levels beside it are then not enqueued in time.
+    All three are off by default; DESIGN.md section 6e has what each measured.
     lanes: 1.  The memories hold one request: lanes > 1 (here or on the executor's backend) is a ValueError."""
 
     def __init__(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packet=None, decrypt_ram=None, words_only=False,
-                 rom_fused=False, tree_fused=False, stage_cb=False, refresh_aside=False, lanes=1):
+                 rom_fused=False, tree_fused=False, stage_cb=False, refresh_aside=False, lanes=1, read_early=False):
         from . import cmux, hip
         from .params import params_80bit
 
@@ -226,10 +285,10 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
             raise ValueError("CMUX memories have no lanes (lanes > 1 is refused): a cmux.Rom / cmux.Ram holds ONE request's rows and "
                              "selectors — run the lowered (mux-*) form of the system with CipherEngine, or one lane")
         self._setup(system, executor, encrypt, decrypt, zero_row, bk2, privks_key, [packet], decrypt_ram, words_only, rom_fused, tree_fused,
-                    stage_cb, refresh_aside, 1)
+                    stage_cb, refresh_aside, 1, read_early)
 
     def _setup(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packets, decrypt_ram, words_only, rom_fused, tree_fused,
-               stage_cb, refresh_aside, K):
+               stage_cb, refresh_aside, K, read_early=False):
         """The engine for K lanes (CmuxLaneEngine; K = 1: this class).  Lane r's arena slots are lane 0's + r * the backend's lane stride,
         every memory is a cmux.Rom / cmux.Ram(lanes=K), and the lvl2 store and the TRLWE scratch hold K x the widest batch."""
         from . import cmux, hip
@@ -246,6 +305,8 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
             raise ValueError("the executor's plan is not the staged plan of this system (FrontierPlan(stages=system.stages))")
         if bk2.n != p.n:
             raise ValueError(f"the lvl2 bootstrapping key rotates TLWEs of n = {bk2.n}, the arena holds n = {p.n}")
+        if read_early and set(getattr(executor.plan, "port_ready", ())) != {pt.name for pt in system.ports}:
+            raise ValueError("read_early needs a plan that knows when every port's address is ready (FrontierPlan(stages=, early=system.ports))")
         CipherEngine.__init__(self, executor, encrypt, decrypt, zero_row)
         be = executor.be
         self.stream, self.arena, self.ports = be.stream, be._arena, list(system.ports)
@@ -262,6 +323,9 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         self.sel_base = self._assign_bases() if self.stage_cb else {}
         self.trgsw = hip.Trgsw(K * sum(pt.addr_width for pt in self.ports), self.stream.gpu_index) if self.stage_cb else None
         self.refresh_stream = hip.Stream(self.stream.gpu_index) if refresh_aside else None   # one per engine, whatever the number of RAMs
+        self.read_early, self._reads_pending = bool(read_early), False
+        self.port_stream = hip.Stream(self.stream.gpu_index) if self.read_early else None   # P: one per engine, every memory lives on it
+        self.mem_stream = self.port_stream if self.read_early else self.stream
         self.mem = {}
         for pt in self.ports:
             shared = {"trgsw": self.trgsw, "sel_base": self.sel_base[pt.name]} if self.stage_cb else {}
@@ -274,11 +338,11 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
                 if 1 << log2w != pt.data_width or pt.data_width > N:
                     raise ValueError(f"ROM {pt.name!r}: a word of {pt.data_width} bits is no power of two up to N")
                 rows = cmux.rom_layout(pt.addr_width, log2w, N).data_rows
-                self.mem[pt.name] = cmux.Rom(self.stream, np.zeros((rows, 2 * N), dtype=np.uint32), pt.addr_width, log2w, **shared)
+                self.mem[pt.name] = cmux.Rom(self.mem_stream, np.zeros((rows, 2 * N), dtype=np.uint32), pt.addr_width, log2w, **shared)
             else:
                 zero = np.zeros((pt.data_width << pt.addr_width, 2 * N), dtype=np.uint32)
                 zero[:, N] = (-int(p.mu)) & 0xFFFFFFFF          # trivial TRLWEs of bit 0, as the DFFs start as trivial 0
-                self.mem[pt.name] = cmux.Ram(self.stream, zero, pt.addr_width, pt.data_width, **shared)
+                self.mem[pt.name] = cmux.Ram(self.mem_stream, zero, pt.addr_width, pt.data_width, **shared)
 
     def _stage_ports(self, s):
         """The ports of stage s in the order their address bits are concatenated in the stage's batch: port order."""
@@ -311,13 +375,43 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         if not self.stage_cb:
             return StagedPorts._reads(self, s)
         pts = self._stage_ports(s)
-        if not pts:
-            return
+        if pts:
+            self._stage_read(pts)
+
+    def _stage_read(self, pts):
         addr = self._lane_slots(np.concatenate([self._slots(pt.addr) for pt in pts]))   # lane-major: the stage-major selector slots
-        self.stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, addr, [1] * len(addr), self.tlwe2, 0, self.scratch,
-                                            self.trgsw, self._stage_first_slot(pts))
+        self.mem_stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, addr, [1] * len(addr), self.tlwe2, 0, self.scratch,
+                                                self.trgsw, self._stage_first_slot(pts))
         for pt in pts:
             self._port_tree(pt)
+
+    # ---- read_early: the reads on the port stream P, beside the executor's stream M (StagedPorts has the program order) ----
+    def _read_groups(self, s):
+        pts = self._stage_ports(s)
+        return ([pts] if pts else []) if self.stage_cb else [[pt] for pt in pts]
+
+    def _read_group(self, pts):
+        if self.stage_cb:
+            self._stage_read(pts)
+        else:
+            self._port_read(pts[0])
+
+    def _fork(self):
+        self.port_stream.wait_stream(self.stream)   # the address slots are final on M
+        self._reads_pending = True
+
+    def _join(self):
+        if self._reads_pending:
+            self.stream.wait_stream(self.port_stream)
+            self._reads_pending = False
+
+    def tick(self):
+        if not self.read_early:
+            return StagedPorts.tick(self)
+        self.port_stream.wait_stream(self.stream)   # wren, wdata and the gate outputs are final
+        self._write_ports()
+        self.stream.wait_stream(self.port_stream)   # the chain has read wren / wdata / rdata before the commit copies overwrite DFF slots
+        self.ex.tick()
 
     def _slots(self, nodes):
         slot = self.ex.plan.slot
@@ -332,8 +426,8 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
     def _port_read(self, pt):
         mem = self.mem[pt.name]
         addr = self._lane_slots(self._slots(pt.addr))   # lane r's selectors land at r * addr_width: the memory's own sel_stride
-        self.stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, addr, [1] * len(addr), self.tlwe2,
-                                            0, self.scratch, mem.trgsw, 0)
+        self.mem_stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, addr, [1] * len(addr), self.tlwe2,
+                                                0, self.scratch, mem.trgsw, 0)
         self._port_tree(pt)
 
     def _port_tree(self, pt):
@@ -361,7 +455,7 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
             rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 2 * rom.N)
             if rows.shape[0] > rom.layout.data_rows:
                 raise ValueError(f"Invalid request packet: the image of {name!r} is longer than the memory")
-            rom.trlwe.upload(self.stream, lane * getattr(rom, "row_stride", 0), rows)
+            rom.trlwe.upload(self.mem_stream, lane * getattr(rom, "row_stride", 0), rows)
 
     def load_ram(self, name, request, lane=0):
         rows, ram = self._rows("ram", name, lane), self.mem[name]
@@ -369,9 +463,9 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
             rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, 2 * ram.N)
             if rows.shape[0] != ram.ncells:
                 raise ValueError("Invalid request packet: wrong length of RAM")
-            ram.order_refresh()   # the upload overwrites the cell rows on the main stream
+            ram.order_refresh()   # the upload overwrites the cell rows on the memories' stream
             # the packet's order is address * width + bit, the store's one plane of 2^addr_width cells per bit
-            ram.trlwe.upload(self.stream, lane * getattr(ram, "row_stride", 0),
+            ram.trlwe.upload(self.mem_stream, lane * getattr(ram, "row_stride", 0),
                              rows.reshape(ram.cells_per_plane, ram.data_width, -1).transpose(1, 0, 2))
 
     def ram_rows(self, name, lane=0):
@@ -385,6 +479,12 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         return [int(b) for b in self.decrypt_ram(self.ram_rows(name, lane))]
 
     def free(self):
+        if self.port_stream is not None:   # nothing is freed under a read, a chain or a refresh that still runs
+            for m in self.mem.values():
+                if hasattr(m, "order_refresh"):
+                    m.order_refresh()
+            self.port_stream.sync()
+            self._reads_pending = False
         for m in self.mem.values():
             m.free()
         if self.trgsw is not None:
@@ -394,6 +494,9 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
             self.refresh_stream = None
         self.tlwe2.free()
         self.scratch.free()
+        if self.port_stream is not None:
+            self.port_stream.destroy()
+            self.port_stream = None
 
 
 class CmuxLaneEngine(CmuxCipherEngine):
@@ -407,13 +510,13 @@ class CmuxLaneEngine(CmuxCipherEngine):
     port_lanes = True   # run_packets: the memory ports of this engine have lanes
 
     def __init__(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packets=None, decrypt_ram=None, words_only=False,
-                 rom_fused=False, tree_fused=False, stage_cb=False, refresh_aside=False):
+                 rom_fused=False, tree_fused=False, stage_cb=False, refresh_aside=False, read_early=False):
         K = getattr(executor.be, "lanes", 1)
         packets = [None] * K if packets is None else list(packets)
         if len(packets) != K:
             raise ValueError(f"{len(packets)} packets for a backend with {K} lanes")
         self._setup(system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packets, decrypt_ram, words_only, rom_fused, tree_fused,
-                    stage_cb, refresh_aside, K)
+                    stage_cb, refresh_aside, K, read_early)
 
 
 def _at_width(system, nl, name):
