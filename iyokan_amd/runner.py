@@ -24,12 +24,14 @@ import numpy as np
 
 from . import netlist as N
 from .packet import PlainPacket
+from .snapshot import PARAM_NAMES, EngineState, Snapshot, as_snapshot
 
 MAX_CB_BATCH = 1 << 20   # rotations of one circuit bootstrapping batch (csrc/jobs.hpp)
 
 
-class PlainEngine:
-    """lanes: that many independent copies of the circuit's state (run_packets: one request each); run / tick clock them all."""
+class PlainEngine(EngineState):
+    """lanes: that many independent copies of the circuit's state (run_packets: one request each); run / tick clock them all.
+    state() / load_state() (snapshot.EngineState): every node's value, per lane."""
 
     def __init__(self, nl, lanes=1):
         if lanes < 1:
@@ -53,14 +55,30 @@ class PlainEngine:
         for sim in self.sims:
             sim.tick()
 
+    # ---- snapshot.EngineState: the "arena" is the simulator's value of every node ----
+    def _state_plan_slot(self):
+        return None
 
-class CipherEngine:
+    def _state_slots(self):
+        return list(range(self.nl.num_nodes))
+
+    def _read_slots(self, slots, lane):
+        return self.sims[lane].val[slots].astype(np.uint8)
+
+    def _write_slots(self, slots, values, lane):
+        self.sims[lane].val[slots] = values
+
+
+class CipherEngine(EngineState):
     """A FrontierExecutor (ciphertext slots) seen as a bit engine: `encrypt(bits) -> rows`,
     `decrypt(rows) -> bits`.  State cells start as trivial 0 like TaskCUFHEGateDFF's constructor
     (/root/reference/src/iyokan_cufhe.hpp:108-133).
     lanes: the copies of the circuit's image the executor's backend holds (HipBackend / PlainBitBackend(lanes=)); None: whatever
     the backend has.  run / tick clock all lanes at once — every level ONE batch of count x lanes gates — and set_nodes / get_nodes
-    address one lane.  The plan is the single-lane plan."""
+    address one lane.  The plan is the single-lane plan.
+    state() / load_state() (snapshot.EngineState): the words of every slot of the plan, lane by lane through the backend's own lane=."""
+
+    state_kind = "cipher"
 
     def __init__(self, executor, encrypt, decrypt, zero_row, lanes=None):
         self.ex, self.encrypt, self.decrypt = executor, encrypt, decrypt
@@ -94,6 +112,22 @@ class CipherEngine:
 
     def tick(self):
         self.ex.tick()
+
+    # ---- snapshot.EngineState ----
+    def _state_params(self):
+        from . import hip
+
+        p = hip.current_params()
+        return {name: int(getattr(p, name)) for name in PARAM_NAMES}
+
+    def _slot_shape(self):
+        return (self._state_params()["n"] + 1,)
+
+    def _read_slots(self, slots, lane):
+        return np.ascontiguousarray(self.ex.be.read_many(slots, **self._lane(lane)), dtype=np.uint32).reshape(len(slots), -1)
+
+    def _write_slots(self, slots, rows, lane):
+        self.ex.be.write_many(slots, rows, **self._lane(lane))
 
 
 class StagedPorts:
@@ -173,13 +207,15 @@ def _staged_executor(system, backend_of, balance=True, spread=True, cost=None, r
     return frontier.FrontierExecutor(plan, backend_of(plan.num_slots))
 
 
-class StagedBitsEngine(StagedPorts):
+class StagedBitsEngine(StagedPorts, EngineState):
     """The bits-only twin of CmuxCipherEngine: the staged plan of `system` on a PlainBitBackend, every memory port an array of bits
     read and written in the clear.  What it checks is the ORDER — stages, read before write, write before commit.
     lanes: that many copies of the circuit's image (PlainBitBackend(lanes=)) and of every memory, one request each (run_packets): a
     port's read and write run lane by lane, the lanes share the clock only.
     read_early=True: the plan hoists the address cones (FrontierPlan(early=)) and every port is read at its port_ready level
-    (StagedPorts): the program order CmuxCipherEngine(read_early=True) spreads over two streams."""
+    (StagedPorts): the program order CmuxCipherEngine(read_early=True) spreads over two streams.
+    state() / load_state() (snapshot.EngineState): the bits of every slot of the plan and the image of every memory, per lane; the address
+    the last read saw (tick()'s write uses it) is recomputed from the restored address slots."""
 
     port_lanes = True   # run_packets: the memory ports of this engine have lanes
 
@@ -244,6 +280,38 @@ class StagedBitsEngine(StagedPorts):
     def ram_image(self, name, lane=0):
         return list(self.mems[lane][name])
 
+    # ---- snapshot.EngineState ----
+    def _state_meta(self, done, reset_ran):
+        return dict(super()._state_meta(done, reset_ran), ran=[bool(a) for a in self._addrs])   # per lane: whether a read has happened
+
+    def check_state(self, snap):
+        super().check_state(snap)
+        if len(snap.meta.get("ran", [])) != self.lanes:
+            raise ValueError("the snapshot does not say which lanes have read their ports")
+
+    def _read_slots(self, slots, lane):
+        return np.asarray(self.ex.be.read_many(slots, **self._lane(lane)), dtype=np.uint8)
+
+    def _write_slots(self, slots, bits, lane):
+        self.ex.be.write_many(slots, bits, **self._lane(lane))
+
+    def _mem_shape(self, pt):
+        return (pt.data_width << pt.addr_width,)
+
+    def _read_mem(self, pt, lane):
+        return np.asarray(self.mems[lane][pt.name], dtype=np.uint8)
+
+    def _write_mem(self, pt, lane, image):
+        self.mems[lane][pt.name][:] = [int(b) for b in image]
+
+    def _after_load(self, snap):
+        slot, be = self.ex.plan.slot, self.ex.be
+        for lane in range(self.lanes):
+            self._addrs[lane].clear()
+            if snap.meta["ran"][lane]:
+                for pt in self.ports:
+                    self._addrs[lane][pt.name] = sum(b << i for i, b in enumerate(be.read_many([slot[a] for a in pt.addr], **self._lane(lane))))
+
 
 class CmuxCipherEngine(StagedPorts, CipherEngine):
     """CipherEngine for a system with CMUX memory ports, on one GPU.  Per port a cmux.Rom / cmux.Ram on the executor's stream; shared
@@ -274,6 +342,7 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
     pays with rom_fused + tree_fused: a read of more than eight calls makes the host wait for the rotation inside the read (a stream
     stages eight calls ahead), and the gate levels beside it are then not enqueued in time.
     All three are off by default; DESIGN.md section 6e has what each measured.
+    state() / load_state() (snapshot.EngineState): the arena's words, every RAM's cell rows and every ROM's rows, per lane; no key.
     lanes: 1.  The memories hold one request: lanes > 1 (here or on the executor's backend) is a ValueError."""
 
     def __init__(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packet=None, decrypt_ram=None, words_only=False,
@@ -379,11 +448,14 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
             self._stage_read(pts)
 
     def _stage_read(self, pts):
+        self._stage_selectors(pts)
+        for pt in pts:
+            self._port_tree(pt)
+
+    def _stage_selectors(self, pts):
         addr = self._lane_slots(np.concatenate([self._slots(pt.addr) for pt in pts]))   # lane-major: the stage-major selector slots
         self.mem_stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, addr, [1] * len(addr), self.tlwe2, 0, self.scratch,
                                                 self.trgsw, self._stage_first_slot(pts))
-        for pt in pts:
-            self._port_tree(pt)
 
     # ---- read_early: the reads on the port stream P, beside the executor's stream M (StagedPorts has the program order) ----
     def _read_groups(self, s):
@@ -424,11 +496,14 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         return (np.arange(self.lanes, dtype=np.int32)[:, None] * self.lane_stride + slots[None, :]).ravel().astype(np.int32)
 
     def _port_read(self, pt):
+        self._port_selectors(pt)
+        self._port_tree(pt)
+
+    def _port_selectors(self, pt):
         mem = self.mem[pt.name]
         addr = self._lane_slots(self._slots(pt.addr))   # lane r's selectors land at r * addr_width: the memory's own sel_stride
         self.mem_stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, addr, [1] * len(addr), self.tlwe2,
                                                 0, self.scratch, mem.trgsw, 0)
-        self._port_tree(pt)
 
     def _port_tree(self, pt):
         mem = self.mem[pt.name]
@@ -477,6 +552,48 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         if self.decrypt_ram is None:
             raise ValueError("CmuxCipherEngine needs decrypt_ram to read a RAM image")
         return [int(b) for b in self.decrypt_ram(self.ram_rows(name, lane))]
+
+    # ---- snapshot.EngineState (the argument for every store that is left out: DESIGN.md section 6e, "Snapshot and resume") ----
+    def state(self, done=0, reset_ran=False):
+        """CipherEngine's, behind pending device work: the main stream joins a pending early read in front of the arena's download
+        (run() has joined already; a state() taken elsewhere still may not race it), Ram.cells() orders itself behind a refresh that
+        runs aside, and the ROM rows come back through their store's download on the memories' stream.  No host synchronisation
+        but what those downloads do."""
+        self._join()
+        return CipherEngine.state(self, done, reset_ran)
+
+    def _mem_shape(self, pt):
+        mem = self.mem[pt.name]
+        return (mem.layout.data_rows, 2 * mem.N) if pt.kind == "rom" else (mem.data_width, mem.cells_per_plane, 2 * mem.N)
+
+    def _read_mem(self, pt, lane):
+        mem = self.mem[pt.name]
+        if pt.kind == "ram":
+            return mem.cells(**self._lane(lane))
+        return mem.trlwe.download(mem.stream, lane * mem.row_stride, mem.layout.data_rows)
+
+    def _write_mem(self, pt, lane, rows):
+        self.mem[pt.name].upload_lane(lane, rows)   # a RAM's behind a pending refresh (order_refresh), both on the memories' stream
+
+    def _before_load(self):
+        self._join()   # the arena's upload overwrites rdata slots: behind an early read that still writes them
+
+    def _after_load(self, snap):
+        """The selectors of every RAM port: the next tick()'s write-back reads them (the address the last read saw) before any run()
+        rewrites them.  The same circuit bootstrapping run() sends, from the restored address slots — fork and join as for a read."""
+        rams = [pt for pt in self.ports if pt.kind == "ram"]
+        if not rams:
+            return
+        if self.read_early:
+            self._fork()
+        for s in sorted({pt.stage for pt in rams}):
+            if self.stage_cb:
+                self._stage_selectors(self._stage_ports(s))
+            else:
+                for pt in rams:
+                    if pt.stage == s:
+                        self._port_selectors(pt)
+        self._join()
 
     def free(self):
         if self.port_stream is not None:   # nothing is freed under a read, a chain or a refresh that still runs
@@ -602,9 +719,41 @@ def _set_inputs(system, engine, request, done):
     engine.set_nodes(nids, vals)
 
 
-def run_packet(system, request, cycles=None, engine=None, skip_reset=False, on_cycle=None):
+def _check_snapshot_args(snapshot_path, snapshot_every):
+    if snapshot_every is not None:
+        if snapshot_path is None:
+            raise ValueError("snapshot_every without snapshot_path: there is no file to save to")
+        if int(snapshot_every) < 1:
+            raise ValueError(f"snapshot_every = {snapshot_every!r}: every m-th cycle, m at least 1")
+
+
+def _check_resume(nl, engine, resume, cycles, skip_reset):
+    """The Snapshot of run_packet(resume=), refused (ValueError) before the engine is touched where the run cannot continue from it."""
+    snap = as_snapshot(resume)
+    if 0 <= cycles < snap.done:
+        raise ValueError(f"cycles = {cycles} is the total number of cycles, the snapshot has run {snap.done} already")
+    if ("reset", 0) in nl.inputs and not skip_reset and not snap.reset_ran:
+        raise ValueError("the snapshot says the reset cycle never ran, and this run asks for it (skip_reset=False)")
+    if not hasattr(engine, "check_state"):
+        raise ValueError(f"{type(engine).__name__} cannot load a snapshot")
+    engine.check_state(snap)
+    return snap
+
+
+def _save_due(snapshot_path, snapshot_every, done, last):
+    return snapshot_path is not None and (last or (snapshot_every is not None and done % int(snapshot_every) == 0))
+
+
+def run_packet(system, request, cycles=None, engine=None, skip_reset=False, on_cycle=None, snapshot_path=None, snapshot_every=None,
+               resume=None):
     """Run `system` (a `System` from `load_blueprint`, or a bare `Netlist`) on the request packet.
-    `cycles`: None -> the packet's own `cycles`, else -1 -> until @finflag.  Returns the result packet."""
+    `cycles`: None -> the packet's own `cycles`, else -1 -> until @finflag.  Returns the result packet.
+    snapshot_path: the engine's state (engine.state(), snapshot.Snapshot) is saved there after the last cycle, and with snapshot_every=m
+    after every m-th cycle as well (each save replaces the file as a whole).
+    resume: a Snapshot or the path of one.  The ROM images, the reset cycle and the cycle-0 RAM images are skipped, the state is loaded
+    into `engine` and the run goes on at the snapshot's `done`: `cycles` stays the TOTAL number of cycles (cycles=6 from a snapshot at 3
+    runs 3 more), the circular inputs continue where they were, and -1 runs on until @finflag.  The request and the engine's keys are
+    supplied as for a new run; a snapshot that does not fit is refused before the engine is touched."""
     nl = getattr(system, "nl", system)
     ports = getattr(system, "ports", [])
     if engine is None:
@@ -613,6 +762,7 @@ def run_packet(system, request, cycles=None, engine=None, skip_reset=False, on_c
         engine = PlainEngine(nl)
     if cycles is None:
         cycles = request.cycles if request.cycles is not None else -1
+    _check_snapshot_args(snapshot_path, snapshot_every)
 
     def set_input(port, bit, v):
         engine.set_nodes([nl.inputs[(port, bit)]], [v])
@@ -620,22 +770,30 @@ def run_packet(system, request, cycles=None, engine=None, skip_reset=False, on_c
     def get_output(port, bit):
         return engine.get_nodes([nl.outputs[(port, bit)]])[0]
 
-    _load_roms(system, engine, request)
-
-    if "reset" in request.bits:
-        raise ValueError("@reset cannot be set by user's input")
-    has_reset = ("reset", 0) in nl.inputs
-    negate_reset = False
-    if has_reset and not skip_reset:
-        set_input("reset", 0, 1)
-        engine.run()
-        negate_reset = True
-
     has_finflag = ("finflag", 0) in nl.outputs
-    if cycles < 0 and not has_finflag:
-        raise ValueError("the number of cycles is unspecified and the system has no @finflag")
-    done = 0
-    while cycles < 0 or done < cycles:
+    if resume is not None:
+        _check_request(system, request, cycles)
+        snap = _check_resume(nl, engine, resume, cycles, skip_reset)
+        engine.load_state(snap)
+        done, reset_ran = snap.done, snap.reset_ran
+        negate_reset = reset_ran and done == 0              # a snapshot of the reset cycle itself: cycle 0 is still to come
+        finished = cycles < 0 and done > 0 and get_output("finflag", 0) == 1
+    else:
+        _load_roms(system, engine, request)
+
+        if "reset" in request.bits:
+            raise ValueError("@reset cannot be set by user's input")
+        has_reset = ("reset", 0) in nl.inputs
+        negate_reset = False
+        if has_reset and not skip_reset:
+            set_input("reset", 0, 1)
+            engine.run()
+            negate_reset = True
+
+        if cycles < 0 and not has_finflag:
+            raise ValueError("the number of cycles is unspecified and the system has no @finflag")
+        done, reset_ran, finished = 0, negate_reset, False
+    while not finished and (cycles < 0 or done < cycles):
         engine.tick()
         if done == 0:
             if negate_reset:
@@ -646,19 +804,21 @@ def run_packet(system, request, cycles=None, engine=None, skip_reset=False, on_c
         done += 1
         if on_cycle is not None:
             on_cycle(done, engine)
-        if cycles < 0 and get_output("finflag", 0) == 1:
-            break
+        finished = cycles < 0 and get_output("finflag", 0) == 1
+        if _save_due(snapshot_path, snapshot_every, done, finished or done == cycles):
+            engine.state(done=done, reset_ran=reset_ran).save(snapshot_path)
     return result_packet(system, engine, done)
 
 
-def run_packets(system, requests, cycles=None, engine=None, skip_reset=False):
+def run_packets(system, requests, cycles=None, engine=None, skip_reset=False, snapshot_path=None, snapshot_every=None, resume=None):
     """K request packets of one system in ONE run: request r lives in lane r of `engine` (PlainEngine(nl, lanes=K), or a CipherEngine on
     a backend with lanes=K: every level of every clock is then ONE batch of count x K gates on the GPU).  Lane r goes through
     run_packet's steps with requests[r] — ROM images, the reset cycle, the cycle-0 RAM images, the circular inputs — and result r is what
     run_packet(system, requests[r]) returns alone; the lanes share only the clock.
     So the requests have to agree on what the clock needs: `cycles` (None: each packet's own) is ONE number of cycles, which an
     until-@finflag run (-1) cannot be — lanes finish on their own clocks; requests that disagree, and what run_packet refuses in any
-    of them, are refused before anything runs.  CMUX memory ports have no lanes (CmuxCipherEngine): run the lowered (mux-*) system."""
+    of them, are refused before anything runs.  CMUX memory ports have no lanes (CmuxCipherEngine): run the lowered (mux-*) system.
+    snapshot_path / snapshot_every / resume: run_packet's, all K lanes in one file."""
     nl = getattr(system, "nl", system)
     requests = list(requests)
     if not requests:
@@ -677,16 +837,24 @@ def run_packets(system, requests, cycles=None, engine=None, skip_reset=False):
         engine = PlainEngine(nl, lanes=len(requests))
     if getattr(engine, "lanes", 1) != len(requests):
         raise ValueError(f"{len(requests)} request packets for an engine with {getattr(engine, 'lanes', 1)} lanes")
+    _check_snapshot_args(snapshot_path, snapshot_every)
     lanes = [_Lane(engine, r) for r in range(len(requests))]
 
-    for lane, request in zip(lanes, requests):
-        _load_roms(system, lane, request)
-    negate_reset = ("reset", 0) in nl.inputs and not skip_reset
-    if negate_reset:
-        for lane in lanes:
-            lane.set_nodes([nl.inputs[("reset", 0)]], [1])
-        engine.run()
-    for done in range(cycles):
+    if resume is not None:
+        snap = _check_resume(nl, engine, resume, cycles, skip_reset)
+        engine.load_state(snap)
+        first, reset_ran = snap.done, snap.reset_ran
+        negate_reset = reset_ran and first == 0
+    else:
+        for lane, request in zip(lanes, requests):
+            _load_roms(system, lane, request)
+        negate_reset = ("reset", 0) in nl.inputs and not skip_reset
+        if negate_reset:
+            for lane in lanes:
+                lane.set_nodes([nl.inputs[("reset", 0)]], [1])
+            engine.run()
+        first, reset_ran = 0, negate_reset
+    for done in range(first, cycles):
         engine.tick()
         for lane, request in zip(lanes, requests):
             if done == 0:
@@ -695,6 +863,8 @@ def run_packets(system, requests, cycles=None, engine=None, skip_reset=False):
                 _load_rams(system, lane, request)
             _set_inputs(system, lane, request, done)
         engine.run()
+        if _save_due(snapshot_path, snapshot_every, done + 1, done + 1 == cycles):
+            engine.state(done=done + 1, reset_ran=reset_ran).save(snapshot_path)
     return [result_packet(system, lane, cycles) for lane in lanes]
 
 

@@ -16,6 +16,12 @@ rom_fused + tree_fused, all four; --sets picks), --pairs interleaved pairs of th
 read_early=True, in ONE process; a figure as above, the refresh stream included.  The flag-off engine runs the plan of before the flag,
 the flagged one FrontierPlan(early=ports); the model price of both plans is printed.
 
+--snapshot: what saving and resuming a run costs ("Snapshot and resume"): per system (ram-addr8bit, cahp-ruby behind
+CMUX memories) and K in --lanes (default 1 and 8), flags off: the ms per clock of that engine as above, then --pairs times state() +
+Snapshot.save() of it into a temporary directory and Snapshot.load() + load_state() into a second, fresh engine of the same shape (up to
+the synchronisation of its streams, the rebuilt selectors included); median (min .. max), and the file's size.
+
+    python tools/cmux_lanes_measure.py --snapshot --pairs 3 >> profiles/snapshot_cost.txt
     python tools/cmux_lanes_measure.py --bk2-form ntt >> profiles/cmux_lanes_ab.txt
     python tools/cmux_lanes_measure.py --bk2-form fft >> profiles/cmux_lanes_ab.txt
     python tools/cmux_lanes_measure.py --defaults [--root OTHER_TREE] >> profiles/cmux_lanes_ab.txt
@@ -133,6 +139,43 @@ def read_early_leg(m, args, keys, bk2, pk, head, gold):
                 print(f"   {K} | {title:25s} | {fmt(off)} | {fmt(on)} | {np.median(on) - np.median(off):+9.2f} | {'yes' if clear else 'no'}", flush=True)
 
 
+def snapshot_leg(m, args, keys, bk2, pk, head, gold):
+    import shutil
+    import tempfile
+
+    from iyokan_amd.snapshot import Snapshot
+
+    print(f"\n{head}; snapshot: state() + save() and load() + load_state(), {args.pairs} times each, ms, median (min .. max)", flush=True)
+    print("   system | K | ms per clock | state() + save() | load() + load_state() | file, MB", flush=True)
+    where = tempfile.mkdtemp()
+    path = os.path.join(where, "run.snapshot")
+    try:
+        for name in args.systems or ["ram-addr8bit", "cahp-ruby"]:
+            sysm = m.load_blueprint(os.path.join(gold, name + ".toml"), cmux_memories=True)
+            for K in args.lanes or [1, 8]:
+                eng, be = engine(m, keys, sysm, bk2, pk, K)
+                fresh, fresh_be = engine(m, keys, sysm, bk2, pk, K)
+                try:
+                    clock = clocks(eng, be, sysm, args.clocks, K)
+                    save, load = [], []
+                    for _ in range(args.pairs):
+                        t = time.perf_counter()
+                        eng.state(done=args.clocks + 1).save(path)
+                        save.append((time.perf_counter() - t) * 1e3)
+                        t = time.perf_counter()
+                        fresh.load_state(Snapshot.load(path))
+                        fresh_be.sync()
+                        fresh.mem_stream.sync()
+                        load.append((time.perf_counter() - t) * 1e3)
+                    print(f"   {name} | {K} | {clock:9.2f} | {fmt(save)} | {fmt(load)} | {os.path.getsize(path) / 1e6:.1f}", flush=True)
+                finally:
+                    for e, b in ((eng, be), (fresh, fresh_be)):
+                        e.free()
+                        b.close()
+    finally:
+        shutil.rmtree(where)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clocks", type=int, default=2)
@@ -142,6 +185,7 @@ def main():
     ap.add_argument("--systems", nargs="+", default=None, help="default ram-addr8bit cahp-ruby; --defaults: ram-addr8bit; --read-early: cahp-ruby small ram-addr8bit")
     ap.add_argument("--defaults", action="store_true", help="the flags-off one-lane CmuxCipherEngine clock alone (of ram-addr8bit, or of --systems)")
     ap.add_argument("--read-early", action="store_true", help="read_early=True against the same engine without it, per system, K and flag set")
+    ap.add_argument("--snapshot", action="store_true", help="state() + save() and load() + load_state() per system and K, beside the ms per clock")
     ap.add_argument("--sets", type=int, nargs="+", default=None, help="--read-early: which of the six flag sets (0 .. 5), default all")
     ap.add_argument("--root", default=HERE, help="the tree whose iyokan_amd package and library are measured")
     args = ap.parse_args()
@@ -176,6 +220,8 @@ def main():
             print(f"defaults  {head}; {name}, CmuxCipherEngine, ms per clock: {' '.join(f'{x:.2f}' for x in v)}   median {fmt(v)}", flush=True)
     elif args.read_early:
         read_early_leg(m, args, keys, bk2, pk, head, gold)
+    elif args.snapshot:
+        snapshot_leg(m, args, keys, bk2, pk, head, gold)
     else:
         print(f"\n{head}; {args.pairs} interleaved pairs (K = 1, then K lanes) per K, median (min .. max)", flush=True)
         for name in args.systems or ["ram-addr8bit", "cahp-ruby"]:
