@@ -1,6 +1,12 @@
 """GPU: the lvl0 -> lvl2 blind rotation of circuit bootstrapping (iyk_hip_cb_rotate_batch, the lvl2 bootstrapping key object,
 cmux.selectors_from_tlwe0) word for word against the numpy restatement of tests/cb_rotate_ref.py, or against the CPU emulation of the
-kernel (itself held to the restatement by tests/test_cb_rotate_emul.py) where the restatement is too slow."""
+kernel (itself held to the restatement by tests/test_cb_rotate_emul.py) where the restatement is too slow.
+
+Every test that launches rotations runs twice, and its id says under which setting of IYK_HIP_CB_KERNEL: `wg` runs cb_rotate_kernel,
+the 256-lane form this file was written for; `unset` runs whatever dispatch::cb_plan answers for the batch's width, which since the
+latency form became the default for every width is cb_rotate_lat_kernel.  Before every launch hip.cb_rotate_form is asserted to be the
+form the id stands for (0 under `wg`; unset, cb_plan's own answer through the emulation), so a change of the threshold cannot move
+these tests onto another kernel unnoticed.  The knob is read per batch, so monkeypatch sets it per test."""
 import functools
 
 import numpy as np
@@ -11,11 +17,13 @@ import cb_rotate_ref as ref
 import cmux_ref
 import privks_ref
 from iyokan_amd import client, cmux
+from test_cb_rotate_lat_emul import emul as lat_emul, plan
 
 pytestmark = pytest.mark.gpu
 
 FILL = np.uint64(0xA5A5A5A5A5A5A5A5)
 N2 = ref.N2
+KNOB = "IYK_HIP_CB_KERNEL"
 
 
 @pytest.fixture(scope="module")
@@ -33,6 +41,27 @@ def gpu(request):
         key.free()
     st.destroy()
     hip.cleanup()
+
+
+@pytest.fixture(params=["wg", "unset"])
+def kind(request, monkeypatch):
+    """the setting of IYK_HIP_CB_KERNEL the test's id names"""
+    if request.param == "wg":
+        monkeypatch.setenv(KNOB, "wg")
+    else:
+        monkeypatch.delenv(KNOB, raising=False)
+    return request.param
+
+
+def _form(gpu, kind, count):
+    """asserts, before a launch of `count` rotations, that the batch will run the form the id names, and returns it: 0 under `wg`;
+    unset, what dispatch::cb_plan answers for that count on this device"""
+    hip, _, _, _, torch = gpu
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    rc, want, _ = plan(count, cus, lat_emul().iyk_emul_cb_kind(b"wg" if kind == "wg" else None, 1))
+    assert rc == 0 and (kind != "wg" or want == 0)
+    assert hip.cb_rotate_form(count) == want, (kind, count)
+    return want
 
 
 def _arena(gpu, tlwes):
@@ -55,13 +84,16 @@ def _key(gpu, name):
     return made[name]
 
 
-def _run(gpu, key, tlwes, jobs, slots, stream=None):
-    """jobs: (in, sign, off, mu, out) -> the whole store u64 [slots][N2 + 1] after the batch, FILL where nothing wrote"""
+def _run(gpu, key, tlwes, jobs, slots, stream=None, kind=None):
+    """jobs: (in, sign, off, mu, out) -> the whole store u64 [slots][N2 + 1] after the batch, FILL where nothing wrote.  kind: the
+    knob's setting whose form is asserted just before the launch"""
     hip, _, st, _, _ = gpu
     st = stream or st
     arena, store = _arena(gpu, tlwes), hip.Tlwe2(N2, slots)
     try:
         store.upload(st, 0, np.full((slots, N2 + 1), FILL, dtype=np.uint64))
+        if kind is not None:
+            _form(gpu, kind, len(jobs))
         st.cb_rotate_batch(key, arena, *zip(*[(j[0], j[1], j[2], j[3]) for j in jobs]), store, [j[4] for j in jobs])
         return store.download(st, 0, slots)
     finally:
@@ -69,12 +101,13 @@ def _run(gpu, key, tlwes, jobs, slots, stream=None):
 
 
 @pytest.mark.parametrize("name", cases.CASES)
-def test_cases_word_for_word(gpu, name):
+def test_cases_word_for_word(gpu, kind, name):
     bk, jobs = cases.case(name)
     want = cases.expected(name)
     tl = np.stack([j[0] for j in jobs])
     out = list(range(len(jobs)))[::-1]
-    got = _run(gpu, _key(gpu, name), tl, [(g, s, off, mu, out[g]) for g, (_, s, off, mu) in enumerate(jobs)], len(jobs) + 1)
+    got = _run(gpu, _key(gpu, name), tl, [(g, s, off, mu, out[g]) for g, (_, s, off, mu) in enumerate(jobs)], len(jobs) + 1,
+               kind=kind)
     for g in range(len(jobs)):
         bad = np.flatnonzero(got[out[g]] != want[g])
         assert bad.size == 0, (name, g, bad[:8])
@@ -128,7 +161,7 @@ def _check(got, jobs, slots):
 
 
 @pytest.mark.parametrize("count", [1, 3, 27, "2cus+1"])
-def test_batch_shapes(gpu, count):
+def test_batch_shapes(gpu, kind, count):
     import torch
 
     cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -136,10 +169,10 @@ def test_batch_shapes(gpu, count):
     slots = count + 3 if count > 1 else 2
     jobs = _n2_jobs(count, slots)
     assert len({j[4] for j in jobs}) == count and {0, slots - 1} <= {j[4] for j in jobs} | ({0, 1} if count == 1 else set())
-    _check(_run(gpu, _key(gpu, "uniform-n2"), _n2_inputs(), jobs, slots), jobs, slots)
+    _check(_run(gpu, _key(gpu, "uniform-n2"), _n2_inputs(), jobs, slots, kind=kind), jobs, slots)
 
 
-def test_queued_batches_and_two_streams(gpu):
+def test_queued_batches_and_two_streams(gpu, kind):
     hip, _, st, _, torch = gpu
     key = _key(gpu, "uniform-n2")
     slots = 12
@@ -153,6 +186,8 @@ def test_queued_batches_and_two_streams(gpu):
             s.upload(st, 0, fill)
         st.sync()                                                           # the fills above, before another stream writes s3
         torch.cuda.synchronize()                                            # and the arena's copy, which torch's stream made
+        _form(gpu, kind, len(a))
+        _form(gpu, kind, len(b))
         st.cb_rotate_batch(key, arena, *args(a), s1, [j[4] for j in a])     # the same batch twice without a sync
         st.cb_rotate_batch(key, arena, *args(a), s1, [j[4] for j in a])
         st.cb_rotate_batch(key, arena, *args(a), s2, [j[4] for j in a])     # two different batches back to back
@@ -169,7 +204,7 @@ def test_queued_batches_and_two_streams(gpu):
     _check(g2, [j for j in a if j[4] not in later] + b, slots)
 
 
-def test_refusals_leave_the_store_untouched(gpu):
+def test_refusals_leave_the_store_untouched(gpu, kind):
     hip, _, st, _, _ = gpu
     key = _key(gpu, "uniform-n2")
     arena, store, small = _arena(gpu, _n2_inputs()), hip.Tlwe2(N2, 4), hip.Tlwe2(64, 4)
@@ -177,6 +212,8 @@ def test_refusals_leave_the_store_untouched(gpu):
     mu = [1 << 56]
     try:
         store.upload(st, 0, fill)
+        _form(gpu, kind, 1)                                                         # the widths of the batches below
+        _form(gpu, kind, 2)
         bad = {"duplicate out": ([0, 1], [1, 1], [0, 0], mu * 2, [2, 2]), "in": ([NIN], [1], [0], mu, [0]), "in<0": ([-1], [1], [0], mu, [0]),
                "out": ([0], [1], [0], mu, [4]), "out<0": ([0], [1], [0], mu, [-1]), "sign 0": ([0], [0], [0], mu, [0]),
                "sign 2": ([0], [2], [0], mu, [0])}
@@ -191,6 +228,7 @@ def test_refusals_leave_the_store_untouched(gpu):
             with pytest.raises(hip.IykHipError, match=r"iyk_hip_bk2_key_create failed \(-1\): .+"):
                 hip.Bk2Key(n, l2, bg)
         assert np.array_equal(store.download(st, 0, 4), fill)
+        _form(gpu, kind, 1)
         st.cb_rotate_batch(key, arena, [1], [1], [0], mu, store, [3])               # and the stream still works
         got = store.download(st, 0, 4)
         _check(got, [(1, 1, 0, mu[0], 3)], 4)
@@ -219,7 +257,7 @@ def test_key_of_another_replica_is_refused(gpu):
     assert hip.bk2_key_bytes(1) == 0
 
 
-def test_upload_in_windows_and_key_bytes(gpu):
+def test_upload_in_windows_and_key_bytes(gpu, kind):
     hip, _, st, made, _ = gpu
     bk, jobs = cases.case("uniform-n5")
     before = hip.bk2_key_bytes(0)
@@ -231,8 +269,8 @@ def test_upload_in_windows_and_key_bytes(gpu):
     try:
         tl = np.stack([j[0] for j in jobs])
         js = [(g, s, off, mu, g) for g, (_, s, off, mu) in enumerate(jobs)]
-        a = _run(gpu, whole, tl, js, len(jobs))
-        b = _run(gpu, _key(gpu, "uniform-n5"), tl, js, len(jobs))   # 1 step, then the rest
+        a = _run(gpu, whole, tl, js, len(jobs), kind=kind)
+        b = _run(gpu, _key(gpu, "uniform-n5"), tl, js, len(jobs), kind=kind)   # 1 step, then the rest
     finally:
         whole.free()
     assert np.array_equal(a, b) and np.array_equal(a, cases.expected("uniform-n5"))
@@ -240,7 +278,7 @@ def test_upload_in_windows_and_key_bytes(gpu):
 
 
 @pytest.mark.parametrize("name", ["128", "80"])
-def test_full_size_against_the_emulation(gpu, name, request):
+def test_full_size_against_the_emulation(gpu, kind, name, request):
     """n = 636 / 500: a real key uploaded in windows, the l rotations of one address bit; words against the emulation"""
     hip, _, st, _, _ = gpu
     keys = request.getfixturevalue("keys" + name)
@@ -253,7 +291,7 @@ def test_full_size_against_the_emulation(gpu, name, request):
         for first in range(0, p.n, 200):
             key.upload(st, first, bk[first:first + 200])
         mus = [ref.mu_of(r, p.Bgbit) for r in range(p.l)]
-        got = _run(gpu, key, ct, [(0, 1, 0, mu, r) for r, mu in enumerate(mus)], p.l)
+        got = _run(gpu, key, ct, [(0, 1, 0, mu, r) for r, mu in enumerate(mus)], p.l, kind=kind)
     finally:
         key.free()
     ntt = cases.key_ntt(bk)
@@ -265,7 +303,7 @@ _PRIVKS_ROWS = {}
 
 
 @pytest.mark.parametrize("invert", [False, True])
-def test_selectors_from_tlwe0(gpu, invert, request):
+def test_selectors_from_tlwe0(gpu, kind, invert, request):
     """a 3-bit address at n = 5, a uniform private key-switching key (n_in = 2048, t = 1, basebit = 1): selectors_from_tlwe0 gives the
     selector slots selectors_from_tlwe2 gives from the downloaded rotation outputs — compared through a ROM read on known rows — and the
     rotation outputs are the emulation's words.  The read row is the restatements' (privks_ref on those words, cmux_ref's exact CMUX
@@ -287,6 +325,7 @@ def test_selectors_from_tlwe0(gpu, invert, request):
     ta, tb, scratch = hip.Tlwe2(N2, A * l + 1), hip.Tlwe2(N2, A * l + 1), hip.Trlwe(A * per)
     rom = cmux.Rom(st, data, A, int(p.N).bit_length() - 1, max_reads=1)
     try:
+        _form(gpu, kind, A * l)                                                     # the one rotation batch of selectors_from_tlwe0
         cmux.selectors_from_tlwe0(st, _key(gpu, "uniform-n5"), pk, arena0, [2, 0, 1], ta, 1, scratch, rom.trgsw, invert=invert)
         rom.read(None, out_arena, np.arange(p.N).reshape(1, p.N), resident=True)
         row_a = rom.trlwe.download(st, rom.row(0, rom.layout.result), 1)[0]
