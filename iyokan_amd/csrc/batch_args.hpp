@@ -348,74 +348,73 @@ inline Refusal cmux_lanes_reach(uint64_t trgsw_slots, uint64_t trlwe_slots, uint
     return ACCEPT;
 }
 
-inline Refusal cmux_batch_lanes_args(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* sel, const int32_t* in0,
-                                     const int32_t* in1, const int32_t* rot, const int32_t* out, uint64_t lanes, uint64_t sel_stride,
-                                     uint64_t row_stride, std::vector<CmuxJob>& jobs)
+// The frame the four checkers below share: (d), then the parent's check (a), which fills the list(s), then `reach` — the kernel's own
+// lines: the rows and selector slots ONE lane's list(s) touch — into (b) and (c).  list: the step list, rotate_chain alone (else null);
+// its sum(steps) x lanes entries stay inside the 32-bit CmuxRotChainJob::first.  A refusal leaves the list(s) empty.
+template <class Job, class Parent, class Reach>
+Refusal cmux_lanes_args(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, uint64_t lanes, uint64_t sel_stride, uint64_t row_stride,
+                        std::vector<Job>& jobs, std::vector<CmuxRotStep>* list, Parent parent, Reach reach)
 {
     auto checked = [&]() -> Refusal {
         if (Refusal r = cmux_lanes_counts(count, lanes, sel_stride, row_stride)) return r;
-        if (Refusal r = check_cmux_batch(trgsw_slots, trlwe_slots, count, sel, in0, in1, rot, out, jobs)) return r;
+        if (Refusal r = parent()) return r;
+        if (list && (uint64_t)list->size() * lanes > (uint64_t)INT32_MAX) return invalid("batch too large: more than 2^31 - 1 steps");
         LaneReach m;
-        for (const CmuxJob& j : jobs) {
-            m.sel(j.sel), m.row(j.in0), m.row(j.out);
-            if (j.in1 >= 0) m.row(j.in1);
-        }
+        reach(m);
         return cmux_lanes_reach(trgsw_slots, trlwe_slots, lanes, sel_stride, row_stride, m);
     };
     const Refusal r = checked();
     if (r) jobs.clear();
+    if (r && list) list->clear();
     return r;
+}
+
+inline Refusal cmux_batch_lanes_args(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* sel, const int32_t* in0,
+                                     const int32_t* in1, const int32_t* rot, const int32_t* out, uint64_t lanes, uint64_t sel_stride,
+                                     uint64_t row_stride, std::vector<CmuxJob>& jobs)
+{
+    return cmux_lanes_args(trgsw_slots, trlwe_slots, count, lanes, sel_stride, row_stride, jobs, nullptr,
+        [&] { return check_cmux_batch(trgsw_slots, trlwe_slots, count, sel, in0, in1, rot, out, jobs); },
+        [&](LaneReach& m) {
+            for (const CmuxJob& j : jobs) {
+                m.sel(j.sel), m.row(j.in0), m.row(j.out);
+                if (j.in1 >= 0) m.row(j.in1);
+            }
+        });
 }
 
 inline Refusal cmux_chain_batch_lanes_args(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* sel0, const int32_t* steps,
                                            const uint32_t* pattern, const int32_t* src, const int32_t* mem, const int32_t* out, uint64_t lanes,
                                            uint64_t sel_stride, uint64_t row_stride, std::vector<CmuxChainJob>& jobs)
 {
-    auto checked = [&]() -> Refusal {
-        if (Refusal r = cmux_lanes_counts(count, lanes, sel_stride, row_stride)) return r;
-        if (Refusal r = check_cmux_chain_batch(trgsw_slots, trlwe_slots, count, sel0, steps, pattern, src, mem, out, jobs)) return r;
-        LaneReach m;
-        for (const CmuxChainJob& j : jobs) m.sel((int64_t)j.sel0 + j.steps - 1), m.row(j.src), m.row(j.mem), m.row(j.out);
-        return cmux_lanes_reach(trgsw_slots, trlwe_slots, lanes, sel_stride, row_stride, m);
-    };
-    const Refusal r = checked();
-    if (r) jobs.clear();
-    return r;
+    return cmux_lanes_args(trgsw_slots, trlwe_slots, count, lanes, sel_stride, row_stride, jobs, nullptr,
+        [&] { return check_cmux_chain_batch(trgsw_slots, trlwe_slots, count, sel0, steps, pattern, src, mem, out, jobs); },
+        [&](LaneReach& m) {
+            for (const CmuxChainJob& j : jobs) m.sel((int64_t)j.sel0 + j.steps - 1), m.row(j.src), m.row(j.mem), m.row(j.out);
+        });
 }
 
-// also: sum(steps) x lanes entries of the expanded step list stay inside the 32-bit CmuxRotChainJob::first
 inline Refusal cmux_rotate_chain_batch_lanes_args(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* steps, const int32_t* sel,
                                                   const int32_t* rot, const int32_t* src, const int32_t* out, uint64_t lanes, uint64_t sel_stride,
                                                   uint64_t row_stride, std::vector<CmuxRotChainJob>& jobs, std::vector<CmuxRotStep>& list)
 {
-    auto checked = [&]() -> Refusal {
-        if (Refusal r = cmux_lanes_counts(count, lanes, sel_stride, row_stride)) return r;
-        if (Refusal r = cmux_rotate_chain_args(trgsw_slots, trlwe_slots, count, steps, sel, rot, src, out, jobs, list)) return r;
-        if ((uint64_t)list.size() * lanes > (uint64_t)INT32_MAX) return invalid("batch too large: more than 2^31 - 1 steps");
-        LaneReach m;
-        for (const CmuxRotChainJob& j : jobs) m.row(j.src), m.row(j.out);
-        for (const CmuxRotStep& s : list) m.sel(s.sel);
-        return cmux_lanes_reach(trgsw_slots, trlwe_slots, lanes, sel_stride, row_stride, m);
-    };
-    const Refusal r = checked();
-    if (r) jobs.clear(), list.clear();
-    return r;
+    return cmux_lanes_args(trgsw_slots, trlwe_slots, count, lanes, sel_stride, row_stride, jobs, &list,
+        [&] { return cmux_rotate_chain_args(trgsw_slots, trlwe_slots, count, steps, sel, rot, src, out, jobs, list); },
+        [&](LaneReach& m) {
+            for (const CmuxRotChainJob& j : jobs) m.row(j.src), m.row(j.out);
+            for (const CmuxRotStep& s : list) m.sel(s.sel);
+        });
 }
 
 inline Refusal cmux_tree_batch_lanes_args(uint64_t trgsw_slots, uint64_t trlwe_slots, uint64_t count, const int32_t* sel0, const int32_t* levels,
                                           const int32_t* first, const int32_t* out, uint64_t lanes, uint64_t sel_stride, uint64_t row_stride,
                                           std::vector<CmuxTreeJob>& jobs)
 {
-    auto checked = [&]() -> Refusal {
-        if (Refusal r = cmux_lanes_counts(count, lanes, sel_stride, row_stride)) return r;
-        if (Refusal r = cmux_tree_args(trgsw_slots, trlwe_slots, count, sel0, levels, first, out, jobs)) return r;
-        LaneReach m;
-        for (const CmuxTreeJob& j : jobs) m.sel((int64_t)j.sel0 + j.levels - 1), m.row(j.first), m.row((int64_t)j.first + (1 << j.levels) - 1), m.row(j.out);
-        return cmux_lanes_reach(trgsw_slots, trlwe_slots, lanes, sel_stride, row_stride, m);
-    };
-    const Refusal r = checked();
-    if (r) jobs.clear();
-    return r;
+    return cmux_lanes_args(trgsw_slots, trlwe_slots, count, lanes, sel_stride, row_stride, jobs, nullptr,
+        [&] { return cmux_tree_args(trgsw_slots, trlwe_slots, count, sel0, levels, first, out, jobs); },
+        [&](LaneReach& m) {
+            for (const CmuxTreeJob& j : jobs) m.sel((int64_t)j.sel0 + j.levels - 1), m.row(j.first), m.row((int64_t)j.first + (1 << j.levels) - 1), m.row(j.out);
+        });
 }
 
 // iyk_hip_trlwe_add_batch

@@ -285,21 +285,22 @@ int release_stage(iyk_hip_stream* st)
 
 // The descriptors of one call into one slot of the staging ring: part i starts at the next 16-byte-aligned offset (the slot ends with
 // the last part, so an empty last part pads the one before it), non-empty parts are copied into the pinned half — the caller's arrays
-// are free on return — and ONE copy sends the slot.  d[i]: device address of part i.  The caller records release_stage.
+// are free on return — and ONE copy sends the slot.  d[i]: device address of part i.  The caller records release_stage.  np: the parts
+// in use, where a caller has one that not every call of its has (launch_cmux's step list); the others and their d[i] are left alone.
 struct StagePart {
     const void* src;
     size_t bytes;
 };
 template <size_t NP>
-int stage_put(iyk_hip_stream* st, const StagePart (&parts)[NP], char* (&d)[NP])
+int stage_put(iyk_hip_stream* st, const StagePart (&parts)[NP], char* (&d)[NP], size_t np = NP)
 {
     size_t off[NP], total = 0, soff = 0;
-    for (size_t i = 0; i < NP; ++i) {
+    for (size_t i = 0; i < np; ++i) {
         off[i] = (total + 15) & ~(size_t)15;
         total = off[i] + parts[i].bytes;
     }
     if (int rc = acquire_stage(st, total, &soff)) return rc;
-    for (size_t i = 0; i < NP; ++i) {
+    for (size_t i = 0; i < np; ++i) {
         if (parts[i].bytes) std::memcpy(st->h_stage + soff + off[i], parts[i].src, parts[i].bytes);
         d[i] = st->d_stage + soff + off[i];
     }
@@ -1679,69 +1680,20 @@ int iyk_hip_peer_access(int gpu_a, int gpu_b)
 
 /* ---- the hot path ------------------------------------------------------------------------ */
 
-int iyk_hip_gate_batch(iyk_hip_stream* st, uint32_t* d_arena, uint64_t arena_slots, uint64_t count, const int32_t* ops,
-                       const int32_t* in0, const int32_t* in1, const int32_t* in2, const int32_t* out)
-{
-    IYK_API_BEGIN
-    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
-    if (!st || !d_arena) return fail(IYK_ERR_INVALID, "null argument");
-    if (count == 0) return IYK_OK;
-    if (!ops || !in0 || !in1 || !in2 || !out) return fail(IYK_ERR_INVALID, "null descriptor array");
-    int rc = set_device(st->gpu);
-    if (rc) return rc;
-    const iyk_params& p = G.p;
-    std::vector<RotJob> rot;
-    std::vector<KsJob> ks;
-    std::vector<EwJob> ew;
-    if (const args::Refusal r = args::check_gate_batch(p, G.debug, arena_slots, count, ops, in0, in1, in2, out, rot, ks, ew)) return refuse(r);
-    if ((rc = ensure_rot(st, rot.size()))) return rc;
-    char* d[3];   // the last part is not padded
-    if ((rc = stage_put(st, {{rot.data(), rot.size() * sizeof(RotJob)}, {ks.data(), ks.size() * sizeof(KsJob)}, {ew.data(), ew.size() * sizeof(EwJob)}}, d)))
-        return rc;
-    if ((rc = release_stage(st))) return rc;
+namespace {
 
-    if (!ew.empty()) {
-        hipLaunchKernelGGL(elementwise_kernel, dim3((unsigned)ew.size()), dim3(256), 0, st->s, d_arena, (const EwJob*)d[2], p.n, p.mu);
-        HIP_TRY(hipGetLastError());
-    }
-    st->timing_valid = false;
-    if (!rot.empty()) {
-        if ((rc = begin_timing(st))) return rc;
-        if ((rc = launch_blind_rotate(st, d_arena, (const RotJob*)d[0], (int)rot.size(), RotOut{st->d_rot, nullptr, 0})))
-            return rc;
-        HIP_TRY(hipEventRecord(st->ev_br1, st->s));
-        if ((rc = launch_keyswitch(st, d_arena, (const KsJob*)d[1], (int)ks.size()))) return rc;
-        HIP_TRY(hipEventRecord(st->ev_ks1, st->s));
-        st->timing_valid = true;
-        st->timing_has_ks = true;
-    }
-    return IYK_OK;
-    IYK_API_END
-}
-
-// iyk_hip_gate_batch for `lanes` copies of one circuit's arena image, lane r in slots [r * lane_stride, (r + 1) * lane_stride): the
-// descriptors are one lane's.  One lane's lists are staged, lane_jobs_kernel writes the lists of all lanes into the stream's d_lane
-// (lane-major), and the elementwise, rotation and key-switch launches of iyk_hip_gate_batch run them as ONE batch of count x lanes
-// jobs — kernel and grid chosen for that total.  lanes == 1: the staged lists are the batch, nothing is expanded.
-int iyk_hip_gate_batch_lanes(iyk_hip_stream* st, uint32_t* d_arena, uint64_t arena_slots, uint64_t count, const int32_t* ops,
-                             const int32_t* in0, const int32_t* in1, const int32_t* in2, const int32_t* out, uint64_t lanes,
-                             uint64_t lane_stride)
+// The launch body of iyk_hip_gate_batch and iyk_hip_gate_batch_lanes, on the lists of ONE lane that the caller's checker has accepted:
+// everything that grows (rotation buffer, lane scratch) first, then stage and release, then the launches.  lanes > 1: lane_jobs_kernel
+// writes the lists of all lanes into the stream's d_lane (lane-major), lane r at slots + r * lane_stride, and the elementwise, rotation
+// and key-switch launches run them as ONE batch of count x lanes jobs — kernel and grid chosen for that total.  lanes == 1: the staged
+// lists are the batch, nothing is expanded and d_lane is not touched.
+int launch_gates(iyk_hip_stream* st, uint32_t* d_arena, const std::vector<RotJob>& rot, const std::vector<KsJob>& ks, const std::vector<EwJob>& ew,
+                 uint64_t lanes, uint64_t lane_stride)
 {
-    IYK_API_BEGIN
-    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
-    if (!st || !d_arena) return fail(IYK_ERR_INVALID, "null argument");
-    if (count == 0) return IYK_OK;
-    if (!ops || !in0 || !in1 || !in2 || !out) return fail(IYK_ERR_INVALID, "null descriptor array");
-    int rc = set_device(st->gpu);
-    if (rc) return rc;
     const iyk_params& p = G.p;
-    std::vector<RotJob> rot;
-    std::vector<KsJob> ks;
-    std::vector<EwJob> ew;
-    if (const args::Refusal r = args::gate_batch_lanes_args(p, G.debug, arena_slots, count, ops, in0, in1, in2, out, lanes, lane_stride, rot, ks, ew))
-        return refuse(r);
     const size_t nrot = rot.size() * lanes, nks = ks.size() * lanes, new_ = ew.size() * lanes;   // of all lanes
     const LaneScratch ls = lane_scratch(rot.size(), ks.size(), ew.size(), lanes);
+    int rc;
     if ((rc = ensure_rot(st, nrot))) return rc;
     if (lanes > 1 && (rc = ensure_lane(st, ls.bytes))) return rc;
     char* d[3];   // the last part is not padded
@@ -1772,6 +1724,46 @@ int iyk_hip_gate_batch_lanes(iyk_hip_stream* st, uint32_t* d_arena, uint64_t are
         st->timing_has_ks = true;
     }
     return IYK_OK;
+}
+
+}  // namespace
+
+// The lanes == 1 case of launch_gates, with the parent's checker (check_gate_batch: `batch too large`, the arena as the one lane).
+int iyk_hip_gate_batch(iyk_hip_stream* st, uint32_t* d_arena, uint64_t arena_slots, uint64_t count, const int32_t* ops,
+                       const int32_t* in0, const int32_t* in1, const int32_t* in2, const int32_t* out)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    if (!st || !d_arena) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    if (!ops || !in0 || !in1 || !in2 || !out) return fail(IYK_ERR_INVALID, "null descriptor array");
+    if (int rc = set_device(st->gpu)) return rc;
+    std::vector<RotJob> rot;
+    std::vector<KsJob> ks;
+    std::vector<EwJob> ew;
+    if (const args::Refusal r = args::check_gate_batch(G.p, G.debug, arena_slots, count, ops, in0, in1, in2, out, rot, ks, ew)) return refuse(r);
+    return launch_gates(st, d_arena, rot, ks, ew, 1, 0);
+    IYK_API_END
+}
+
+// iyk_hip_gate_batch for `lanes` copies of one circuit's arena image, lane r in slots [r * lane_stride, (r + 1) * lane_stride): the
+// descriptors are one lane's.  Its own checker (gate_batch_lanes_args, also when lanes == 1), then launch_gates on count x lanes jobs.
+int iyk_hip_gate_batch_lanes(iyk_hip_stream* st, uint32_t* d_arena, uint64_t arena_slots, uint64_t count, const int32_t* ops,
+                             const int32_t* in0, const int32_t* in1, const int32_t* in2, const int32_t* out, uint64_t lanes,
+                             uint64_t lane_stride)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    if (!st || !d_arena) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    if (!ops || !in0 || !in1 || !in2 || !out) return fail(IYK_ERR_INVALID, "null descriptor array");
+    if (int rc = set_device(st->gpu)) return rc;
+    std::vector<RotJob> rot;
+    std::vector<KsJob> ks;
+    std::vector<EwJob> ew;
+    if (const args::Refusal r = args::gate_batch_lanes_args(G.p, G.debug, arena_slots, count, ops, in0, in1, in2, out, lanes, lane_stride, rot, ks, ew))
+        return refuse(r);
+    return launch_gates(st, d_arena, rot, ks, ew, lanes, lane_stride);
     IYK_API_END
 }
 
@@ -2222,6 +2214,110 @@ int iyk_hip_trgsw_upload(iyk_hip_stream* st, void* d_trgsw, uint64_t trgsw_slots
     IYK_API_END
 }
 
+}  // extern "C"
+
+// ---- batched CMUX, one lane or many (cmux_fft.hpp, cmux_lane_jobs.hpp) -------------------------------------------------------------
+// Four kernels, each behind a plain and a _lanes entry point.  An entry point checks (batch_args.hpp, nothing staged on a refusal) and
+// calls launch_cmux on ONE lane's accepted list(s): that is the one body of each kernel — lane scratch, stage, expand on the device
+// into the stream's lane scratch, the parent's UNCHANGED kernel on count x lanes jobs with the grid from that total, release.  The
+// plain entry point is the lanes == 1 case with the parent's checker (`batch too large`); the _lanes entry point calls its
+// *_lanes_args, also when lanes == 1 (`batch too large: count x lanes`).  lanes == 1: the kernel reads the staged list, nothing is
+// expanded, d_lane and ensure_lane are not touched.
+namespace {
+
+// The staged list(s) of one lane -> those of all lanes in st->d_lane, which ensure_lane has sized; jobs / steps: in, the staged ones,
+// out, what the kernel reads.
+template <class Job>
+int expand_cmux_lanes(iyk_hip_stream* st, size_t n, size_t nsteps, uint32_t lanes, uint64_t sel_stride, uint64_t row_stride, const Job*& jobs,
+                      const CmuxRotStep*& steps)
+{
+    const CmuxLaneScratch ls = cmux_lane_scratch(n, sizeof(Job), nsteps, lanes);
+    const CmuxLaneLists<Job> L{jobs, steps, (Job*)st->d_lane, (CmuxRotStep*)(st->d_lane + ls.step_off), (uint32_t)n, (uint32_t)nsteps, lanes,
+                               (uint32_t)sel_stride, (uint32_t)row_stride};
+    hipLaunchKernelGGL(cmux_lane_jobs_kernel<Job>, dim3(lane_jobs_grid(lane_cmux_total(L))), dim3(LANE_JOBS_THREADS), 0, st->s, L);
+    HIP_TRY(hipGetLastError());
+    jobs = L.job, steps = L.step;
+    return IYK_OK;
+}
+
+// What differs between the four kernels, once each: the job type, the kernel template, its grid for `total` jobs, its argument order.
+struct CmuxTarget {
+    iyk_hip_stream* st;
+    const fft::cplx* d_trgsw;
+    uint32_t* d_trlwe;
+};
+struct CmuxOne {
+    typedef CmuxJob Job;
+    template <class GD>
+    static void launch(const CmuxTarget& t, const Device& D, const Job* jobs, const CmuxRotStep*, uint64_t total)
+    {
+        auto kern = G.debug ? cmux_fft_kernel<GD, true> : cmux_fft_kernel<GD, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((total + BR_WAVES - 1) / BR_WAVES)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, t.st->s, jobs, (int)total,
+                           t.d_trgsw, t.d_trlwe, &D.fftc->c, D.fft_err);
+    }
+};
+struct CmuxChain {
+    typedef CmuxChainJob Job;
+    template <class GD>
+    static void launch(const CmuxTarget& t, const Device& D, const Job* jobs, const CmuxRotStep*, uint64_t total)
+    {
+        auto kern = G.debug ? cmux_chain_kernel<GD, true> : cmux_chain_kernel<GD, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((total + BR_WAVES - 1) / BR_WAVES)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, t.st->s, jobs, (int)total,
+                           t.d_trgsw, t.d_trlwe, &D.fftc->c, D.fft_err);
+    }
+};
+struct CmuxRotChain {
+    typedef CmuxRotChainJob Job;
+    template <class GD>
+    static void launch(const CmuxTarget& t, const Device& D, const Job* jobs, const CmuxRotStep* steps, uint64_t total)
+    {
+        auto kern = G.debug ? cmux_rotate_chain_kernel<GD, true> : cmux_rotate_chain_kernel<GD, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)cmux_rotate_chain_grid((long)total)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, t.st->s, jobs, (int)total,
+                           steps, t.d_trgsw, t.d_trlwe, &D.fftc->c, D.fft_err);
+    }
+};
+struct CmuxTree {
+    typedef CmuxTreeJob Job;
+    template <class GD>
+    static void launch(const CmuxTarget& t, const Device& D, const Job* jobs, const CmuxRotStep*, uint64_t total)
+    {
+        auto kern = G.debug ? cmux_tree_kernel<GD, true> : cmux_tree_kernel<GD, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)cmux_tree_grid((long)total)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, t.st->s, jobs, t.d_trgsw, t.d_trlwe,
+                           &D.fftc->c, D.fft_err);
+    }
+};
+
+// lane scratch, stage, expand, launch, release of kernel K on the accepted list of ONE lane; list: that lane's steps, rotate_chain
+// alone (else null).  Nothing here refuses, and nothing grows after stage_put.  release_stage comes after the kernel: the slot holds
+// what the kernel (lanes == 1) or the expansion reads.
+template <class K>
+int launch_cmux(iyk_hip_stream* st, const void* d_trgsw, uint32_t* d_trlwe, const std::vector<typename K::Job>& jobs, const std::vector<CmuxRotStep>* list,
+                uint32_t lanes, uint64_t sel_stride, uint64_t row_stride)
+{
+    typedef typename K::Job Job;
+    const size_t count = jobs.size(), nsteps = list ? list->size() : 0;
+    int rc;
+    if (lanes > 1 && (rc = ensure_lane(st, cmux_lane_scratch(count, sizeof(Job), nsteps, lanes).bytes))) return rc;
+    char* d[2] = {nullptr, nullptr};   // the step list is a part of its own only where there is one
+    if ((rc = stage_put(st, {{jobs.data(), count * sizeof(Job)}, {list ? list->data() : nullptr, nsteps * sizeof(CmuxRotStep)}}, d, list ? 2 : 1))) return rc;
+    const Job* dj = (const Job*)d[0];
+    const CmuxRotStep* ds = (const CmuxRotStep*)d[1];
+    if (lanes > 1 && (rc = expand_cmux_lanes<Job>(st, count, nsteps, lanes, sel_stride, row_stride, dj, ds))) return rc;
+    const uint64_t total = (uint64_t)count * lanes;
+    const CmuxTarget t{st, (const fft::cplx*)d_trgsw, d_trlwe};
+    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
+        K::template launch<decltype(gd)>(t, G.devs[st->gpu], dj, ds, total);
+        HIP_TRY(hipGetLastError());
+        return (int)IYK_OK;
+    });
+    if (rc) return rc;
+    return release_stage(st);
+}
+
+}  // namespace
+
+extern "C" {
+
 int iyk_hip_cmux_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
                        uint64_t count, const int32_t* sel, const int32_t* in0, const int32_t* in1, const int32_t* rot,
                        const int32_t* out)
@@ -2230,23 +2326,26 @@ int iyk_hip_cmux_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_s
     if (int rc = need_fft_path("iyk_hip_cmux_batch")) return rc;
     if (!st || !d_trgsw || !d_trlwe || !sel || !in0 || !in1 || !rot || !out) return fail(IYK_ERR_INVALID, "null argument");
     if (count == 0) return IYK_OK;
-    int rc = set_device(st->gpu);
-    if (rc) return rc;
+    if (int rc = set_device(st->gpu)) return rc;
     std::vector<CmuxJob> jobs;
     if (const args::Refusal r = args::check_cmux_batch(trgsw_slots, trlwe_slots, count, sel, in0, in1, rot, out, jobs)) return refuse(r);
-    char* d[1];
-    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxJob)}}, d))) return rc;
-    const Device& D = G.devs[st->gpu];
-    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
-        typedef decltype(gd) GD;
-        auto kern = G.debug ? cmux_fft_kernel<GD, true> : cmux_fft_kernel<GD, false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((count + BR_WAVES - 1) / BR_WAVES)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s,
-                           (const CmuxJob*)d[0], (int)count, (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
-        HIP_TRY(hipGetLastError());
-        return (int)IYK_OK;
-    });
-    if (rc) return rc;
-    return release_stage(st);
+    return launch_cmux<CmuxOne>(st, d_trgsw, d_trlwe, jobs, nullptr, 1, 0, 0);
+    IYK_API_END
+}
+
+int iyk_hip_cmux_batch_lanes(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
+                             uint64_t count, const int32_t* sel, const int32_t* in0, const int32_t* in1, const int32_t* rot,
+                             const int32_t* out, uint32_t lanes, uint64_t sel_stride, uint64_t row_stride)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_cmux_batch_lanes")) return rc;
+    if (!st || !d_trgsw || !d_trlwe || !sel || !in0 || !in1 || !rot || !out) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    if (int rc = set_device(st->gpu)) return rc;
+    std::vector<CmuxJob> jobs;
+    if (const args::Refusal r = args::cmux_batch_lanes_args(trgsw_slots, trlwe_slots, count, sel, in0, in1, rot, out, lanes, sel_stride, row_stride, jobs))
+        return refuse(r);
+    return launch_cmux<CmuxOne>(st, d_trgsw, d_trlwe, jobs, nullptr, lanes, sel_stride, row_stride);
     IYK_API_END
 }
 
@@ -2258,140 +2357,10 @@ int iyk_hip_cmux_chain_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t t
     if (int rc = need_fft_path("iyk_hip_cmux_chain_batch")) return rc;
     if (!st || !d_trgsw || !d_trlwe || !sel0 || !steps || !pattern || !src || !mem || !out) return fail(IYK_ERR_INVALID, "null argument");
     if (count == 0) return IYK_OK;
-    int rc = set_device(st->gpu);
-    if (rc) return rc;
+    if (int rc = set_device(st->gpu)) return rc;
     std::vector<CmuxChainJob> jobs;
     if (const args::Refusal r = args::check_cmux_chain_batch(trgsw_slots, trlwe_slots, count, sel0, steps, pattern, src, mem, out, jobs)) return refuse(r);
-    char* d[1];
-    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxChainJob)}}, d))) return rc;
-    const Device& D = G.devs[st->gpu];
-    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
-        typedef decltype(gd) GD;
-        auto kern = G.debug ? cmux_chain_kernel<GD, true> : cmux_chain_kernel<GD, false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((count + BR_WAVES - 1) / BR_WAVES)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s,
-                           (const CmuxChainJob*)d[0], (int)count, (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
-        HIP_TRY(hipGetLastError());
-        return (int)IYK_OK;
-    });
-    if (rc) return rc;
-    return release_stage(st);
-    IYK_API_END
-}
-
-int iyk_hip_cmux_rotate_chain_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
-                                    uint64_t count, const int32_t* steps, const int32_t* sel, const int32_t* rot, const int32_t* src,
-                                    const int32_t* out)
-{
-    IYK_API_BEGIN
-    if (int rc = need_fft_path("iyk_hip_cmux_rotate_chain_batch")) return rc;
-    if (!st || !d_trgsw || !d_trlwe || !steps || !sel || !rot || !src || !out) return fail(IYK_ERR_INVALID, "null argument");
-    if (count == 0) return IYK_OK;
-    int rc = set_device(st->gpu);
-    if (rc) return rc;
-    std::vector<CmuxRotChainJob> jobs;
-    std::vector<CmuxRotStep> list;
-    if (const args::Refusal r = args::cmux_rotate_chain_args(trgsw_slots, trlwe_slots, count, steps, sel, rot, src, out, jobs, list))
-        return refuse(r);
-    char* d[2];
-    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxRotChainJob)}, {list.data(), list.size() * sizeof(CmuxRotStep)}}, d))) return rc;
-    const Device& D = G.devs[st->gpu];
-    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
-        typedef decltype(gd) GD;
-        auto kern = G.debug ? cmux_rotate_chain_kernel<GD, true> : cmux_rotate_chain_kernel<GD, false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)cmux_rotate_chain_grid((long)count)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s,
-                           (const CmuxRotChainJob*)d[0], (int)count, (const CmuxRotStep*)d[1], (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c,
-                           D.fft_err);
-        HIP_TRY(hipGetLastError());
-        return (int)IYK_OK;
-    });
-    if (rc) return rc;
-    return release_stage(st);
-    IYK_API_END
-}
-
-int iyk_hip_cmux_tree_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
-                            uint64_t count, const int32_t* sel0, const int32_t* levels, const int32_t* first, const int32_t* out)
-{
-    IYK_API_BEGIN
-    if (int rc = need_fft_path("iyk_hip_cmux_tree_batch")) return rc;
-    if (!st || !d_trgsw || !d_trlwe || !sel0 || !levels || !first || !out) return fail(IYK_ERR_INVALID, "null argument");
-    if (count == 0) return IYK_OK;
-    int rc = set_device(st->gpu);
-    if (rc) return rc;
-    std::vector<CmuxTreeJob> jobs;
-    if (const args::Refusal r = args::cmux_tree_args(trgsw_slots, trlwe_slots, count, sel0, levels, first, out, jobs)) return refuse(r);
-    char* d[1];
-    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxTreeJob)}}, d))) return rc;
-    const Device& D = G.devs[st->gpu];
-    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
-        typedef decltype(gd) GD;
-        auto kern = G.debug ? cmux_tree_kernel<GD, true> : cmux_tree_kernel<GD, false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)cmux_tree_grid((long)count)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s,
-                           (const CmuxTreeJob*)d[0], (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
-        HIP_TRY(hipGetLastError());
-        return (int)IYK_OK;
-    });
-    if (rc) return rc;
-    return release_stage(st);
-    IYK_API_END
-}
-
-}  // extern "C"
-
-// ---- CMUX memories per lane (cmux_lane_jobs.hpp) ---------------------------------------------------------------------------------
-// The four entry points below: check (batch_args.hpp: *_lanes_args, nothing staged on a refusal), stage ONE lane's list, expand it on
-// the device into the stream's lane scratch, launch the parent's UNCHANGED kernel on count x lanes jobs, the grid from that total.
-namespace {
-
-// The staged list(s) of one lane -> those of all lanes in st->d_lane, which ensure_lane has sized; jobs / steps: what the kernel reads.
-template <class Job>
-int expand_cmux_lanes(iyk_hip_stream* st, const char* d_job1, const char* d_step1, size_t n, size_t nsteps, uint32_t lanes, uint64_t sel_stride,
-                      uint64_t row_stride, const Job** jobs, const CmuxRotStep** steps)
-{
-    const CmuxLaneScratch ls = cmux_lane_scratch(n, sizeof(Job), nsteps, lanes);
-    const CmuxLaneLists<Job> L{(const Job*)d_job1, (const CmuxRotStep*)d_step1, (Job*)st->d_lane, (CmuxRotStep*)(st->d_lane + ls.step_off),
-                               (uint32_t)n, (uint32_t)nsteps, lanes, (uint32_t)sel_stride, (uint32_t)row_stride};
-    hipLaunchKernelGGL(cmux_lane_jobs_kernel<Job>, dim3(lane_jobs_grid(lane_cmux_total(L))), dim3(LANE_JOBS_THREADS), 0, st->s, L);
-    HIP_TRY(hipGetLastError());
-    *jobs = L.job;
-    if (steps) *steps = L.step;
-    return IYK_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int iyk_hip_cmux_batch_lanes(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
-                             uint64_t count, const int32_t* sel, const int32_t* in0, const int32_t* in1, const int32_t* rot,
-                             const int32_t* out, uint32_t lanes, uint64_t sel_stride, uint64_t row_stride)
-{
-    IYK_API_BEGIN
-    if (int rc = need_fft_path("iyk_hip_cmux_batch_lanes")) return rc;
-    if (!st || !d_trgsw || !d_trlwe || !sel || !in0 || !in1 || !rot || !out) return fail(IYK_ERR_INVALID, "null argument");
-    if (count == 0) return IYK_OK;
-    int rc = set_device(st->gpu);
-    if (rc) return rc;
-    std::vector<CmuxJob> jobs;
-    if (const args::Refusal r = args::cmux_batch_lanes_args(trgsw_slots, trlwe_slots, count, sel, in0, in1, rot, out, lanes, sel_stride, row_stride, jobs))
-        return refuse(r);
-    if (lanes > 1 && (rc = ensure_lane(st, cmux_lane_scratch(count, sizeof(CmuxJob), 0, lanes).bytes))) return rc;
-    char* d[1];
-    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxJob)}}, d))) return rc;
-    const CmuxJob* dj = (const CmuxJob*)d[0];
-    if (lanes > 1 && (rc = expand_cmux_lanes<CmuxJob>(st, d[0], nullptr, count, 0, lanes, sel_stride, row_stride, &dj, nullptr))) return rc;
-    const uint64_t total = count * lanes;
-    const Device& D = G.devs[st->gpu];
-    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
-        typedef decltype(gd) GD;
-        auto kern = G.debug ? cmux_fft_kernel<GD, true> : cmux_fft_kernel<GD, false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((total + BR_WAVES - 1) / BR_WAVES)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s, dj, (int)total,
-                           (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
-        HIP_TRY(hipGetLastError());
-        return (int)IYK_OK;
-    });
-    if (rc) return rc;
-    return release_stage(st);
+    return launch_cmux<CmuxChain>(st, d_trgsw, d_trlwe, jobs, nullptr, 1, 0, 0);
     IYK_API_END
 }
 
@@ -2403,29 +2372,29 @@ int iyk_hip_cmux_chain_batch_lanes(iyk_hip_stream* st, const void* d_trgsw, uint
     if (int rc = need_fft_path("iyk_hip_cmux_chain_batch_lanes")) return rc;
     if (!st || !d_trgsw || !d_trlwe || !sel0 || !steps || !pattern || !src || !mem || !out) return fail(IYK_ERR_INVALID, "null argument");
     if (count == 0) return IYK_OK;
-    int rc = set_device(st->gpu);
-    if (rc) return rc;
+    if (int rc = set_device(st->gpu)) return rc;
     std::vector<CmuxChainJob> jobs;
     if (const args::Refusal r = args::cmux_chain_batch_lanes_args(trgsw_slots, trlwe_slots, count, sel0, steps, pattern, src, mem, out, lanes, sel_stride,
                                                                   row_stride, jobs))
         return refuse(r);
-    if (lanes > 1 && (rc = ensure_lane(st, cmux_lane_scratch(count, sizeof(CmuxChainJob), 0, lanes).bytes))) return rc;
-    char* d[1];
-    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxChainJob)}}, d))) return rc;
-    const CmuxChainJob* dj = (const CmuxChainJob*)d[0];
-    if (lanes > 1 && (rc = expand_cmux_lanes<CmuxChainJob>(st, d[0], nullptr, count, 0, lanes, sel_stride, row_stride, &dj, nullptr))) return rc;
-    const uint64_t total = count * lanes;
-    const Device& D = G.devs[st->gpu];
-    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
-        typedef decltype(gd) GD;
-        auto kern = G.debug ? cmux_chain_kernel<GD, true> : cmux_chain_kernel<GD, false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((total + BR_WAVES - 1) / BR_WAVES)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s, dj, (int)total,
-                           (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
-        HIP_TRY(hipGetLastError());
-        return (int)IYK_OK;
-    });
-    if (rc) return rc;
-    return release_stage(st);
+    return launch_cmux<CmuxChain>(st, d_trgsw, d_trlwe, jobs, nullptr, lanes, sel_stride, row_stride);
+    IYK_API_END
+}
+
+int iyk_hip_cmux_rotate_chain_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
+                                    uint64_t count, const int32_t* steps, const int32_t* sel, const int32_t* rot, const int32_t* src,
+                                    const int32_t* out)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_cmux_rotate_chain_batch")) return rc;
+    if (!st || !d_trgsw || !d_trlwe || !steps || !sel || !rot || !src || !out) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    if (int rc = set_device(st->gpu)) return rc;
+    std::vector<CmuxRotChainJob> jobs;
+    std::vector<CmuxRotStep> list;
+    if (const args::Refusal r = args::cmux_rotate_chain_args(trgsw_slots, trlwe_slots, count, steps, sel, rot, src, out, jobs, list))
+        return refuse(r);
+    return launch_cmux<CmuxRotChain>(st, d_trgsw, d_trlwe, jobs, &list, 1, 0, 0);
     IYK_API_END
 }
 
@@ -2438,31 +2407,27 @@ int iyk_hip_cmux_rotate_chain_batch_lanes(iyk_hip_stream* st, const void* d_trgs
     if (int rc = need_fft_path("iyk_hip_cmux_rotate_chain_batch_lanes")) return rc;
     if (!st || !d_trgsw || !d_trlwe || !steps || !sel || !rot || !src || !out) return fail(IYK_ERR_INVALID, "null argument");
     if (count == 0) return IYK_OK;
-    int rc = set_device(st->gpu);
-    if (rc) return rc;
+    if (int rc = set_device(st->gpu)) return rc;
     std::vector<CmuxRotChainJob> jobs;
     std::vector<CmuxRotStep> list;
     if (const args::Refusal r = args::cmux_rotate_chain_batch_lanes_args(trgsw_slots, trlwe_slots, count, steps, sel, rot, src, out, lanes, sel_stride,
                                                                          row_stride, jobs, list))
         return refuse(r);
-    if (lanes > 1 && (rc = ensure_lane(st, cmux_lane_scratch(count, sizeof(CmuxRotChainJob), list.size(), lanes).bytes))) return rc;
-    char* d[2];
-    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxRotChainJob)}, {list.data(), list.size() * sizeof(CmuxRotStep)}}, d))) return rc;
-    const CmuxRotChainJob* dj = (const CmuxRotChainJob*)d[0];
-    const CmuxRotStep* ds = (const CmuxRotStep*)d[1];
-    if (lanes > 1 && (rc = expand_cmux_lanes<CmuxRotChainJob>(st, d[0], d[1], count, list.size(), lanes, sel_stride, row_stride, &dj, &ds))) return rc;
-    const uint64_t total = count * lanes;
-    const Device& D = G.devs[st->gpu];
-    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
-        typedef decltype(gd) GD;
-        auto kern = G.debug ? cmux_rotate_chain_kernel<GD, true> : cmux_rotate_chain_kernel<GD, false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)cmux_rotate_chain_grid((long)total)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s, dj, (int)total, ds,
-                           (const fft::cplx*)d_trgsw, d_trlwe, &D.fftc->c, D.fft_err);
-        HIP_TRY(hipGetLastError());
-        return (int)IYK_OK;
-    });
-    if (rc) return rc;
-    return release_stage(st);
+    return launch_cmux<CmuxRotChain>(st, d_trgsw, d_trlwe, jobs, &list, lanes, sel_stride, row_stride);
+    IYK_API_END
+}
+
+int iyk_hip_cmux_tree_batch(iyk_hip_stream* st, const void* d_trgsw, uint64_t trgsw_slots, uint32_t* d_trlwe, uint64_t trlwe_slots,
+                            uint64_t count, const int32_t* sel0, const int32_t* levels, const int32_t* first, const int32_t* out)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_cmux_tree_batch")) return rc;
+    if (!st || !d_trgsw || !d_trlwe || !sel0 || !levels || !first || !out) return fail(IYK_ERR_INVALID, "null argument");
+    if (count == 0) return IYK_OK;
+    if (int rc = set_device(st->gpu)) return rc;
+    std::vector<CmuxTreeJob> jobs;
+    if (const args::Refusal r = args::cmux_tree_args(trgsw_slots, trlwe_slots, count, sel0, levels, first, out, jobs)) return refuse(r);
+    return launch_cmux<CmuxTree>(st, d_trgsw, d_trlwe, jobs, nullptr, 1, 0, 0);
     IYK_API_END
 }
 
@@ -2474,29 +2439,12 @@ int iyk_hip_cmux_tree_batch_lanes(iyk_hip_stream* st, const void* d_trgsw, uint6
     if (int rc = need_fft_path("iyk_hip_cmux_tree_batch_lanes")) return rc;
     if (!st || !d_trgsw || !d_trlwe || !sel0 || !levels || !first || !out) return fail(IYK_ERR_INVALID, "null argument");
     if (count == 0) return IYK_OK;
-    int rc = set_device(st->gpu);
-    if (rc) return rc;
+    if (int rc = set_device(st->gpu)) return rc;
     std::vector<CmuxTreeJob> jobs;
     if (const args::Refusal r = args::cmux_tree_batch_lanes_args(trgsw_slots, trlwe_slots, count, sel0, levels, first, out, lanes, sel_stride, row_stride,
                                                                  jobs))
         return refuse(r);
-    if (lanes > 1 && (rc = ensure_lane(st, cmux_lane_scratch(count, sizeof(CmuxTreeJob), 0, lanes).bytes))) return rc;
-    char* d[1];
-    if ((rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CmuxTreeJob)}}, d))) return rc;
-    const CmuxTreeJob* dj = (const CmuxTreeJob*)d[0];
-    if (lanes > 1 && (rc = expand_cmux_lanes<CmuxTreeJob>(st, d[0], nullptr, count, 0, lanes, sel_stride, row_stride, &dj, nullptr))) return rc;
-    const uint64_t total = count * lanes;
-    const Device& D = G.devs[st->gpu];
-    rc = with_rot_set(G.p, G.split, [&](auto, auto gd) {
-        typedef decltype(gd) GD;
-        auto kern = G.debug ? cmux_tree_kernel<GD, true> : cmux_tree_kernel<GD, false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)cmux_tree_grid((long)total)), dim3(64 * BR_WAVES), BR_FFT_LDS_BYTES, st->s, dj, (const fft::cplx*)d_trgsw,
-                           d_trlwe, &D.fftc->c, D.fft_err);
-        HIP_TRY(hipGetLastError());
-        return (int)IYK_OK;
-    });
-    if (rc) return rc;
-    return release_stage(st);
+    return launch_cmux<CmuxTree>(st, d_trgsw, d_trlwe, jobs, nullptr, lanes, sel_stride, row_stride);
     IYK_API_END
 }
 

@@ -155,7 +155,83 @@ def test_refusals_leave_the_store_unchanged(gpu):
         st.destroy()
 
 
-# ---- Rom / Ram with two lanes -------------------------------------------------------------------------------------------------------------
+# ---- the plain entry point is the lanes == 1 case of the laned one's body, each with its own checker ------------------------------------
+
+@pytest.mark.parametrize("name", ["cmux3-x1", "chain-ram21-x1", "rot31-x1", "tree41-x1"])
+def test_plain_call_and_lanes_call_with_one_lane_give_the_same_words(gpu, store, name):
+    """iyk_hip_<kernel> against iyk_hip_<kernel>_lanes with lanes = 1 (the strides given, so Stream._cmux_call takes the laned symbol), on
+    copies of one store: the same words in every row"""
+    hip, keys = gpu
+    st, sel = store
+    c = _moved(cc.CASES[name])
+    T = _rows(keys, c, 500 + GPU_CASES.index(name))
+    a, b = hip.Trlwe(T.shape[0]), hip.Trlwe(T.shape[0])
+    try:
+        a.upload(st, 0, T)
+        b.upload(st, 0, T)
+        _call(st, sel, a, c["family"], c["arrays"])
+        _call(st, sel, b, c["family"], c["arrays"], lanes=1, sel_stride=c["sel_stride"], row_stride=c["row_stride"])
+        st.sync()
+        plain, laned = a.download(st, 0, T.shape[0]), b.download(st, 0, T.shape[0])
+    finally:
+        a.free()
+        b.free()
+    assert np.array_equal(plain, laned)
+    written = _written(c)
+    assert (plain[written] != T[written]).any(axis=1).all()                                    # every job did run
+
+
+def test_gate_batch_and_gate_batch_lanes_with_one_lane_give_the_same_words(gpu):
+    """four gates, a NOT (elementwise) and a MUX (two rotations) among them, on random arena words (the gates are exact functions of any
+    words): iyk_hip_gate_batch against iyk_hip_gate_batch_lanes with lanes = 1 and the arena as the one lane"""
+    from iyokan_amd.params import OPS
+
+    hip, keys = gpu
+    ops, in0, in1, in2, out = [OPS["NAND"], OPS["NOT"], OPS["MUX"], OPS["XOR"]], [0, 1, 2, 5], [1, -1, 3, 6], [-1, -1, 4, -1], [7, 8, 9, 10]
+    rows = np.random.default_rng([11, 0x6F, 600]).integers(0, 1 << 32, size=(12, keys.params.n + 1), dtype=np.uint64).astype(np.uint32)
+    st = hip.Stream(0)
+    a, b = hip.Arena(len(rows)), hip.Arena(len(rows))
+    try:
+        st.upload(a, 0, rows)
+        st.upload(b, 0, rows)
+        st.gate_batch(a, ops, in0, in1, in2, out)
+        st.gate_batch(b, ops, in0, in1, in2, out, lanes=1, lane_stride=b.slots)
+        st.sync()
+        plain, laned = st.download(a, 0, len(rows)), st.download(b, 0, len(rows))
+    finally:
+        a.free()
+        b.free()
+        st.destroy()
+    assert np.array_equal(plain, laned)
+    assert (plain[out] != rows[out]).any(axis=1).all() and np.array_equal(plain[:7], rows[:7]) and np.array_equal(plain[11], rows[11])
+
+
+def test_too_many_jobs_each_entry_point_refuses_in_its_own_checkers_words(gpu):
+    """2^24 + 1 jobs (np.zeros arrays: pages nobody touches — the count is refused before a job is read or anything is staged): the plain
+    call answers with check_cmux_batch's text, the laned call with lanes = 1 with cmux_batch_lanes_args'; the store stays as uploaded"""
+    hip, keys = gpu
+    count = (1 << 24) + 1
+    z = np.zeros(count, dtype=np.int32)
+    st = hip.Stream(0)
+    sel, trl = hip.Trgsw(4), hip.Trlwe(8)
+    T = np.random.default_rng([11, 0x6F, 700]).integers(0, 1 << 32, size=(8, 2 * keys.params.N), dtype=np.uint64).astype(np.uint32)
+    try:
+        trl.upload(st, 0, T)
+        with pytest.raises(hip.IykHipError) as plain:
+            st.cmux_batch(sel, trl, z, z, z, z, z)
+        with pytest.raises(hip.IykHipError) as laned:
+            st.cmux_batch(sel, trl, z, z, z, z, z, lanes=1, sel_stride=1, row_stride=1)
+        st.sync()
+        assert "batch too large" in str(plain.value) and "count x lanes" not in str(plain.value)
+        assert "batch too large: count x lanes" in str(laned.value)
+        assert np.array_equal(trl.download(st, 0, 8), T)
+    finally:
+        sel.free()
+        trl.free()
+        st.destroy()
+
+
+# ---- Rom / Ram with two lanes-------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("fused", [False, True], ids=["unfused", "fused"])
 def test_rom_two_lanes_equal_one_lane_roms(gpu, fused):
