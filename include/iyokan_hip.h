@@ -458,6 +458,16 @@ int iyk_hip_bk2_key_bytes(int gpu_index, uint64_t* out);
 int iyk_hip_cb_rotate_batch(iyk_hip_stream* st, const void* key, const uint32_t* d_tlwe0, uint64_t tlwe0_slots, uint64_t count,
                             const int32_t* in, const int32_t* sign, const uint32_t* off, const uint64_t* mu, uint64_t* d_tlwe2,
                             uint64_t tlwe2_slots, const int32_t* out);
+/* The many-digit form of the same rotation: ONE rotation per job gives the l lvl2 TLWEs of the constants mu[0 .. l) —
+ * job g writes slots out[g] .. out[g] + l - 1, slot out[g] + r being a TLWE of 2 mu[r] where the phase of lin is positive and of 0 where
+ * it is negative.  The mod switch is coarser by bw bits (2^bw >= l), the test vector interleaves the l constants, and coefficients
+ * 0 .. l - 1 of the one accumulator are extracted; l = 1 gives iyk_hip_cb_rotate_batch's words.  mu: l words, shared by the batch.
+ * Checked before anything is enqueued: 1 <= l <= 4, in / sign / off as above, out[g] + l inside the store, no two jobs' output ranges
+ * overlapping, count <= 2^20 — a violation is IYK_ERR_INVALID and no store changes.  The form (iyk_hip_cb_rotate_form) is that of a
+ * batch of `count` rotations: it does not depend on l. */
+int iyk_hip_cb_rotate_many_batch(iyk_hip_stream* st, const void* key, const uint32_t* d_tlwe0, uint64_t tlwe0_slots, uint64_t count,
+                                 const int32_t* in, const int32_t* sign, const uint32_t* off, uint32_t l, const uint64_t* mu,
+                                 uint64_t* d_tlwe2, uint64_t tlwe2_slots, const int32_t* out);
 /* *form_out = the kernel form a batch of count rotations would run on GPU gpu_index now: 0 = cb_rotate_kernel (256 lanes, the wide-batch
  * form), 1 = cb_rotate_lat_kernel (512 lanes, wave-owned polynomials, 4 barriers per step: the narrow-batch form).  Both give the same
  * words.  The answer of dispatch::cb_plan (csrc/dispatch.hpp) with the current environment: IYK_HIP_CB_KERNEL = wg / lat forces a form
@@ -480,6 +490,14 @@ int iyk_hip_circuit_bootstrap_batch(iyk_hip_stream* st, const void* bk2_key, con
                                     uint64_t tlwe0_slots, const int32_t* in, const int32_t* sign, uint64_t* d_tlwe2, uint32_t tlwe2_n_in,
                                     uint64_t tlwe2_slots, uint64_t tlwe2_first, uint32_t* d_trlwe, uint64_t trlwe_slots, void* d_trgsw,
                                     uint64_t trgsw_slots, uint64_t trgsw_first, uint64_t bits);
+
+/* iyk_hip_circuit_bootstrap_batch with the many-digit rotation: the same arguments, checks, slots, rows and selector meaning, `bits`
+ * rotations instead of bits * l (the initialised l must be at most 4), then the unchanged iyk_hip_privks_batch and
+ * iyk_hip_trgsw_from_rows.  The selectors' noise differs from the per-digit call's (other rotations), their plaintext does not. */
+int iyk_hip_circuit_bootstrap_many_batch(iyk_hip_stream* st, const void* bk2_key, const void* privks_key, const uint32_t* d_tlwe0,
+                                         uint64_t tlwe0_slots, const int32_t* in, const int32_t* sign, uint64_t* d_tlwe2,
+                                         uint32_t tlwe2_n_in, uint64_t tlwe2_slots, uint64_t tlwe2_first, uint32_t* d_trlwe,
+                                         uint64_t trlwe_slots, void* d_trgsw, uint64_t trgsw_slots, uint64_t trgsw_first, uint64_t bits);
 
 /* Kernel-only time of the most recent iyk_hip_gate_batch on this stream, from HIP events
  * recorded on the stream around the blind-rotate and key-switch launches (milliseconds).

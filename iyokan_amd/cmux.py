@@ -139,17 +139,26 @@ def selectors_from_tlwe2(stream, key, tlwe2, first, addr_width, trlwe_scratch, t
                            np.arange(addr_width * per).reshape(addr_width, per))
 
 
-def selectors_from_tlwe0(stream, bk2, privks_key, arena, addr_slots, tlwe2, first, trlwe_scratch, trgsw, first_slot=0, invert=False):
+def selectors_from_tlwe0(stream, bk2, privks_key, arena, addr_slots, tlwe2, first, trlwe_scratch, trgsw, first_slot=0, invert=False,
+                         many=False):
     """The selectors of a whole address from its lvl0 TLWEs in `arena` (slot addr_slots[bit]), on the device: circuit bootstrapping.
     ONE cb_rotate_batch of len(addr_slots) * l rotations under the lvl2 bootstrapping key `bk2` into TLWE lvl2 slots first + bit l + r of
     `tlwe2` (mu = 2^(63 - (r+1) Bgbit), off = 0; invert: sign = -1, the selector of the negated bit — the reference's
     CircuitBootstrappingFFTInv), then selectors_from_tlwe2.  Replaces the reference's TaskTFHEppCB / CBInv in front of a ROM / RAM port
-    (/root/reference/src/iyokan_tfhepp.hpp:194-236).  Asynchronous on the stream."""
+    (/root/reference/src/iyokan_tfhepp.hpp:194-236).  many=True: ONE cb_rotate_many_batch of len(addr_slots) rotations instead — each
+    gives the l TLWEs of its bit, into the same slots (the many-digit form; l <= 4).  Asynchronous on the stream."""
     from . import hip
 
     p = hip.current_params()
     l, bg = int(p.l), int(p.Bgbit)
     addr_slots = [int(s) for s in np.asarray(addr_slots).ravel()]
+    if many:
+        bits = len(addr_slots)
+        stream.cb_rotate_many_batch(bk2, arena, addr_slots, [-1 if invert else 1] * bits, [0] * bits,
+                                    np.array([1 << (63 - (r + 1) * bg) for r in range(l)], dtype=np.uint64), tlwe2,
+                                    [first + bit * l for bit in range(bits)])
+        selectors_from_tlwe2(stream, privks_key, tlwe2, first, bits, trlwe_scratch, trgsw, first_slot)
+        return
     in_, mu, out = [], [], []
     for bit, slot in enumerate(addr_slots):
         for r in range(l):

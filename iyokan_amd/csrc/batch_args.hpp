@@ -11,6 +11,7 @@
 // is part of the ABI's behaviour (which refusal a doubly wrong call gets): per-job checks stay in one loop, in the order written.
 #pragma once
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <initializer_list>
@@ -533,6 +534,79 @@ inline Refusal check_circuit_bootstrap_batch(const iyk_params& p, uint32_t bk2_n
             }
     }
     if (Refusal r = check_cb_rotate_batch(tlwe0_slots, tlwe2_slots, bits * l, r_in.data(), r_sign.data(), r_off.data(), r_mu.data(), r_out.data(), o.rot))
+        return r;
+    if (Refusal r = check_privks_batch(p.k, tlwe2_slots, trlwe_slots, bits * per, p_in.data(), p_c.data(), o.rows.data(), o.privks)) return r;
+    return check_trgsw_from_rows(p, trgsw_slots, trlwe_slots, bits, o.sel.data(), o.rows.data());
+}
+
+// ---- the many-digit form of the lvl2 rotation: one job per bit, l outputs per job ----------------------------------
+
+// the smallest bw with 2^bw >= l, for 1 <= l <= CB_MANY_MAX_L
+constexpr uint32_t cb_many_bw(uint32_t l) { return l <= 1 ? 0u : l <= 2 ? 1u : 2u; }
+
+// iyk_hip_cb_rotate_many_batch: job g writes lvl2 slots out[g] .. out[g] + l - 1.  shared: the kernel argument, mu[r] = 0 for r >= l.
+// Named like cmux_rotate_chain_args and for its reason; tests/test_cb_many_cases.py holds every refusal of the two functions below.
+inline Refusal cb_rotate_many_args(uint64_t tlwe0_slots, uint64_t tlwe2_slots, uint64_t count, const int32_t* in, const int32_t* sign,
+                                          const uint32_t* off, uint32_t l, const uint64_t* mu, const int32_t* out, std::vector<CbManyJob>& jobs,
+                                          CbManyMu& shared)
+{
+    if (count > MAX_CB_BATCH) return invalid("batch too large");
+    if (tlwe0_slots > MAX_STORE_ROWS || tlwe2_slots > MAX_STORE_ROWS) return invalid("store larger than an allocation can be");
+    if (l < 1 || l > CB_MANY_MAX_L) return invalid("l outside [1, 4]");
+    jobs.resize(count);
+    for (uint64_t g = 0; g < count; ++g) {
+        if (!slot_ok(in[g], tlwe0_slots)) return invalid("TLWE index outside the lvl0 store");
+        if (sign[g] != 1 && sign[g] != -1) return invalid("sign outside {+1, -1}");
+        if (out[g] < 0 || (uint64_t)out[g] + l > tlwe2_slots) return invalid("l TLWEs from out do not fit the lvl2 store");
+        jobs[g] = CbManyJob{in[g], sign[g], off[g], out[g]};
+    }
+    std::vector<int32_t> sorted(out, out + count);
+    std::sort(sorted.begin(), sorted.end());
+    for (uint64_t g = 1; g < count; ++g)
+        if ((uint64_t)sorted[g] - (uint64_t)sorted[g - 1] < l) return invalid("two jobs of one batch write the same lvl2 TLWE");
+    shared = CbManyMu{mu[0], l > 1 ? mu[1] : 0, l > 2 ? mu[2] : 0, l > 3 ? mu[3] : 0, l, cb_many_bw(l)};
+    return ACCEPT;
+}
+
+// What iyk_hip_circuit_bootstrap_many_batch hands its three parts: CbLists' slots and rows, with one rotation per bit
+struct CbManyLists {
+    std::vector<CbManyJob> rot;     // bits rotations
+    CbManyMu shared;
+    std::vector<PrivksJob> privks;  // bits * (k+1) l private key switches
+    std::vector<int32_t> rows, sel;
+};
+// iyk_hip_circuit_bootstrap_many_batch: check_circuit_bootstrap_batch's checks in its order, then the three parts' own builders
+inline Refusal circuit_bootstrap_many_args(const iyk_params& p, uint32_t bk2_n, uint32_t privks_n_in, uint64_t tlwe0_slots, const int32_t* in,
+                                                  const int32_t* sign, uint32_t tlwe2_n_in, uint64_t tlwe2_slots, uint64_t tlwe2_first,
+                                                  uint64_t trlwe_slots, uint64_t trgsw_slots, uint64_t trgsw_first, uint64_t bits, CbManyLists& o)
+{
+    const uint64_t l = p.l, per = (uint64_t)(p.k + 1) * l;
+    if (l < 1 || l > CB_MANY_MAX_L) return invalid("l outside [1, 4]");   // first: the cap below divides by per
+    if (bits > MAX_CB_BATCH / per) return invalid("batch too large");
+    if (tlwe0_slots > MAX_STORE_ROWS || tlwe2_slots > MAX_STORE_ROWS || trlwe_slots > MAX_STORE_ROWS || trgsw_slots > MAX_TRGSW_SLOTS)
+        return invalid("store larger than an allocation can be");
+    if (bk2_n != p.n) return invalid("the lvl2 bootstrapping key's n is not the initialised n of the lvl0 store's rows");
+    if (tlwe2_n_in != CB_RING_N) return invalid("the lvl2 store's n_in is not the 2048 the rotation writes");
+    if (tlwe2_n_in != privks_n_in) return invalid("the lvl2 store's n_in is not the private key-switching key's");
+    if (tlwe2_first > tlwe2_slots || bits * l > tlwe2_slots - tlwe2_first) return invalid("bits * l lvl2 slots from the first do not fit the lvl2 store");
+    if (trlwe_slots < bits * per) return invalid("the TRLWE scratch store has fewer than bits (k+1) l rows");
+    if (trgsw_first > trgsw_slots || bits > trgsw_slots - trgsw_first) return invalid("selector slots outside the selector store");
+    std::vector<int32_t> r_out(bits), p_in(bits * per), p_c(bits * per);
+    std::vector<uint32_t> r_off(bits, 0u);
+    uint64_t mu[CB_MANY_MAX_L] = {0, 0, 0, 0};
+    for (uint64_t r = 0; r < l; ++r) mu[r] = 1ull << (63 - (r + 1) * p.Bgbit);
+    o.rows.resize(bits * per);
+    o.sel.resize(bits);
+    for (uint64_t b = 0; b < bits; ++b) {
+        o.sel[b] = (int32_t)(trgsw_first + b);
+        r_out[b] = (int32_t)(tlwe2_first + b * l);
+        for (uint64_t c = 0; c <= p.k; ++c)
+            for (uint64_t r = 0; r < l; ++r) {
+                const uint64_t row = b * per + c * l + r;
+                p_in[row] = (int32_t)(tlwe2_first + b * l + r), p_c[row] = (int32_t)c, o.rows[row] = (int32_t)row;
+            }
+    }
+    if (Refusal r = cb_rotate_many_args(tlwe0_slots, tlwe2_slots, bits, in, sign, r_off.data(), (uint32_t)l, mu, r_out.data(), o.rot, o.shared))
         return r;
     if (Refusal r = check_privks_batch(p.k, tlwe2_slots, trlwe_slots, bits * per, p_in.data(), p_c.data(), o.rows.data(), o.privks)) return r;
     return check_trgsw_from_rows(p, trgsw_slots, trlwe_slots, bits, o.sel.data(), o.rows.data());

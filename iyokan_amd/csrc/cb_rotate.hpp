@@ -75,6 +75,42 @@ IYK_HD u32 cb_digit_u(u64 x, int lvl)
     return (u32)((x + C::offset_plus_round()) >> (64u - (u32)(lvl + 1) * BGBIT2)) & C::mask;
 }
 
+// ---- what a job's form decides: the mod switch, the test vector and the extraction; the step loop between them is one ---------------
+// The per-digit job {in, sign, off, mu, out} shares nothing with its batch.  The many-digit job {in, sign, off, out} of DESIGN.md §6d
+// shares CbManyMu {mu[0..l), l, bw}: the mod switch is coarser by bw bits and its values are multiples of 2^bw, the test vector
+// interleaves the l constants with period 2^bw, and coefficients 0 .. l - 1 of the one accumulator are extracted into W2[out .. out + l).
+// With l = 1 (bw = 0) every function below computes what its per-digit overload computes.  The kernels and their phases take what the
+// batch shares as a trailing pack `k...`: empty for CbJob — the per-digit kernels keep their argument lists — and one CbManyMu for CbManyJob.
+
+IYK_HD u32 cb_many_modswitch_a(u32 a, u32 bw) { return ((u32)(a + (1u << (19 + bw))) >> (20 + bw)) << bw; }   // round, multiples of 2^bw in [0, 2 N2)
+IYK_HD u32 cb_many_modswitch_b(u32 b, u32 bw) { return (2u * CB_N - ((b >> (20 + bw)) << bw)) & (2u * CB_N - 1); }   // truncate
+// mu[c], c < 4.  All four words are read first: a choice between the fields themselves is a choice between addresses, which keeps the
+// kernel argument in scratch memory.
+IYK_HD u64 cb_many_mu_at(const CbManyMu& k, u32 c)
+{
+    const u64 m0 = k.mu0, m1 = k.mu1, m2 = k.mu2, m3 = k.mu3;
+    const u64 lo = (c & 1) ? m1 : m0, hi = (c & 1) ? m3 : m2;
+    return (c & 2) ? hi : lo;
+}
+
+// abar of step i < n, and the rotation of the test vector (i == n), from the lvl0 word
+IYK_HD u32 cb_abar(const CbJob& jb, const u32* w, u32 n, u32 i)
+{
+    const u32 v = (u32)jb.sign * w[i];
+    return i == n ? cb_modswitch_b(v + jb.off) : cb_modswitch_a(v);
+}
+IYK_HD u32 cb_abar(const CbManyJob& jb, const u32* w, u32 n, u32 i, const CbManyMu& k)
+{
+    const u32 v = (u32)jb.sign * w[i];
+    return i == n ? cb_many_modswitch_b(v + jb.off, k.bw) : cb_many_modswitch_a(v, k.bw);
+}
+// coefficient c < N2 of the test vector (mu[r] = 0 for r >= l is the host's)
+IYK_HD u64 cb_tv(const CbJob& jb, u32) { return jb.mu; }
+IYK_HD u64 cb_tv(const CbManyJob&, u32 c, const CbManyMu& k) { return cb_many_mu_at(k, c & ((1u << k.bw) - 1)); }
+// lvl2 TLWEs a job writes
+IYK_HD u32 cb_outputs() { return 1; }
+IYK_HD u32 cb_outputs(const CbManyMu& k) { return k.l; }
+
 // ---- the transform's passes; bp = one polynomial slot of the exchange buffer ----------------------------------------------------
 // pass 1 forward, lane j1 < 64: x[j2] already twisted by zeta^j2.  Leaves Y[j1][k2] at bp[k2 * 65 + j1].
 IYK_HD void cb_pass1_fwd(int j1, u64 (&x)[32], const u64* twf, u64* bp)
@@ -121,19 +157,18 @@ IYK_HD void cb_pass2_inv(int j1, const u64* bp, u64 (&y)[32])
 
 // ---- the phases of one rotation, per lane < 256; a workgroup barrier stands between any two of them ------------------------------
 // abar[i] for i <= n (abar[n] = the test vector's rotation) and the initial accumulator
-IYK_HD void cb_prologue(int lane, const CbJob& jb, const u32* w, u32 n, u32* abar, u64* acc)
+template <class Job, class... Shared>
+IYK_HD void cb_prologue(int lane, const Job& jb, const u32* w, u32 n, u32* abar, u64* acc, const Shared&... k)
 {
-    for (u32 i = (u32)lane; i <= n; i += CB_LANES) {
-        const u32 v = (u32)jb.sign * w[i];
-        abar[i] = (i == n) ? cb_modswitch_b(v + jb.off) : cb_modswitch_a(v);
-    }
-    const u32 rot = cb_modswitch_b((u32)jb.sign * w[n] + jb.off);
+    for (u32 i = (u32)lane; i <= n; i += CB_LANES) abar[i] = cb_abar(jb, w, n, i, k...);
+    const u32 rot = cb_abar(jb, w, n, n, k...);
 #pragma unroll
     for (int q = 0; q < CB_N / CB_LANES; ++q) {
         const int j = lane + CB_LANES * q;
         const u32 idx = ((u32)j - rot) & (2 * CB_N - 1);
+        const u64 t = cb_tv(jb, idx & (CB_N - 1), k...);
         acc[j] = 0;
-        acc[CB_N + j] = (idx & CB_N) ? 0ull - jb.mu : jb.mu;
+        acc[CB_N + j] = (idx & CB_N) ? 0ull - t : t;
     }
 }
 
@@ -221,6 +256,25 @@ IYK_HD u64 cb_extract_word(const u64* acc, int j, u64 mu)
     if (j == CB_N) return acc[CB_N] + mu;
     return j == 0 ? acc[0] : 0ull - acc[CB_N - j];
 }
+// word j <= N2 of SampleExtractIndex(acc, r) + (0, .., 0, mu): the negated, reversed part starts behind index r
+IYK_HD u64 cb_extract_word_at(const u64* acc, int j, u32 r, u64 mu)
+{
+    if (j == CB_N) return acc[CB_N + r] + mu;
+    return (u32)j <= r ? acc[r - (u32)j] : 0ull - acc[CB_N + r - (u32)j];
+}
+IYK_HD u64 cb_out_word(const CbJob& jb, const u64* acc, int j, u32) { return cb_extract_word(acc, j, jb.mu); }
+IYK_HD u64 cb_out_word(const CbManyJob&, const u64* acc, int j, u32 r, const CbManyMu& k) { return cb_extract_word_at(acc, j, r, cb_many_mu_at(k, r)); }
+// a job's outputs from the finished accumulator, per lane < LANES: W2[out + r] for r < cb_outputs
+template <int LANES, class Job, class... Shared>
+IYK_HD void cb_epilogue(int lane, const Job& jb, const u64* acc, u64* tlwe2, const Shared&... k)
+{
+    for (u32 r = 0; r < cb_outputs(k...); ++r) {
+        u64* row = tlwe2 + ((size_t)jb.out + r) * (CB_N + 1);
+#pragma unroll
+        for (int q = 0; q < CB_N / LANES; ++q) row[lane + LANES * q] = cb_out_word(jb, acc, lane + LANES * q, r, k...);
+        if (lane == 0) row[CB_N] = cb_out_word(jb, acc, CB_N, r, k...);
+    }
+}
 
 // ---- host-side tables: twf[k2 * 64 + j1] = psi^(j1 (2 k2 + 1)), twi[j1 * 32 + k2] = psi^(-j1 (2 k2 + 1)) / N2; psi^64 = 2^3 --------
 inline u64 cb_find_psi()
@@ -269,9 +323,11 @@ __global__ __launch_bounds__(64) void bk2_ntt_kernel(const u64* __restrict__ tor
 }
 
 // grid: min(njobs, CUs) workgroups; workgroup b runs jobs b, b + grid, ... (rounds).  tw: twf then twi (2 x 2048 u64).
-template <int L2, int BGBIT2>
-__global__ __launch_bounds__(CB_LANES) void cb_rotate_kernel(const CbJob* __restrict__ jobs, int njobs, const u32* __restrict__ tlwe0, u32 n,
-                                                             const u64* __restrict__ bk, const u64* __restrict__ tw, u64* __restrict__ tlwe2)
+// <L2, BGBIT2>: the per-digit form, its arguments end at tlwe2; <L2, BGBIT2, CbManyJob, CbManyMu>: the many-digit form, k = one CbManyMu.
+template <int L2, int BGBIT2, class Job = CbJob, class... Shared>
+__global__ __launch_bounds__(CB_LANES) void cb_rotate_kernel(const Job* __restrict__ jobs, int njobs, const u32* __restrict__ tlwe0, u32 n,
+                                                             const u64* __restrict__ bk, const u64* __restrict__ tw, u64* __restrict__ tlwe2,
+                                                             const Shared... k)
 {
     extern __shared__ __align__(16) u64 cb_lds[];
     u64* acc = cb_lds;
@@ -284,8 +340,8 @@ __global__ __launch_bounds__(CB_LANES) void cb_rotate_kernel(const CbJob* __rest
     for (int q = 0; q < 2 * CB_N / CB_LANES; ++q) twf[lane + CB_LANES * q] = tw[lane + CB_LANES * q];   // twf and twi are adjacent
 
     for (int job = blockIdx.x; job < njobs; job += gridDim.x) {
-        const CbJob jb = jobs[job];
-        cb_prologue(lane, jb, tlwe0 + (size_t)jb.in * (n + 1), n, abar, acc);
+        const Job jb = jobs[job];
+        cb_prologue(lane, jb, tlwe0 + (size_t)jb.in * (n + 1), n, abar, acc, k...);
         __syncthreads();
         for (u32 i = 0; i < n; ++i) {
             const u32 ab = abar[i];
@@ -313,10 +369,7 @@ __global__ __launch_bounds__(CB_LANES) void cb_rotate_kernel(const CbJob* __rest
             cb_inv2(lane, buf, acc);
             __syncthreads();
         }
-        u64* row = tlwe2 + (size_t)jb.out * (CB_N + 1);
-#pragma unroll
-        for (int q = 0; q < CB_N / CB_LANES; ++q) row[lane + CB_LANES * q] = cb_extract_word(acc, lane + CB_LANES * q, jb.mu);
-        if (lane == 0) row[CB_N] = cb_extract_word(acc, CB_N, jb.mu);
+        cb_epilogue<CB_LANES>(lane, jb, acc, tlwe2, k...);
         __syncthreads();   // the next round's prologue writes acc and abar
     }
 }

@@ -20,7 +20,7 @@
 // Workgroup barriers per step: 4.  LDS: acc 32 KiB + 8 slots x 16 KiB = 160 KiB of 160.  The tables (33 KiB) are read from global
 // memory behind the key.  No FP64 matrix instruction, no sync between workgroups, no spin wait.
 #pragma once
-#include "cb_rotate_lat.hpp"   // cbl_abar, cbl_prologue, cbl_wave_sync; cb_rotate.hpp
+#include "cb_rotate_lat.hpp"   // cbl_prologue, cbl_wave_sync; cb_rotate.hpp: cb_abar, cb_epilogue
 #include "fft1024.hpp"
 
 namespace iyk {
@@ -162,10 +162,11 @@ __global__ __launch_bounds__(64) void bk2_fft_kernel(const u64* __restrict__ tor
 
 // grid: dispatch::cb_fft_grid workgroups; workgroup b runs jobs b, b + grid, ... (rounds, indexed by the job number).
 // tab: fft1k::make_tables', in global memory.
-template <int L2, int BGBIT2, bool CHECK>
-__global__ __launch_bounds__(CBF_LANES) void cb_rotate_fft_kernel(const CbJob* __restrict__ jobs, int njobs, const u32* __restrict__ tlwe0, u32 n,
+// <L2, BGBIT2, CHECK>: the per-digit form, its arguments end at max_err_bits; <.., CbManyJob, CbManyMu>: the many-digit form, k = one CbManyMu.
+template <int L2, int BGBIT2, bool CHECK, class Job = CbJob, class... Shared>
+__global__ __launch_bounds__(CBF_LANES) void cb_rotate_fft_kernel(const Job* __restrict__ jobs, int njobs, const u32* __restrict__ tlwe0, u32 n,
                                                                   const cplx* __restrict__ bk, const cplx* __restrict__ tab, u64* __restrict__ tlwe2,
-                                                                  unsigned long long* __restrict__ max_err_bits)
+                                                                  unsigned long long* __restrict__ max_err_bits, const Shared... k)
 {
     static_assert(L2 * 2 == CB_ROWS, "one wave per digit polynomial");
     extern __shared__ __align__(16) u64 cbf_lds[];
@@ -175,16 +176,16 @@ __global__ __launch_bounds__(CBF_LANES) void cb_rotate_fft_kernel(const CbJob* _
     double err = 0.0;
 
     for (int job = blockIdx.x; job < njobs; job += gridDim.x) {
-        const CbJob jb = jobs[job];
+        const Job jb = jobs[job];
         const u32* w = tlwe0 + (size_t)jb.in * (n + 1);
-        cbl_prologue(lane, jb, w, n, acc);
+        cbl_prologue(lane, jb, w, n, acc, k...);
         __syncthreads();
         for (u32 i = 0; i < n; ++i) {
             // The lane number as a value of the step (i < n <= CB_MAX_N0 = 2047: the term is 0), as in cb_rotate_lat_kernel: what a phase
             // derives from its lane alone (addresses, and here the 48 table constants of the transforms) would otherwise be fetched once
             // in front of the loop and held in registers through all phases at once.
             const int ln = lane + (int)(i >> 11);
-            const u32 ab = cbl_abar(jb, w, n, i);
+            const u32 ab = cb_abar(jb, w, n, i, k...);
             const cplx* bk_step = bk + (size_t)i * CBF_STEP_POINTS;
             cplx* sp = cbf_slot(buf, ln);
             const int L = ln & 63;
@@ -217,10 +218,7 @@ __global__ __launch_bounds__(CBF_LANES) void cb_rotate_fft_kernel(const CbJob* _
             if (CHECK) err = __builtin_fmax(err, e);
             __syncthreads();   // the accumulator is complete
         }
-        u64* row = tlwe2 + (size_t)jb.out * (CB_N + 1);
-#pragma unroll
-        for (int q = 0; q < CB_N / CBF_LANES; ++q) row[lane + CBF_LANES * q] = cb_extract_word(acc, lane + CBF_LANES * q, jb.mu);
-        if (lane == 0) row[CB_N] = cb_extract_word(acc, CB_N, jb.mu);
+        cb_epilogue<CBF_LANES>(lane, jb, acc, tlwe2, k...);
         __syncthreads();   // the next round's prologue writes acc
     }
     if (CHECK && max_err_bits) {   // non-negative doubles order like their bit patterns

@@ -98,22 +98,20 @@ IYK_HD void cbl_pass2_inv(int j1, const u64* bp, u64 (&y)[32])
 }
 
 // ---- the phases of one rotation, per lane < 512 -------------------------------------------------------------------------------------
-// abar of step i < n, and the rotation of the test vector (i == n): recomputed from the lvl0 word, there is no LDS array
-IYK_HD u32 cbl_abar(const CbJob& jb, const u32* w, u32 n, u32 i)
-{
-    const u32 v = (u32)jb.sign * w[i];
-    return i == n ? cb_modswitch_b(v + jb.off) : cb_modswitch_a(v);
-}
+// abar of step i < n, and the rotation of the test vector (i == n): recomputed from the lvl0 word (cb_abar), there is no LDS array
+IYK_HD u32 cbl_abar(const CbJob& jb, const u32* w, u32 n, u32 i) { return cb_abar(jb, w, n, i); }
 // the initial accumulator
-IYK_HD void cbl_prologue(int lane, const CbJob& jb, const u32* w, u32 n, u64* acc)
+template <class Job, class... Shared>
+IYK_HD void cbl_prologue(int lane, const Job& jb, const u32* w, u32 n, u64* acc, const Shared&... k)
 {
-    const u32 rot = cbl_abar(jb, w, n, n);
+    const u32 rot = cb_abar(jb, w, n, n, k...);
 #pragma unroll
     for (int q = 0; q < CB_N / CBL_LANES; ++q) {
         const int j = lane + CBL_LANES * q;
         const u32 idx = ((u32)j - rot) & (2 * CB_N - 1);
+        const u64 t = cb_tv(jb, idx & (CB_N - 1), k...);
         acc[j] = 0;
-        acc[CB_N + j] = (idx & CB_N) ? 0ull - jb.mu : jb.mu;
+        acc[CB_N + j] = (idx & CB_N) ? 0ull - t : t;
     }
 }
 
@@ -228,9 +226,11 @@ __device__ __forceinline__ void cbl_wave_sync()
 }
 
 // grid: min(njobs, CUs) workgroups; workgroup b runs jobs b, b + grid, ... (rounds).  tw: twf then twi (2 x 2048 u64), in global memory.
-template <int L2, int BGBIT2>
-__global__ __launch_bounds__(CBL_LANES) void cb_rotate_lat_kernel(const CbJob* __restrict__ jobs, int njobs, const u32* __restrict__ tlwe0, u32 n,
-                                                                  const u64* __restrict__ bk, const u64* __restrict__ tw, u64* __restrict__ tlwe2)
+// <L2, BGBIT2>: the per-digit form, its arguments end at tlwe2; <L2, BGBIT2, CbManyJob, CbManyMu>: the many-digit form, k = one CbManyMu.
+template <int L2, int BGBIT2, class Job = CbJob, class... Shared>
+__global__ __launch_bounds__(CBL_LANES) void cb_rotate_lat_kernel(const Job* __restrict__ jobs, int njobs, const u32* __restrict__ tlwe0, u32 n,
+                                                                  const u64* __restrict__ bk, const u64* __restrict__ tw, u64* __restrict__ tlwe2,
+                                                                  const Shared... k)
 {
     static_assert(L2 * 2 == CB_ROWS, "one wave per digit polynomial");
     extern __shared__ __align__(16) u64 cbl_lds[];
@@ -241,11 +241,11 @@ __global__ __launch_bounds__(CBL_LANES) void cb_rotate_lat_kernel(const CbJob* _
     const int lane = threadIdx.x;
 
     for (int job = blockIdx.x; job < njobs; job += gridDim.x) {
-        const CbJob jb = jobs[job];
+        const Job jb = jobs[job];
         const u32* w = tlwe0 + (size_t)jb.in * (n + 1);
-        cbl_prologue(lane, jb, w, n, acc);
+        cbl_prologue(lane, jb, w, n, acc, k...);
         CbPair pf[CBL_PF];
-        u32 ab = cbl_abar(jb, w, n, 0);
+        u32 ab = cb_abar(jb, w, n, 0, k...);
         __syncthreads();
         for (u32 i = 0; i < n; ++i) {
             // The lane number as a value of the step (i < n <= CB_MAX_N0 = 2047: the term is 0).  Everything a phase derives from its lane
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(CBL_LANES) void cb_rotate_lat_kernel(const CbJob* _
             // at once: 650 registers' worth, against the 256 a lane has at two waves per SIMD.
             const int ln = lane + (int)(i >> 11);
             const u64* bk_step = bk + (size_t)i * CB_STEP_WORDS;
-            const u32 ab_next = cbl_abar(jb, w, n, i + 1);   // word i + 1 <= n is inside the row
+            const u32 ab_next = cb_abar(jb, w, n, i + 1, k...);   // word i + 1 <= n is inside the row
             if (i == 0) cbl_prefetch(ln, bk_step, pf);       // later steps: requested by the step before
             u64 x[32];
             cbl_fwd1<L2, BGBIT2>(ln, ab, acc, twf, buf);
@@ -278,10 +278,7 @@ __global__ __launch_bounds__(CBL_LANES) void cb_rotate_lat_kernel(const CbJob* _
             __syncthreads();   // the accumulator is complete
             ab = ab_next;
         }
-        u64* row = tlwe2 + (size_t)jb.out * (CB_N + 1);
-#pragma unroll
-        for (int q = 0; q < CB_N / CBL_LANES; ++q) row[lane + CBL_LANES * q] = cb_extract_word(acc, lane + CBL_LANES * q, jb.mu);
-        if (lane == 0) row[CB_N] = cb_extract_word(acc, CB_N, jb.mu);
+        cb_epilogue<CBL_LANES>(lane, jb, acc, tlwe2, k...);
         __syncthreads();   // the next round's prologue writes acc
     }
 }

@@ -1375,8 +1375,9 @@ void cb_inverse(const u64* in, u64* out)
 
 // lane-by-lane run of cb_rotate_kernel for one job: the same phase functions in the same order, one loop over the 256 lanes wherever
 // the kernel has a barrier
-template <int L2, int BGBIT2>
-void cb_rotate(u32 n, const u32* w, const CbJob& jb, const u64* bk, u64* out)
+// out: u64 [cb_outputs(k)][N2 + 1], the job's out taken as 0
+template <int L2, int BGBIT2, class Job, class... Shared>
+void cb_rotate(u32 n, const u32* w, const Job& jb, const u64* bk, u64* out, const Shared&... k)
 {
     const u64* twf = cb_tables().tw.data();
     const u64* twi = twf + CB_N;
@@ -1388,7 +1389,7 @@ void cb_rotate(u32 n, const u32* w, const CbJob& jb, const u64* bk, u64* out)
     std::vector<Lane> R(CB_LANES);
 #define CB_LANES_ALL for (int lane = 0; lane < CB_LANES; ++lane)
 #define CB_LANES_HALF for (int lane = 0; lane < 128; ++lane)
-    CB_LANES_ALL cb_prologue(lane, jb, w, n, abar.data(), acc.data());
+    CB_LANES_ALL cb_prologue(lane, jb, w, n, abar.data(), acc.data(), k...);
     for (u32 i = 0; i < n; ++i) {
         const u32 ab = abar[i];
         const u64* bk_step = bk + (size_t)i * CB_STEP_WORDS;
@@ -1404,7 +1405,7 @@ void cb_rotate(u32 n, const u32* w, const CbJob& jb, const u64* bk, u64* out)
         CB_LANES_HALF cb_pass1_inv_write(lane & 31, R[lane].x, buf.data() + (lane >> 5) * CB_PSTRIDE);
         CB_LANES_ALL cb_inv2(lane, buf.data(), acc.data());
     }
-    for (int j = 0; j <= CB_N; ++j) out[j] = cb_extract_word(acc.data(), j, jb.mu);
+    CB_LANES_ALL cb_epilogue<CB_LANES>(lane, jb, acc.data(), out, k...);
 #undef CB_LANES_ALL
 #undef CB_LANES_HALF
 }
@@ -1488,8 +1489,8 @@ void cbl_inverse(const u64* in, u64* out)
 
 // lane-by-lane run of cb_rotate_lat_kernel for one job: the same phase functions in the same order, one loop over the lanes wherever
 // the kernel has a workgroup barrier or a wave-level ordering point
-template <int L2, int BGBIT2>
-void cb_rotate_lat(u32 n, const u32* w, const CbJob& jb, const u64* bk, u64* out)
+template <int L2, int BGBIT2, class Job, class... Shared>
+void cb_rotate_lat(u32 n, const u32* w, const Job& jb, const u64* bk, u64* out, const Shared&... k)
 {
     const u64* twf = cb_tables().tw.data();
     const u64* twi = twf + CB_N;
@@ -1501,12 +1502,12 @@ void cb_rotate_lat(u32 n, const u32* w, const CbJob& jb, const u64* bk, u64* out
     std::vector<Lane> R(CBL_LANES);
 #define CBL_LANES_ALL for (int lane = 0; lane < CBL_LANES; ++lane)
 #define CBL_LANES_INV for (int lane = 0; lane < 4 * 64; ++lane)
-    CBL_LANES_ALL cbl_prologue(lane, jb, w, n, acc.data());
+    CBL_LANES_ALL cbl_prologue(lane, jb, w, n, acc.data(), k...);
     CBL_LANES_ALL cbl_prefetch(lane, bk, R[lane].pf);
-    u32 ab = cbl_abar(jb, w, n, 0);
+    u32 ab = cb_abar(jb, w, n, 0, k...);
     for (u32 i = 0; i < n; ++i) {
         const u64* bk_step = bk + (size_t)i * CB_STEP_WORDS;
-        const u32 ab_next = cbl_abar(jb, w, n, i + 1);
+        const u32 ab_next = cb_abar(jb, w, n, i + 1, k...);
         CBL_LANES_ALL cbl_fwd1<L2, BGBIT2>(lane, ab, acc.data(), twf, buf.data());
         CBL_LANES_ALL cbl_fwd2_read(lane, buf.data(), R[lane].x);
         CBL_LANES_ALL cbl_fwd2_write(lane, R[lane].x, buf.data());
@@ -1518,7 +1519,7 @@ void cb_rotate_lat(u32 n, const u32* w, const CbJob& jb, const u64* bk, u64* out
         CBL_LANES_INV cbl_inv2(lane, buf.data(), acc.data());
         ab = ab_next;
     }
-    for (int j = 0; j <= CB_N; ++j) out[j] = cb_extract_word(acc.data(), j, jb.mu);
+    CBL_LANES_ALL cb_epilogue<CBL_LANES>(lane, jb, acc.data(), out, k...);
 #undef CBL_LANES_ALL
 #undef CBL_LANES_INV
 }
@@ -1603,8 +1604,8 @@ void cbf_inverse_to_last_pass(std::vector<Cbf16>& X, cplx* sp)
 
 // lane-by-lane run of cb_rotate_fft_kernel for one job: the same phase functions in the same order, one loop over the lanes wherever
 // the kernel has a workgroup barrier or a wave-level ordering point
-template <int L2, int BGBIT2>
-void cb_rotate_fft(u32 n, const u32* w, const CbJob& jb, const cplx* bk, u64* out)
+template <int L2, int BGBIT2, class Job, class... Shared>
+void cb_rotate_fft(u32 n, const u32* w, const Job& jb, const cplx* bk, u64* out, const Shared&... k)
 {
     const cplx* tab = cbf_tables();
     std::vector<u64> acc(2 * CB_N);
@@ -1614,9 +1615,9 @@ void cb_rotate_fft(u32 n, const u32* w, const CbJob& jb, const cplx* bk, u64* ou
     };
     std::vector<Lane> R(CBF_LANES);
 #define CBF_LANES_ALL for (int lane = 0; lane < CBF_LANES; ++lane)
-    CBF_LANES_ALL cbl_prologue(lane, jb, w, n, acc.data());
+    CBF_LANES_ALL cbl_prologue(lane, jb, w, n, acc.data(), k...);
     for (u32 i = 0; i < n; ++i) {
-        const u32 ab = cbl_abar(jb, w, n, i);
+        const u32 ab = cb_abar(jb, w, n, i, k...);
         const cplx* bk_step = bk + (size_t)i * CBF_STEP_POINTS;
         CBF_LANES_ALL cbf_digits<L2, BGBIT2>(lane, ab, acc.data(), R[lane].x);
         CBF_LANES_ALL fft1k::fwd1(lane & 63, R[lane].x, tab, cbf_slot(buf.data(), lane));
@@ -1632,7 +1633,7 @@ void cb_rotate_fft(u32 n, const u32* w, const CbJob& jb, const cplx* bk, u64* ou
         CBF_LANES_ALL fft1k::inv2_write(lane & 63, R[lane].x, cbf_slot(buf.data(), lane));
         CBF_LANES_ALL g_cbf_worst = std::max(g_cbf_worst, cbf_inv_add<true>(lane, tab, buf.data(), acc.data()));
     }
-    for (int j = 0; j <= CB_N; ++j) out[j] = cb_extract_word(acc.data(), j, jb.mu);
+    CBF_LANES_ALL cb_epilogue<CBF_LANES>(lane, jb, acc.data(), out, k...);
 #undef CBF_LANES_ALL
 }
 }  // namespace
@@ -1707,6 +1708,41 @@ double iyk_emul_cb_fft_round_error(int reset)
 }
 /* dispatch::cb_fft_grid, dispatch::bk2_form_known */
 int iyk_emul_cb_fft_grid(int64_t count, int cus) { return dispatch::cb_fft_grid((long)count, cus); }
+
+static CbManyMu cb_many_shared(uint32_t l, const uint64_t* mu)
+{
+    return CbManyMu{mu[0], l > 1 ? mu[1] : 0, l > 2 ? mu[2] : 0, l > 3 ? mu[3] : 0, l, args::cb_many_bw(l)};
+}
+/* ---- the many-digit form: one job of the CbManyJob instance of cb_rotate_kernel (form 0), cb_rotate_lat_kernel (1) or
+ * cb_rotate_fft_kernel (2, bk: iyk_emul_bk2_fft's key), lane by lane.  mu: l words; out: u64 [l][N2 + 1] */
+int iyk_emul_cb_rotate_many(int form, uint32_t n, uint32_t l2, uint32_t Bgbit2, const uint32_t* w, int32_t sign, uint32_t off, uint32_t l,
+                            const uint64_t* mu, const void* bk, uint64_t* out)
+{
+    if (l2 != 4 || Bgbit2 != 9 || n == 0 || n > CB_MAX_N0 || (sign != 1 && sign != -1) || l < 1 || l > CB_MANY_MAX_L || form < 0 || form > 2) return -1;
+    const CbManyMu k = cb_many_shared(l, mu);
+    const CbManyJob jb{0, sign, off, 0};
+    if (form == 0) cb_rotate<4, 9>(n, w, jb, static_cast<const u64*>(bk), out, k);
+    else if (form == 1) cb_rotate_lat<4, 9>(n, w, jb, static_cast<const u64*>(bk), out, k);
+    else cb_rotate_fft<4, 9>(n, w, jb, static_cast<const cplx*>(bk), out, k);
+    return 0;
+}
+/* cb_epilogue alone on an accumulator u64 [2][N2] (a, then b), as the `lanes` (256 or 512) lanes of a kernel run it: out u64 [l][N2 + 1] */
+int iyk_emul_cb_many_extract(const uint64_t* acc, int lanes, uint32_t l, const uint64_t* mu, uint64_t* out)
+{
+    if (l < 1 || l > CB_MANY_MAX_L || (lanes != CB_LANES && lanes != CBL_LANES)) return -1;
+    const CbManyMu k = cb_many_shared(l, mu);
+    const CbManyJob jb{0, 1, 0, 0};
+    for (int lane = 0; lane < lanes; ++lane) {
+        if (lanes == CB_LANES) cb_epilogue<CB_LANES>(lane, jb, acc, out, k);
+        else cb_epilogue<CBL_LANES>(lane, jb, acc, out, k);
+    }
+    return 0;
+}
+/* the many-digit mod switch of `count` words: a[g] rounded, b[g] truncated (the value before 2 N2 - .), both multiples of 2^bw */
+void iyk_emul_cb_many_modswitch(const uint32_t* x, int count, uint32_t bw, uint32_t* a, uint32_t* b)
+{
+    for (int g = 0; g < count; ++g) a[g] = cb_many_modswitch_a(x[g], bw), b[g] = (2u * CB_N - cb_many_modswitch_b(x[g], bw)) & (2u * CB_N - 1);
+}
 int iyk_emul_bk2_form_known(int form) { return dispatch::bk2_form_known(form) ? 1 : 0; }
 }
 
@@ -1848,6 +1884,29 @@ int iyk_emul_check_cb_rotate_batch(uint64_t tlwe0_slots, uint64_t tlwe2_slots, u
     std::vector<CbJob> jobs;
     const args::Refusal r = args::check_cb_rotate_batch(tlwe0_slots, tlwe2_slots, count, in, sign, off, mu, out, jobs);
     if (!r) o.list(jobs);
+    return o.finish(r);
+}
+/* lists: the jobs, then the shared CbManyMu as one element */
+int iyk_emul_cb_rotate_many_args(uint64_t tlwe0_slots, uint64_t tlwe2_slots, uint64_t count, const int32_t* in, const int32_t* sign,
+                                        const uint32_t* off, uint32_t l, const uint64_t* mu, const int32_t* out, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    std::vector<CbManyJob> jobs;
+    std::vector<CbManyMu> shared(1);
+    const args::Refusal r = args::cb_rotate_many_args(tlwe0_slots, tlwe2_slots, count, in, sign, off, l, mu, out, jobs, shared[0]);
+    if (!r) o.list(jobs), o.list(shared);
+    return o.finish(r);
+}
+/* lists: the rotations, the shared CbManyMu, the private key switches, the scratch rows of every selector, the selector slots */
+int iyk_emul_circuit_bootstrap_many_args(const iyk_params* p, uint32_t bk2_n, uint32_t privks_n_in, uint64_t tlwe0_slots, const int32_t* in,
+                                                const int32_t* sign, uint32_t tlwe2_n_in, uint64_t tlwe2_slots, uint64_t tlwe2_first,
+                                                uint64_t trlwe_slots, uint64_t trgsw_slots, uint64_t trgsw_first, uint64_t bits, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    args::CbManyLists l;
+    const args::Refusal r = args::circuit_bootstrap_many_args(*p, bk2_n, privks_n_in, tlwe0_slots, in, sign, tlwe2_n_in, tlwe2_slots,
+                                                                     tlwe2_first, trlwe_slots, trgsw_slots, trgsw_first, bits, l);
+    if (!r) o.list(l.rot), o.list(std::vector<CbManyMu>(1, l.shared)), o.list(l.privks), o.list(l.rows), o.list(l.sel);
     return o.finish(r);
 }
 /* lists: the rotations, the private key switches, the scratch rows of every selector, the selector slots */

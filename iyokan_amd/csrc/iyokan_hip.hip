@@ -688,12 +688,18 @@ int set_kernel_attrs(const iyk_params& p, bool use_fp, int split, bool* cb_lat_g
 {
     // the latency form of the lvl2 rotation asks for the whole LDS of a CU: a device that does not grant it runs cb_rotate_kernel
     // (dispatch::cb_kind_for_device), initialisation does not fail
-    *cb_lat_granted = hipFuncSetAttribute(reinterpret_cast<const void*>(cb_rotate_lat_kernel<4, 9>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)CBL_LDS_BYTES) == hipSuccess;
-    if (!*cb_lat_granted) (void)hipGetLastError();   // not sticky: leave no pending error behind
+    // (each form's many-digit sibling is granted or refused with it: one flag per form)
+    *cb_lat_granted = true;
+    for (const void* f : {reinterpret_cast<const void*>(cb_rotate_lat_kernel<4, 9>), reinterpret_cast<const void*>(cb_rotate_lat_kernel<4, 9, CbManyJob, CbManyMu>)})
+        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CBL_LDS_BYTES) != hipSuccess) {
+            (void)hipGetLastError();   // not sticky: leave no pending error behind
+            *cb_lat_granted = false;
+        }
     // the FP64 form of the lvl2 rotation asks for the same: a device that does not grant it creates no key of that form
     *cb_fft_granted = true;
-    for (const void* f : {reinterpret_cast<const void*>(cb_rotate_fft_kernel<4, 9, false>), reinterpret_cast<const void*>(cb_rotate_fft_kernel<4, 9, true>)})
+    for (const void* f : {reinterpret_cast<const void*>(cb_rotate_fft_kernel<4, 9, false>), reinterpret_cast<const void*>(cb_rotate_fft_kernel<4, 9, true>),
+                          reinterpret_cast<const void*>(cb_rotate_fft_kernel<4, 9, false, CbManyJob, CbManyMu>),
+                          reinterpret_cast<const void*>(cb_rotate_fft_kernel<4, 9, true, CbManyJob, CbManyMu>)})
         if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CBF_LDS_BYTES) != hipSuccess) {
             (void)hipGetLastError();
             *cb_fft_granted = false;
@@ -706,6 +712,7 @@ int set_kernel_attrs(const iyk_params& p, bool use_fp, int split, bool* cb_lat_g
     });
     if (rc) return rc;
     if ((rc = set_lds(cb_rotate_kernel<4, 9>, CB_LDS_BYTES))) return rc;   // lvl2 rotation of circuit bootstrapping: every path
+    if ((rc = set_lds(cb_rotate_kernel<4, 9, CbManyJob, CbManyMu>, CB_LDS_BYTES))) return rc;
     return with_ks_set(p.t, [&](auto t, auto nc) {
         constexpr int T = decltype(t)::value, NC = decltype(nc)::value;
         if constexpr (NC != 0)
@@ -2842,28 +2849,32 @@ CbPlan cb_plan_of_batch(const Device& D, uint64_t count)
     return cb_plan((long)count, D.cus, cb_kind_for_device(cb_kind_of(std::getenv("IYK_HIP_CB_KERNEL")), D.cb_lat_granted));
 }
 
-// stage, launch, release of iyk_hip_cb_rotate_batch; jobs: args::check_cb_rotate_batch's
-int launch_cb_rotate(iyk_hip_stream* st, const Bk2Key* key, const uint32_t* d_tlwe0, uint64_t* d_tlwe2, const std::vector<CbJob>& jobs)
+// stage, launch, release of one rotation batch under either form of job.  jobs: args::check_cb_rotate_batch's (CbJob, nothing shared) or
+// args::cb_rotate_many_args' (CbManyJob, shared = the one CbManyMu), the kernels' own template arguments.  A template: C++ linkage
+// inside this file's extern "C" block.
+extern "C++" template <class Job, class... Shared>
+int launch_cb_rotate(iyk_hip_stream* st, const Bk2Key* key, const uint32_t* d_tlwe0, uint64_t* d_tlwe2, const std::vector<Job>& jobs,
+                     const Shared&... shared)
 {
-    const uint64_t count = jobs.size();
-    const CbPlan plan = cb_plan_of_batch(G.devs[st->gpu], count);   // before anything is staged: a refused kind launches nothing
+    const int count = (int)jobs.size();
+    const Device& D = G.devs[st->gpu];
+    const CbPlan plan = cb_plan_of_batch(D, jobs.size());   // before anything is staged: a refused kind launches nothing
     if (plan.form < 0) return fail(IYK_ERR_INVALID, "IYK_HIP_CB_KERNEL names neither wg nor lat");
     char* d[1];
-    if (int rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(CbJob)}}, d)) return rc;
+    if (int rc = stage_put(st, {{jobs.data(), jobs.size() * sizeof(Job)}}, d)) return rc;
     const bool timed = !st->log_on && st->ev_br0 && st->ev_br1;
     if (timed) HIP_TRY(hipEventRecord(st->ev_br0, st->s));
     if (key->form == BK2_FORM_FFT) {   // the key's form, not the batch's plan: wg / lat name kernels of the integer key
-        const Device& D = G.devs[st->gpu];
-        auto kern = G.debug ? cb_rotate_fft_kernel<4, 9, true> : cb_rotate_fft_kernel<4, 9, false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)cb_fft_grid((long)count, D.cus)), dim3(CBF_LANES), CBF_LDS_BYTES, st->s, (const CbJob*)d[0], (int)count,
-                           d_tlwe0, key->n, key->spectra(), key->tab(), d_tlwe2, D.fft_err);
+        auto kern = G.debug ? cb_rotate_fft_kernel<4, 9, true, Job, Shared...> : cb_rotate_fft_kernel<4, 9, false, Job, Shared...>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)cb_fft_grid((long)count, D.cus)), dim3(CBF_LANES), CBF_LDS_BYTES, st->s, (const Job*)d[0], count,
+                           d_tlwe0, key->n, key->spectra(), key->tab(), d_tlwe2, D.fft_err, shared...);
     }
     else if (plan.form == CB_FORM_LAT)
-        hipLaunchKernelGGL((cb_rotate_lat_kernel<4, 9>), dim3((unsigned)plan.grid), dim3(CBL_LANES), CBL_LDS_BYTES, st->s, (const CbJob*)d[0],
-                           (int)count, d_tlwe0, key->n, (const u64*)key->d, (const u64*)key->tw, d_tlwe2);
+        hipLaunchKernelGGL((cb_rotate_lat_kernel<4, 9, Job, Shared...>), dim3((unsigned)plan.grid), dim3(CBL_LANES), CBL_LDS_BYTES, st->s,
+                           (const Job*)d[0], count, d_tlwe0, key->n, (const u64*)key->d, (const u64*)key->tw, d_tlwe2, shared...);
     else
-        hipLaunchKernelGGL((cb_rotate_kernel<4, 9>), dim3((unsigned)plan.grid), dim3(CB_LANES), CB_LDS_BYTES, st->s, (const CbJob*)d[0],
-                           (int)count, d_tlwe0, key->n, (const u64*)key->d, (const u64*)key->tw, d_tlwe2);
+        hipLaunchKernelGGL((cb_rotate_kernel<4, 9, Job, Shared...>), dim3((unsigned)plan.grid), dim3(CB_LANES), CB_LDS_BYTES, st->s,
+                           (const Job*)d[0], count, d_tlwe0, key->n, (const u64*)key->d, (const u64*)key->tw, d_tlwe2, shared...);
     HIP_TRY(hipGetLastError());
     if (timed) {
         HIP_TRY(hipEventRecord(st->ev_br1, st->s));
@@ -2888,6 +2899,25 @@ int iyk_hip_cb_rotate_batch(iyk_hip_stream* st, const void* key_, const uint32_t
     std::vector<CbJob> jobs;
     if (const args::Refusal r = args::check_cb_rotate_batch(tlwe0_slots, tlwe2_slots, count, in, sign, off, mu, out, jobs)) return refuse(r);
     return launch_cb_rotate(st, key, d_tlwe0, d_tlwe2, jobs);
+    IYK_API_END
+}
+
+int iyk_hip_cb_rotate_many_batch(iyk_hip_stream* st, const void* key_, const uint32_t* d_tlwe0, uint64_t tlwe0_slots, uint64_t count,
+                                 const int32_t* in, const int32_t* sign, const uint32_t* off, uint32_t l, const uint64_t* mu, uint64_t* d_tlwe2,
+                                 uint64_t tlwe2_slots, const int32_t* out)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    const Bk2Key* key = (const Bk2Key*)key_;
+    if (!st || !key || !d_tlwe0 || !in || !sign || !off || !mu || !d_tlwe2 || !out) return fail(IYK_ERR_INVALID, "null argument");
+    if (st->gpu != key->gpu) return fail(IYK_ERR_INVALID, "the stream and the key are on different GPUs");
+    if (count == 0) return IYK_OK;
+    if (int rc = set_device(st->gpu)) return rc;
+    std::vector<CbManyJob> jobs;
+    CbManyMu shared;
+    if (const args::Refusal r = args::cb_rotate_many_args(tlwe0_slots, tlwe2_slots, count, in, sign, off, l, mu, out, jobs, shared))
+        return refuse(r);
+    return launch_cb_rotate(st, key, d_tlwe0, d_tlwe2, jobs, shared);
     IYK_API_END
 }
 
@@ -2931,6 +2961,34 @@ int iyk_hip_circuit_bootstrap_batch(iyk_hip_stream* st, const void* bk2_key, con
     if ((rc = ensure_stage(st, std::max({lists.rot.size() * sizeof(CbJob), lists.privks.size() * sizeof(PrivksJob), lists.rows.size() * sizeof(int32_t)}))))
         return rc;
     if ((rc = launch_cb_rotate(st, bk2, d_tlwe0, d_tlwe2, lists.rot))) return rc;
+    if ((rc = launch_privks(st, pk, d_tlwe2, d_trlwe, lists.privks))) return rc;
+    return launch_trgsw_from_rows(st, d_trgsw, bits, lists.sel.data(), d_trlwe, lists.rows.data());
+    IYK_API_END
+}
+
+int iyk_hip_circuit_bootstrap_many_batch(iyk_hip_stream* st, const void* bk2_key, const void* privks_key, const uint32_t* d_tlwe0,
+                                         uint64_t tlwe0_slots, const int32_t* in, const int32_t* sign, uint64_t* d_tlwe2, uint32_t tlwe2_n_in,
+                                         uint64_t tlwe2_slots, uint64_t tlwe2_first, uint32_t* d_trlwe, uint64_t trlwe_slots, void* d_trgsw,
+                                         uint64_t trgsw_slots, uint64_t trgsw_first, uint64_t bits)
+{
+    IYK_API_BEGIN
+    if (int rc = need_fft_path("iyk_hip_circuit_bootstrap_many_batch")) return rc;
+    const Bk2Key* bk2 = (const Bk2Key*)bk2_key;
+    const PrivksKey* pk = (const PrivksKey*)privks_key;
+    if (!st || !bk2 || !pk || !d_tlwe0 || !in || !sign || !d_tlwe2 || !d_trlwe || !d_trgsw) return fail(IYK_ERR_INVALID, "null argument");
+    if (st->gpu != bk2->gpu || st->gpu != pk->gpu) return fail(IYK_ERR_INVALID, "the stream and the key are on different GPUs");
+    if (bits == 0) return IYK_OK;
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    // as iyk_hip_circuit_bootstrap_batch: every check, then the two buffers the launches could have to grow, then the launches
+    args::CbManyLists lists;
+    if (const args::Refusal r = args::circuit_bootstrap_many_args(G.p, bk2->n, pk->n_in, tlwe0_slots, in, sign, tlwe2_n_in, tlwe2_slots,
+                                                                         tlwe2_first, trlwe_slots, trgsw_slots, trgsw_first, bits, lists))
+        return refuse(r);
+    if ((rc = ensure_sel(st, bits, trgsw_polys() * NTT_N))) return rc;
+    if ((rc = ensure_stage(st, std::max({lists.rot.size() * sizeof(CbManyJob), lists.privks.size() * sizeof(PrivksJob), lists.rows.size() * sizeof(int32_t)}))))
+        return rc;
+    if ((rc = launch_cb_rotate(st, bk2, d_tlwe0, d_tlwe2, lists.rot, lists.shared))) return rc;
     if ((rc = launch_privks(st, pk, d_tlwe2, d_trlwe, lists.privks))) return rc;
     return launch_trgsw_from_rows(st, d_trgsw, bits, lists.sel.data(), d_trlwe, lists.rows.data());
     IYK_API_END

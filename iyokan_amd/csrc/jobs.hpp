@@ -72,10 +72,24 @@ struct CbJob {
     uint64_t mu;
 };
 
+// the many-digit form of the same rotation: one job per address bit writes the l lvl2 TLWEs out .. out + l - 1
+struct CbManyJob {
+    int32_t in, sign;
+    uint32_t off;
+    int32_t out;
+};
+// what a many-digit batch shares, a kernel argument: mu[r] for r < l, 0 behind; bw = the smallest integer with 2^bw >= l
+static constexpr uint32_t CB_MANY_MAX_L = 4;
+struct CbManyMu {
+    uint64_t mu0, mu1, mu2, mu3;   // named words, no array: a kernel argument read by index would be copied to scratch memory
+    uint32_t l, bw;
+};
+
 static_assert(sizeof(RotJob) == 20 && sizeof(KsJob) == 16 && sizeof(EwJob) == 12 && sizeof(TrlweAddJob) == 12, "job layout is the upload format");
 static_assert(sizeof(CmuxJob) == 20 && sizeof(CmuxChainJob) == 24 && sizeof(PrivksJob) == 12 && sizeof(CbJob) == 24, "job layout is the upload format");
 static_assert(sizeof(CmuxRotChainJob) == 16 && sizeof(CmuxRotStep) == 8, "job layout is the upload format");
 static_assert(sizeof(CmuxTreeJob) == 16, "job layout is the upload format");
+static_assert(sizeof(CbManyJob) == 16 && sizeof(CbManyMu) == 40, "job layout is the upload format");
 
 static constexpr int CMUX_CHAIN_MAX_STEPS = 32;       // the bits of CmuxChainJob::pattern
 static constexpr int CMUX_ROT_CHAIN_MAX_STEPS = 32;   // steps of one CmuxRotChainJob: count * 32 steps bound the step list's 32-bit index

@@ -42,7 +42,7 @@ EXPORTS = [
     "iyk_hip_tlwe2_alloc", "iyk_hip_tlwe2_free", "iyk_hip_tlwe2_upload", "iyk_hip_tlwe2_download", "iyk_hip_privks_batch",
     "iyk_hip_trgsw_from_rows",
     "iyk_hip_bk2_key_create", "iyk_hip_bk2_key_upload", "iyk_hip_bk2_key_free", "iyk_hip_bk2_key_bytes", "iyk_hip_cb_rotate_batch",
-    "iyk_hip_circuit_bootstrap_batch", "iyk_hip_cb_rotate_form", "iyk_hip_bk2_key_create_form", "iyk_hip_bk2_key_form",
+    "iyk_hip_circuit_bootstrap_batch", "iyk_hip_cb_rotate_many_batch", "iyk_hip_circuit_bootstrap_many_batch", "iyk_hip_cb_rotate_form", "iyk_hip_bk2_key_create_form", "iyk_hip_bk2_key_form",
     "iyk_hip_cmux_rotate_chain_batch", "iyk_hip_cmux_tree_batch", "iyk_hip_stream_wait_stream",
     "iyk_hip_gate_batch_lanes",
     "iyk_hip_cmux_batch_lanes", "iyk_hip_cmux_chain_batch_lanes", "iyk_hip_cmux_rotate_chain_batch_lanes", "iyk_hip_cmux_tree_batch_lanes",
@@ -130,9 +130,11 @@ def lib():
         L.iyk_hip_bk2_key_free.argtypes = [_vp]
         L.iyk_hip_bk2_key_bytes.argtypes = [ctypes.c_int, ctypes.POINTER(u64)]
         L.iyk_hip_cb_rotate_batch.argtypes = [_vp, _vp, _vp, u64, u64, _i32p, _i32p, _u32p, _u64p, _vp, u64, _i32p]
+        L.iyk_hip_cb_rotate_many_batch.argtypes = [_vp, _vp, _vp, u64, u64, _i32p, _i32p, _u32p, u32, _u64p, _vp, u64, _i32p]
         L.iyk_hip_cb_rotate_form.argtypes = [ctypes.c_int, u64, ctypes.POINTER(ctypes.c_int)]
         L.iyk_hip_trgsw_from_rows.argtypes = [_vp, _vp, u64, u64, _i32p, _vp, u64, _i32p]
         L.iyk_hip_circuit_bootstrap_batch.argtypes = [_vp, _vp, _vp, _vp, u64, _i32p, _i32p, _vp, u32, u64, u64, _vp, u64, _vp, u64, u64, u64]
+        L.iyk_hip_circuit_bootstrap_many_batch.argtypes = L.iyk_hip_circuit_bootstrap_batch.argtypes
         L.iyk_hip_last_batch_timing.argtypes = [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.iyk_hip_resident_key_bytes.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
         L.iyk_hip_level_cost_ms.restype = ctypes.c_double
@@ -710,6 +712,22 @@ class Stream:
         _check(lib().iyk_hip_cb_rotate_batch(self.h, key.h, arena.ptr, arena.slots, len(in_), p(in_), p(sign), off.ctypes.data_as(_u32p),
                                              mu.ctypes.data_as(_u64p), tlwe2.ptr, tlwe2.slots, p(out)), "iyk_hip_cb_rotate_batch")
 
+    def cb_rotate_many_batch(self, key, arena, in_, sign, off, mu, tlwe2, out):
+        """The many-digit form of cb_rotate_batch: ONE rotation per job gives the l = len(mu) lvl2 TLWEs of the constants mu[0 .. l), shared
+        by the batch — slot out[g] + r of the Tlwe2 store = a TLWE of 2 mu[r] where the phase of sign[g] * arena[in_[g]] + (0, off[g]) is
+        positive, of 0 where it is negative.  1 <= l <= 4; no two jobs' ranges out[g] .. out[g] + l - 1 may overlap.  l = 1 gives
+        cb_rotate_batch's words; for l > 1 the mod switch is coarser."""
+        in_, sign, out = map(_i32, (in_, sign, out))
+        off = np.ascontiguousarray(np.asarray(off, dtype=np.uint64) & np.uint64(0xFFFFFFFF), dtype=np.uint32)
+        mu = np.ascontiguousarray(mu, dtype=np.uint64).ravel()
+        assert len(in_) == len(sign) == len(off) == len(out)
+        if tlwe2.n_in != key.N2:
+            raise ValueError(f"the store holds TLWEs of n_in = {tlwe2.n_in}, the rotation writes n_in = {key.N2}")
+        p = lambda a: a.ctypes.data_as(_i32p)
+        _check(lib().iyk_hip_cb_rotate_many_batch(self.h, key.h, arena.ptr, arena.slots, len(in_), p(in_), p(sign), off.ctypes.data_as(_u32p),
+                                                  len(mu), mu.ctypes.data_as(_u64p), tlwe2.ptr, tlwe2.slots, p(out)),
+               "iyk_hip_cb_rotate_many_batch")
+
     def trgsw_from_rows(self, trgsw, out_slot, trlwe, rows):
         """Selector out_slot[g] of a Trgsw store from the (k+1) l torus-domain rows rows[g] of a Trlwe store (row order c l + r), on the
         device: the twin of Trgsw.upload for rows that never were on the host.  Asynchronous."""
@@ -734,6 +752,18 @@ class Stream:
         _check(lib().iyk_hip_circuit_bootstrap_batch(self.h, bk2.h, privks_key.h, arena.ptr, arena.slots, p(in_), p(sign), tlwe2.ptr,
                                                      tlwe2.n_in, tlwe2.slots, int(first), trlwe_scratch.ptr, trlwe_scratch.slots, trgsw.ptr,
                                                      trgsw.slots, int(first_slot), len(in_)), "iyk_hip_circuit_bootstrap_batch")
+
+    def circuit_bootstrap_many_batch(self, bk2, privks_key, arena, in_, sign, tlwe2, first, trlwe_scratch, trgsw, first_slot=0):
+        """circuit_bootstrap_batch with the many-digit rotation: one rotation per address bit instead of l, the same arguments, checks,
+        lvl2 slots, scratch rows and selector slots; cb_rotate_many_batch, privks_batch and trgsw_from_rows as ONE checked call."""
+        in_, sign = _i32(in_).ravel(), _i32(sign).ravel()
+        if len(in_) != len(sign):
+            raise ValueError(f"{len(in_)} input slots, {len(sign)} signs")
+        p = lambda a: a.ctypes.data_as(_i32p)
+        _check(lib().iyk_hip_circuit_bootstrap_many_batch(self.h, bk2.h, privks_key.h, arena.ptr, arena.slots, p(in_), p(sign), tlwe2.ptr,
+                                                          tlwe2.n_in, tlwe2.slots, int(first), trlwe_scratch.ptr, trlwe_scratch.slots,
+                                                          trgsw.ptr, trgsw.slots, int(first_slot), len(in_)),
+               "iyk_hip_circuit_bootstrap_many_batch")
 
     def last_batch_timing(self):
         """(blind_rotate_ms, keyswitch_ms) of the most recent batch, from HIP events on this stream."""

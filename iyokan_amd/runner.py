@@ -346,7 +346,7 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
     lanes: 1.  The memories hold one request: lanes > 1 (here or on the executor's backend) is a ValueError."""
 
     def __init__(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packet=None, decrypt_ram=None, words_only=False,
-                 rom_fused=False, tree_fused=False, stage_cb=False, refresh_aside=False, lanes=1, read_early=False):
+                 rom_fused=False, tree_fused=False, stage_cb=False, refresh_aside=False, lanes=1, read_early=False, cb_many=False):
         from . import cmux, hip
         from .params import params_80bit
 
@@ -354,10 +354,10 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
             raise ValueError("CMUX memories have no lanes (lanes > 1 is refused): a cmux.Rom / cmux.Ram holds ONE request's rows and "
                              "selectors — run the lowered (mux-*) form of the system with CipherEngine, or one lane")
         self._setup(system, executor, encrypt, decrypt, zero_row, bk2, privks_key, [packet], decrypt_ram, words_only, rom_fused, tree_fused,
-                    stage_cb, refresh_aside, 1, read_early)
+                    stage_cb, refresh_aside, 1, read_early, cb_many)
 
     def _setup(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packets, decrypt_ram, words_only, rom_fused, tree_fused,
-               stage_cb, refresh_aside, K, read_early=False):
+               stage_cb, refresh_aside, K, read_early=False, cb_many=False):
         """The engine for K lanes (CmuxLaneEngine; K = 1: this class).  Lane r's arena slots are lane 0's + r * the backend's lane stride,
         every memory is a cmux.Rom / cmux.Ram(lanes=K), and the lvl2 store and the TRLWE scratch hold K x the widest batch."""
         from . import cmux, hip
@@ -382,6 +382,7 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         self.bk2, self.privks_key, self.packets, self.decrypt_ram = bk2, privks_key, list(packets), decrypt_ram
         self.packet = self.packets[0]
         self.rom_fused, self.tree_fused, self.stage_cb = bool(rom_fused), bool(tree_fused), bool(stage_cb)
+        self.cb_many = bool(cb_many)   # every circuit bootstrapping is a circuit_bootstrap_many_batch: one rotation per address bit
         self.lanes, self.lane_stride = K, int(getattr(be, "lane_stride", 0))
         N, l, per = int(p.N), int(p.l), int(p.trgsw_rows)
         widest = K * self._cb_bits()
@@ -454,8 +455,12 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
 
     def _stage_selectors(self, pts):
         addr = self._lane_slots(np.concatenate([self._slots(pt.addr) for pt in pts]))   # lane-major: the stage-major selector slots
-        self.mem_stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, addr, [1] * len(addr), self.tlwe2, 0, self.scratch,
-                                                self.trgsw, self._stage_first_slot(pts))
+        self._cb_call()(self.bk2, self.privks_key, self.arena, addr, [1] * len(addr), self.tlwe2, 0, self.scratch, self.trgsw,
+                        self._stage_first_slot(pts))
+
+    def _cb_call(self):
+        """The circuit bootstrapping of the memories' stream: per digit, or with cb_many one rotation per bit (the same arguments)."""
+        return self.mem_stream.circuit_bootstrap_many_batch if self.cb_many else self.mem_stream.circuit_bootstrap_batch
 
     # ---- read_early: the reads on the port stream P, beside the executor's stream M (StagedPorts has the program order) ----
     def _read_groups(self, s):
@@ -502,8 +507,7 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
     def _port_selectors(self, pt):
         mem = self.mem[pt.name]
         addr = self._lane_slots(self._slots(pt.addr))   # lane r's selectors land at r * addr_width: the memory's own sel_stride
-        self.mem_stream.circuit_bootstrap_batch(self.bk2, self.privks_key, self.arena, addr, [1] * len(addr), self.tlwe2,
-                                                0, self.scratch, mem.trgsw, 0)
+        self._cb_call()(self.bk2, self.privks_key, self.arena, addr, [1] * len(addr), self.tlwe2, 0, self.scratch, mem.trgsw, 0)
 
     def _port_tree(self, pt):
         mem = self.mem[pt.name]
@@ -561,6 +565,17 @@ class CmuxCipherEngine(StagedPorts, CipherEngine):
         but what those downloads do."""
         self._join()
         return CipherEngine.state(self, done, reset_ran)
+
+    def _state_meta(self, done, reset_ran):
+        """cb_many is recorded where it is on (a snapshot without the key was taken with it off): the selectors a resume rebuilds, and
+        every word after them, are those of the setting the snapshot's words came from."""
+        meta = super()._state_meta(done, reset_ran)
+        return dict(meta, cb_many=True) if self.cb_many else meta
+
+    def check_state(self, snap):
+        super().check_state(snap)
+        if bool(snap.meta.get("cb_many", False)) != self.cb_many:
+            raise ValueError(f"the snapshot was taken with cb_many={bool(snap.meta.get('cb_many', False))}, this engine has cb_many={self.cb_many}")
 
     def _mem_shape(self, pt):
         mem = self.mem[pt.name]
@@ -627,13 +642,13 @@ class CmuxLaneEngine(CmuxCipherEngine):
     port_lanes = True   # run_packets: the memory ports of this engine have lanes
 
     def __init__(self, system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packets=None, decrypt_ram=None, words_only=False,
-                 rom_fused=False, tree_fused=False, stage_cb=False, refresh_aside=False, read_early=False):
+                 rom_fused=False, tree_fused=False, stage_cb=False, refresh_aside=False, read_early=False, cb_many=False):
         K = getattr(executor.be, "lanes", 1)
         packets = [None] * K if packets is None else list(packets)
         if len(packets) != K:
             raise ValueError(f"{len(packets)} packets for a backend with {K} lanes")
         self._setup(system, executor, encrypt, decrypt, zero_row, bk2, privks_key, packets, decrypt_ram, words_only, rom_fused, tree_fused,
-                    stage_cb, refresh_aside, K, read_early)
+                    stage_cb, refresh_aside, K, read_early, cb_many)
 
 
 def _at_width(system, nl, name):

@@ -21,6 +21,12 @@ CMUX memories) and K in --lanes (default 1 and 8), flags off: the ms per clock o
 Snapshot.save() of it into a temporary directory and Snapshot.load() + load_state() into a second, fresh engine of the same shape (up to
 the synchronisation of its streams, the rebuilt selectors included); median (min .. max), and the file's size.
 
+--cb-many: what one lvl2 rotation per address bit gains on a clock (the many-digit form): per system — ram-addr8bit
+and the three-port system of tools/cmux_system_measure.py (23 address bits in one stage) — and K in --lanes (default 1 and 8), flags off
+but for stage_cb on the three-port system (its one batch per stage is the 23 x K x l rotations the form divides by l): --pairs
+interleaved pairs of the engine with cb_many off and on, in ONE process; a figure as above.
+
+    python tools/cmux_lanes_measure.py --cb-many --pairs 3 >> profiles/cb_many_ab.txt
     python tools/cmux_lanes_measure.py --snapshot --pairs 3 >> profiles/snapshot_cost.txt
     python tools/cmux_lanes_measure.py --bk2-form ntt >> profiles/cmux_lanes_ab.txt
     python tools/cmux_lanes_measure.py --bk2-form fft >> profiles/cmux_lanes_ab.txt
@@ -139,6 +145,33 @@ def read_early_leg(m, args, keys, bk2, pk, head, gold):
                 print(f"   {K} | {title:25s} | {fmt(off)} | {fmt(on)} | {np.median(on) - np.median(off):+9.2f} | {'yes' if clear else 'no'}", flush=True)
 
 
+def cb_many_leg(m, args, keys, bk2, pk, head, gold):
+    import tempfile
+
+    sys.path.insert(0, os.path.join(HERE, "tools"))
+    import cmux_system_measure
+
+    l = int(keys.params.l)
+    systems = {"ram-addr8bit": (os.path.join(gold, "ram-addr8bit.toml"), {}),
+               "three-port": (cmux_system_measure.write_three_port(tempfile.mkdtemp()), {"stage_cb": True})}
+    print(f"\n{head.replace('; flags off', '')}; cb_many: {args.pairs} interleaved pairs (off, then on) per line, ms per clock, median (min .. max)",
+          flush=True)
+    print("   system | flags | K | lvl2 rotations of the widest batch, off -> on | off | on | on / off | every pair outside the larger spread", flush=True)
+    for name in args.systems or ["ram-addr8bit", "three-port"]:
+        path, flags = systems[name]
+        sysm = m.load_blueprint(path, cmux_memories=True)
+        for K in args.lanes or [1, 8]:
+            off, on = [], []
+            for _ in range(args.pairs):
+                off.append(one(m, keys, sysm, bk2, pk, K, args.clocks, **flags))
+                on.append(one(m, keys, sysm, bk2, pk, K, args.clocks, cb_many=True, **flags))
+            bits = K * (sum(pt.addr_width for pt in sysm.ports) if flags else max(pt.addr_width for pt in sysm.ports))
+            spread = max(max(off) - min(off), max(on) - min(on))
+            clear = all(abs(a - b) > spread for a, b in zip(off, on)) and len({a > b for a, b in zip(off, on)}) == 1
+            print(f"   {name} | {' + '.join(flags) or 'none'} | {K} | {bits * l} -> {bits} | {fmt(off)} | {fmt(on)} | "
+                  f"{np.median(on) / np.median(off):.2f} | {'yes' if clear else 'no'}", flush=True)
+
+
 def snapshot_leg(m, args, keys, bk2, pk, head, gold):
     import shutil
     import tempfile
@@ -186,6 +219,7 @@ def main():
     ap.add_argument("--defaults", action="store_true", help="the flags-off one-lane CmuxCipherEngine clock alone (of ram-addr8bit, or of --systems)")
     ap.add_argument("--read-early", action="store_true", help="read_early=True against the same engine without it, per system, K and flag set")
     ap.add_argument("--snapshot", action="store_true", help="state() + save() and load() + load_state() per system and K, beside the ms per clock")
+    ap.add_argument("--cb-many", action="store_true", help="cb_many=True against the same engine without it, per system and K")
     ap.add_argument("--sets", type=int, nargs="+", default=None, help="--read-early: which of the six flag sets (0 .. 5), default all")
     ap.add_argument("--root", default=HERE, help="the tree whose iyokan_amd package and library are measured")
     args = ap.parse_args()
@@ -222,6 +256,8 @@ def main():
         read_early_leg(m, args, keys, bk2, pk, head, gold)
     elif args.snapshot:
         snapshot_leg(m, args, keys, bk2, pk, head, gold)
+    elif args.cb_many:
+        cb_many_leg(m, args, keys, bk2, pk, head, gold)
     else:
         print(f"\n{head}; {args.pairs} interleaved pairs (K = 1, then K lanes) per K, median (min .. max)", flush=True)
         for name in args.systems or ["ram-addr8bit", "cahp-ruby"]:
