@@ -606,12 +606,14 @@ void blind_rotate_fft(const iyk_params* p, const u32* lin, const fft::cplx* bk_f
     const u32 bbar = br_modswitch_b(lin[p->n]);
     ALL_LANES br_init_acc(lane >> 5, lane & 31, bbar, p->mu, acc.data() + (lane >> 5) * NTT_N);
     static thread_local fft::cplx S[2][2][64][8], a[64][8];
-    static thread_local u32 u[64][16], lo[64][16];
+    static thread_local u32 u[64][16], u_b[64][16], lo[64][16];
     for (u32 i = 0; i < p->n; ++i) {
         const u32 ab = br_modswitch_a(lin[i]);
+        // as the kernel: the rotated difference of both polynomials once per step, b's moves into u at row L
+        ALL_LANES fft::diff16_pair<G>(lane, ab, acc.data(), u[lane], u_b[lane]);
         for (int r = 0; r < 2 * L; ++r) {
             const int c = r >= L ? 1 : 0, lvl = r - c * L;
-            if (lvl == 0) ALL_LANES fft::diff16<G>(lane, ab, acc.data() + c * NTT_N, u[lane]);
+            if (r == L) ALL_LANES std::memcpy(u[lane], u_b[lane], sizeof u[lane]);
             ALL_LANES fft::digits8<G>(lvl, u[lane], a[lane]);
             fft_forward_lf_wave(a, xb);
             const u32 row_off = (i * (u32)(2 * L) + (u32)r) * 4u * (u32)fft::M;
@@ -962,6 +964,25 @@ void blind_rotate_fft_lat(const iyk_params* p, const u32* lin, const fft::cplx* 
     for (u32 j = 1; j < (u32)NTT_N; ++j) tlwe1[j] = acc2[NTT_N + (NTT_N - j)];
     tlwe1[NTT_N] = acc2[2 * NTT_N];
 }
+
+// iyk_emul_diff16_pair: the three forms of a step's rotated differences, all 64 lanes, out [2][64][16]
+template <class G>
+int diff16_pair_forms(u32 abar, const u32* acc, int form, u32* out)
+{
+    u32(*ua)[16] = reinterpret_cast<u32(*)[16]>(out);
+    u32(*ub)[16] = reinterpret_cast<u32(*)[16]>(out + 64 * 16);
+    ALL_LANES
+    {
+        if (form == 0) {
+            fft::diff16<G>(lane, abar, acc, ua[lane]);
+            fft::diff16<G>(lane, abar, acc + NTT_N, ub[lane]);
+        }
+        else if (form == 1) fft::diff16_pair<G>(lane, abar, acc, ua[lane], ub[lane]);
+        else if (form == 2) fft::diff16_pair_device_order<G>(lane, abar, acc, ua[lane], ub[lane]);
+        else return -1;
+    }
+    return 0;
+}
 }  // namespace
 
 static int g_direct = 0;  // 80-bit set: Decomp<2, 10, 1> (IYK_HIP_DECOMP=direct on the device) instead of the split digits
@@ -1206,6 +1227,15 @@ int iyk_emul_fft_inverse2_selftest(unsigned seed, int scale_bits)
         bad += std::memcmp(&b[lane][q].im, &rb[lane][q].im, 8) != 0;
     }
     return bad;
+}
+/* The rotated difference of both polynomials of one accumulator block acc [2][1024] for all 64 lanes, out [2][64][16].  form 0: two
+ * calls of diff16; 1: diff16_pair's host path; 2: the host restatement of its device path's byte arithmetic
+ * (diff16_pair_device_order).  set as above.  Returns 0, or -1 for an unknown set or form. */
+int iyk_emul_diff16_pair(int set, uint32_t abar, const uint32_t* acc, int form, uint32_t* out)
+{
+    if (set == 0) return diff16_pair_forms<fft::Gadget<3, 6>>(abar, acc, form, out);
+    if (set == 1) return diff16_pair_forms<fft::Gadget<2, 10>>(abar, acc, form, out);
+    return -1;
 }
 /* The Linzer-Feig forward network (round 5) against a direct long-double evaluation A[k] = sum_j z[j] psi^(j (4 k + 1)) and
  * against the round-4 network on the same random input (integers of 16 bits).  which = 0: largest |LF - direct| relative to

@@ -518,8 +518,13 @@ __global__ __launch_bounds__(64 * BR_WAVES, 2) void blind_rotate_fft_kernel(
         if (i % FFT_BARRIER_EVERY == 0u) asm volatile("s_barrier" ::: "memory");
 
         fft::cplx S[2][2][8];   // [c'][half][k2]
-        u32 u[16];
-        // one row: (rotated difference at the first level of a polynomial,) digits, forward transform, MAC against the row's
+        // The rotated difference of BOTH polynomials, once per step and before the sums exist (fft::diff16_pair: index, address and
+        // sign mask are the same for a and b, one two-word read per coefficient serves both): the block's 64 result registers
+        // are taken while S is not live yet.  u_b waits in 16 registers through polynomial a's rows and moves into u at row L
+        // (16 v_mov, a scalar branch: u stays indexed by the compile-time level only, the row loop one code path).
+        u32 u[16], u_b[16];
+        fft::diff16_pair<G>(fft_lane_id(lane0), ab, acc_lds, u, u_b);
+        // one row: digits (of polynomial a's difference, from row L on of b's), forward transform, MAC against the row's
         // four key spectra, frequency block q = register q.  The key words come through a ring of KB_RING blocks (4 loads of
         // 16 bytes per lane each): blocks 0 .. KB_AHEAD-1 of a row were issued during the previous row's MAC and landed during
         // the transform; the rest are issued as ring slots free up, and the tail of a MAC issues the first blocks of the NEXT
@@ -528,14 +533,21 @@ __global__ __launch_bounds__(64 * BR_WAVES, 2) void blind_rotate_fft_kernel(
         // peeled out of the loop) made the register allocator copy or spill S (profiles/r04_fft_ab.txt).
 #pragma unroll
         for (int e = 0; e < 32; ++e) S[e >> 4][(e >> 3) & 1][e & 7] = {0.0, 0.0};
+        int lvl = 0;   // r mod L, counted beside r
 #pragma unroll 1
-        for (int r = 0; r < 2 * L; ++r) {
+        for (int r = 0; r < 2 * L; ++r, ++lvl) {
             // the lane id is RECOMPUTED (two v_mbcnt) where it is needed: kept in a register across the step it was the one
             // value the allocator spilled at 256 VGPRs, and its reload (scratch_load + s_waitcnt vmcnt(0)) waited for every key
             // load in flight, three times per step (round 5)
             int lane = fft_lane_id(lane0);
-            const int c = r >= L ? 1 : 0, lvl = r - c * L;
-            if (lvl == 0) fft::diff16<G>(lane, ab, acc_lds + c * NTT_N, u);
+            if (r == L) {
+                lvl = 0;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    u[e] = u_b[e];
+                    asm volatile("" : "+v"(u[e]));   // a move under a scalar branch, not sixteen selects in every row
+                }
+            }
             fft::cplx a[8];
             fft::digits8<G>(lvl, u, a);
             set_prio<FFT_PRIO_FWD1>();
