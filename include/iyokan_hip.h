@@ -402,6 +402,16 @@ int iyk_hip_privks_key_create(int gpu_index, uint32_t n_in, uint32_t t, uint32_t
 int iyk_hip_privks_key_upload(iyk_hip_stream* st, void* key, uint64_t first_row, uint64_t row_count, const uint32_t* host_rows);
 int iyk_hip_privks_key_free(void* key);
 int iyk_hip_privks_key_bytes(int gpu_index, uint64_t* out);
+/* A window of a SEEDED key: the client sends a public 256-bit mask seed and the b polynomials only, u32 [row_count][N] (half the bytes
+ * of _upload's window); the a polynomial of host row R is words 0 .. N - 1 of the ChaCha20 stream of (mask_seed, kind 1, R) — state
+ * words 4 .. 11 the seed as little-endian u32, 12 the block index inside the row, 13 / 14 the row index low / high, 15 the kind
+ * (csrc/key_expand.hpp) — and is written into the store by key_mask_expand_kernel on st, which also places the b halves.  host_b is
+ * copied before return and goes through the same page-locked ring as _upload.  Seeded and unseeded windows may be mixed on one key;
+ * the device-resident key is the same size either way.  Checked before anything is staged or launched: a null seed / key / buffer,
+ * a window outside the key, an empty window, a stream of another replica or GPU than the key's are IYK_ERR_INVALID and leave the
+ * store unchanged. */
+int iyk_hip_privks_key_upload_seeded(iyk_hip_stream* st, void* key, const uint8_t* mask_seed /* [32] */, uint64_t first_row,
+                                     uint64_t row_count, const uint32_t* host_b /* u32 [row_count][N] */);
 /* TLWE lvl2 store: u64 [slots][n_in+1], a[0 .. n_in-1] then b (TFHEpp::TLWE<lvl2param>) — what the lvl0 -> lvl2 blind rotation will
  * write.  upload / download move a contiguous range, ordered on the stream; the host buffer must stay valid until the stream is idle. */
 int iyk_hip_tlwe2_alloc(int gpu_index, uint32_t n_in, uint64_t slots, uint64_t** d_tlwe2_out);
@@ -451,6 +461,12 @@ int iyk_hip_bk2_key_upload(iyk_hip_stream* st, void* key, uint64_t first_step, u
                            const uint64_t* host_trgsw /* u64 [step_count][(k+1) l2][k+1][N2], torus domain */);
 int iyk_hip_bk2_key_free(void* key);
 int iyk_hip_bk2_key_bytes(int gpu_index, uint64_t* out);
+/* A window of a SEEDED lvl2 key, as iyk_hip_privks_key_upload_seeded: host_b holds the b polynomials only, the a polynomial of host row
+ * R = step (k+1) l2 + r is a[m] = w[2m] | w[2m+1] << 32 of the ChaCha20 stream of (mask_seed, kind 2, R).  The window is staged as
+ * _upload stages it, key_mask_expand_kernel fills the a polynomials of the staged torus-domain window, and the unchanged transform of
+ * the key's form runs behind it; the first upload of a key, seeded or not, sends the tables.  Same checks, same refusals. */
+int iyk_hip_bk2_key_upload_seeded(iyk_hip_stream* st, void* key, const uint8_t* mask_seed /* [32] */, uint64_t first_step,
+                                  uint64_t step_count, const uint64_t* host_b /* u64 [step_count][(k+1) l2][N2] */);
 /* count rotations, asynchronous on st, host arrays copied before return.  One workgroup per rotation; a batch wider than the GPU has
  * compute units runs in rounds inside the one launch.  Checked in O(count): every index inside its store, sign in {+1, -1}, no two jobs
  * with one out — a violation is IYK_ERR_INVALID and nothing is launched.  The kernel's time is what iyk_hip_last_batch_timing reports

@@ -44,6 +44,13 @@ def _lib():
                                                    ctypes.c_uint32, u64, u64, u64, ctypes.c_int, ctypes.c_int, _u32p]
         lib.iyk_client_bk2_rows.argtypes = [ctypes.c_uint32, _u32p, ctypes.c_uint32, _u32p, ctypes.c_uint32, ctypes.c_uint32,
                                             ctypes.c_double, u64, u64, u64, ctypes.c_int, ctypes.c_int, _u64p]
+        _seedp = ctypes.c_char_p
+        lib.iyk_client_chacha20_block.argtypes = [_u32p, _u32p]
+        lib.iyk_client_expand_key_masks.argtypes = [ctypes.c_uint32, _seedp, u64, u64, u64, _u32p]
+        lib.iyk_client_privks_key_rows_seeded.argtypes = [ctypes.POINTER(IykParams), _u32p, ctypes.c_uint32, _u32p, ctypes.c_uint32,
+                                                          ctypes.c_uint32, _seedp, u64, u64, u64, ctypes.c_int, ctypes.c_int, _u32p]
+        lib.iyk_client_bk2_rows_seeded.argtypes = [ctypes.c_uint32, _u32p, ctypes.c_uint32, _u32p, ctypes.c_uint32, ctypes.c_uint32,
+                                                   ctypes.c_double, _seedp, u64, u64, u64, ctypes.c_int, ctypes.c_int, _u64p]
         _LIB = lib
     return _LIB
 
@@ -205,15 +212,62 @@ def privks_key_total_rows(params, n_in, t, basebit):
     return (params.k + 1) * (int(n_in) + 1) * int(t) * ((1 << int(basebit)) - 1)
 
 
-def privks_key_rows(keys: KeySet, s2, t, basebit, first_row=0, row_count=None, seed=None, nthreads=None) -> np.ndarray:
+MASK_PRIVKS, MASK_BK2 = 1, 2   # the `kind` of a seeded key's mask stream (csrc/key_expand.hpp)
+
+
+def new_mask_seed() -> bytes:
+    """32 bytes from the OS: the PUBLIC mask seed of ONE seeded key.  Draw a new one for every key: two keys made with one seed share
+    their masks row for row."""
+    return os.urandom(32)
+
+
+def chacha20_block(state) -> np.ndarray:
+    """The ChaCha20 block function (RFC 8439 §2.3) on a state of 16 u32 words: the one copy the client's generators, the mask
+    expansion and the GPU kernel share (csrc/key_expand.hpp)."""
+    state = np.ascontiguousarray(state, dtype=np.uint32).reshape(16)
+    out = np.zeros(16, dtype=np.uint32)
+    if _lib().iyk_client_chacha20_block(_p32(state), _p32(out)) != 0:
+        raise ValueError("iyk_client_chacha20_block refused its arguments")
+    return out
+
+
+def _seed32(mask_seed) -> bytes:
+    seed = bytes(mask_seed)
+    if len(seed) != 32:
+        raise ValueError(f"a mask seed is 32 bytes, not {len(seed)}")
+    return seed
+
+
+def expand_key_masks(kind, mask_seed, first_row, row_count, words_per_row) -> np.ndarray:
+    """The masks of rows [first_row, first_row + row_count) of a seeded key -> u32 (row_count, words_per_row): kind MASK_PRIVKS with
+    words_per_row = N gives the a polynomials of the private key-switching key's rows, kind MASK_BK2 with words_per_row = 2 N2 those of the
+    lvl2 bootstrapping key's (`.view(np.uint64)`: a[m] = w[2m] | w[2m+1] << 32).  What the GPU writes in upload_seeded."""
+    out = np.zeros((int(row_count), int(words_per_row)), dtype=np.uint32)
+    rc = _lib().iyk_client_expand_key_masks(int(kind), _seed32(mask_seed), int(first_row), int(row_count), int(words_per_row), _p32(out))
+    if rc != 0:
+        raise ValueError(f"iyk_client_expand_key_masks refused its arguments ({rc})")
+    return out
+
+
+def privks_key_rows(keys: KeySet, s2, t, basebit, first_row=0, row_count=None, seed=None, nthreads=None, mask_seed=None) -> np.ndarray:
     """Rows [first_row, first_row + row_count) of the private key-switching key lvl2 -> lvl1, host layout
     u32 [k+1][n_in+1][t][2^basebit-1][k+1][N] flattened over its first four axes -> (row_count, 2N).  Row (c, i, j, u) is a TRLWE of
     zero (noise alpha1) plus sigma_i (u+1) 2^(32 - (j+1) basebit) at coefficient 0 of polynomial c, sigma_i = s2[i], sigma_{n_in} = -1.
-    Any window gives the same words as the whole key (an int seed), so a full-size key (2.35 GB) is made and uploaded in chunks."""
+    Any window gives the same words as the whole key (an int seed), so a full-size key (2.35 GB) is made and uploaded in chunks.
+    mask_seed (32 public bytes, new_mask_seed()): the SEEDED key — only the b halves, (row_count, N), half the bytes; the a half of row R
+    is expand_key_masks(MASK_PRIVKS, mask_seed, R, 1, N), and (a, b) has the phase of the unseeded row."""
     s2 = np.ascontiguousarray(s2, dtype=np.uint32)
     p = keys.params
     total = privks_key_total_rows(p, s2.size, t, basebit)
     row_count = total - first_row if row_count is None else int(row_count)
+    if mask_seed is not None:
+        out = np.zeros((max(row_count, 0), p.N), dtype=np.uint32)
+        rc = _lib().iyk_client_privks_key_rows_seeded(ctypes.byref(p), _p32(keys.s1), s2.size, _p32(s2), int(t), int(basebit),
+                                                      _seed32(mask_seed), int(first_row), row_count, 0 if seed is None else int(seed),
+                                                      int(seed is not None), _threads() if nthreads is None else int(nthreads), _p32(out))
+        if rc != 0:
+            raise ValueError(f"iyk_client_privks_key_rows_seeded refused its arguments ({rc})")
+        return out
     out = np.zeros((row_count, 2 * p.N), dtype=np.uint32)
     rc = _lib().iyk_client_privks_key_rows(ctypes.byref(p), _p32(keys.s1), s2.size, _p32(s2), int(t), int(basebit), int(first_row),
                                            row_count, 0 if seed is None else int(seed), int(seed is not None),
@@ -231,14 +285,24 @@ def encrypt_cb_digits(s2, bits, params, alpha, seed=None) -> np.ndarray:
     return encrypt_tlwe2(s2, msgs.ravel(), alpha, seed)
 
 
-def bk2_rows(keys: KeySet, s2, l2, Bgbit2, alpha2, first_step=0, step_count=None, seed=None, nthreads=None) -> np.ndarray:
+def bk2_rows(keys: KeySet, s2, l2, Bgbit2, alpha2, first_step=0, step_count=None, seed=None, nthreads=None, mask_seed=None) -> np.ndarray:
     """Steps [first_step, first_step + step_count) of the lvl2 bootstrapping key of the lvl0 -> lvl2 rotation, torus domain:
     u64 [step_count][(k+1) l2][k+1][N2], N2 = len(s2).  Row c l2 + j of step i is a lvl2 TRLWE of zero (noise alpha2) under the ring key s2
     plus s0[i] 2^(64 - (j+1) Bgbit2) at coefficient 0 of polynomial c.  The lvl2 TLWE key the rotation's outputs decrypt under is s2 as
-    tlwe2_phases takes it.  Any window gives the same words as the whole key (an int seed); at most MAX_THREADS threads."""
+    tlwe2_phases takes it.  Any window gives the same words as the whole key (an int seed); at most MAX_THREADS threads.
+    mask_seed (32 public bytes, new_mask_seed()): the SEEDED key — only the b halves, u64 [step_count][(k+1) l2][N2]; the a half of row
+    R = step (k+1) l2 + r is expand_key_masks(MASK_BK2, mask_seed, R, 1, 2 N2).view(np.uint64)."""
     s2 = np.ascontiguousarray(s2, dtype=np.uint32)
     s0 = np.ascontiguousarray(keys.s0, dtype=np.uint32)
     step_count = s0.size - first_step if step_count is None else int(step_count)
+    if mask_seed is not None:
+        out = np.zeros((max(step_count, 0), 2 * int(l2), s2.size), dtype=np.uint64)
+        rc = _lib().iyk_client_bk2_rows_seeded(s0.size, _p32(s0), s2.size, _p32(s2), int(l2), int(Bgbit2), float(alpha2), _seed32(mask_seed),
+                                               int(first_step), step_count, 0 if seed is None else int(seed), int(seed is not None),
+                                               _threads() if nthreads is None else int(nthreads), out.ctypes.data_as(_u64p))
+        if rc != 0:
+            raise ValueError(f"iyk_client_bk2_rows_seeded refused its arguments ({rc})")
+        return out
     out = np.zeros((max(step_count, 0), 2 * int(l2), 2, s2.size), dtype=np.uint64)
     rc = _lib().iyk_client_bk2_rows(s0.size, _p32(s0), s2.size, _p32(s2), int(l2), int(Bgbit2), float(alpha2), int(first_step), step_count,
                                     0 if seed is None else int(seed), int(seed is not None),

@@ -628,5 +628,22 @@ inline Refusal stream_wait_args(const void* st, const void* other, int st_replic
     return ACCEPT;
 }
 
+// ---- seeded key windows -------------------------------------------------------------------------------------------------------------
+
+// iyk_hip_privks_key_upload_seeded / iyk_hip_bk2_key_upload_seeded: a window [first, first + count) of a key of key_units rows (private
+// key) or steps (lvl2 key), its mask seed and its b halves.  *_replica / *_ordinal: as stream_wait_args, read from non-null handles
+// only.  An empty window is refused: a seeded call always launches the expansion, and a launch of no lanes is no launch.  The largest
+// legal window is the whole key.  Not named check_*, for cmux_rotate_chain_args' reason; tests/test_key_expand.py holds every refusal.
+inline Refusal key_upload_seeded_args(const void* st, const void* key, const void* mask_seed, const void* host_b, int st_replica,
+                                      int key_replica, int st_ordinal, int key_ordinal, uint64_t key_units, uint64_t first, uint64_t count)
+{
+    if (!st || !key || !mask_seed || !host_b) return invalid("null argument");
+    if (st_ordinal != key_ordinal) return invalid("the stream and the key are on different GPUs");
+    if (st_replica != key_replica) return invalid("the stream and the key belong to different replicas");
+    if (count == 0) return invalid("empty window");
+    if (first > key_units || count > key_units - first) return invalid("window outside the key");
+    return ACCEPT;
+}
+
 }  // namespace args
 }  // namespace iyk

@@ -23,6 +23,8 @@
 //   BK lvl2 (torus) u64[n][(k+1)l2][k+1][N2]     row r = c*l2 + j: TRLWE2(0) + s0[i]*2^(64-(j+1)Bgbit2) on poly c, coeff 0 (iyk_client_bk2_rows)
 //   private KSK    u32[k+1][n_in+1][t][2^basebit-1][k+1][N]   row (c, i, j, u): TRLWE(0) + sigma_i (u+1) 2^(32-(j+1)basebit) on poly c,
 //                                                coeff 0; sigma_i = s2[i], sigma_{n_in} = -1 (phase: f_c = 1 for c = 1, -s1(X) for c = 0)
+//   seeded keys    the b polynomials of the two keys above alone, u32 [rows][N] / u64 [n][(k+1)l2][N2], plus a public 256-bit mask seed:
+//                                                the a polynomials are key_expand.hpp's masks (iyk_client_*_seeded, iyk_client_expand_key_masks)
 #include <sys/random.h>
 
 #include <algorithm>
@@ -35,6 +37,9 @@
 #include <vector>
 
 #include "../../include/iyokan_hip_params.h"
+#include "key_expand.hpp"
+
+using namespace iyk;
 
 namespace {
 
@@ -48,27 +53,12 @@ class Rng {
     int avail_ = 0;          // unread 64-bit words in blk_
 
     static uint64_t rotl(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
-    static uint32_t rotl32(uint32_t x, int k) { return (x << k) | (x >> (32 - k)); }
-    void chacha_block()
+    void chacha_block()   // state: words 12, 13 = the 64-bit block counter, 14, 15 = 0; the block function is key_expand.hpp's
     {
-        static const uint32_t sigma[4] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u};
-        uint32_t in[16], x[16];
-        for (int i = 0; i < 4; ++i) in[i] = sigma[i];
-        for (int i = 0; i < 8; ++i) in[4 + i] = key_[i];
-        in[12] = (uint32_t)ctr_;
-        in[13] = (uint32_t)(ctr_ >> 32);
-        in[14] = in[15] = 0;
+        uint32_t in[16];
+        kx::chacha20_state(key_, (uint32_t)ctr_, (uint32_t)(ctr_ >> 32), 0, 0, in);
         ++ctr_;
-        for (int i = 0; i < 16; ++i) x[i] = in[i];
-#define IYK_QR(a, b, c, d)                                                          \
-    x[a] += x[b]; x[d] = rotl32(x[d] ^ x[a], 16); x[c] += x[d]; x[b] = rotl32(x[b] ^ x[c], 12); \
-    x[a] += x[b]; x[d] = rotl32(x[d] ^ x[a], 8);  x[c] += x[d]; x[b] = rotl32(x[b] ^ x[c], 7);
-        for (int r = 0; r < 10; ++r) {
-            IYK_QR(0, 4, 8, 12) IYK_QR(1, 5, 9, 13) IYK_QR(2, 6, 10, 14) IYK_QR(3, 7, 11, 15)
-            IYK_QR(0, 5, 10, 15) IYK_QR(1, 6, 11, 12) IYK_QR(2, 7, 8, 13) IYK_QR(3, 4, 9, 14)
-        }
-#undef IYK_QR
-        for (int i = 0; i < 16; ++i) blk_[i] = x[i] + in[i];
+        kx::chacha20_block(in, blk_);
         avail_ = 8;
     }
 
@@ -145,6 +135,32 @@ void trlwe_encrypt_zero(const iyk_params* p, const uint32_t* s1, Rng& rng, uint3
         for (uint32_t x = 0; x < N - i; ++x) b[x + i] += a[x];
         for (uint32_t x = N - i; x < N; ++x) b[x + i - N] -= a[x];
     }
+}
+
+// b = a*s1 + e for a GIVEN a — the expanded mask of a seeded key row (key_expand.hpp): only the noise is drawn from rng
+void trlwe_zero_b_of(const iyk_params* p, const uint32_t* s1, Rng& rng, const uint32_t* a, uint32_t* b)
+{
+    const uint32_t N = p->N;
+    for (uint32_t x = 0; x < N; ++x) b[x] = rng.gauss_torus(p->alpha1);
+    for (uint32_t i = 0; i < N; ++i) {
+        if (!s1[i]) continue;
+        for (uint32_t x = 0; x < N - i; ++x) b[x + i] += a[x];
+        for (uint32_t x = N - i; x < N; ++x) b[x + i - N] -= a[x];
+    }
+}
+
+// fn(lo, hi) over [0, total) on at most min(nthreads, 16, total) threads: the rows of a key window
+template <class F>
+void over_rows(uint64_t total, int nthreads, F fn)
+{
+    const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)nthreads, 16, (int64_t)total}));
+    if (nt == 1) {
+        fn(0, total);
+        return;
+    }
+    std::vector<std::thread> pool;
+    for (int k = 0; k < nt; ++k) pool.emplace_back(fn, total * k / nt, total * (k + 1) / nt);
+    for (auto& th : pool) th.join();
 }
 
 }  // namespace
@@ -373,6 +389,104 @@ int iyk_client_bk2_rows(uint32_t n, const uint32_t* s0, uint32_t N2, const uint3
     std::vector<std::thread> pool;
     for (int k = 0; k < nt; ++k) pool.emplace_back(work, total * k / nt, total * (k + 1) / nt);
     for (auto& th : pool) th.join();
+    return 0;
+}
+
+// ---- seeded keys (key_expand.hpp): the client sends the b halves and a PUBLIC 256-bit mask seed, the masks are regenerated -----------
+//
+// A seeded row is (a', b) with a' = the expanded mask of (mask_seed, kind, host row index) and the phase of the unseeded row: a message
+// v on polynomial 1 is b[0] += v as before; a message v on polynomial 0 (the unseeded row is (a + v, b), phase e - v s(X)) becomes
+// b -= v s(X), since a' itself cannot move.  Noise and nothing else comes from the row's private generator, seeded as in the unseeded
+// call; the mask seed must be fresh per key.
+
+// key_expand.hpp's block function on a whole state of 16 words (RFC 8439 §2.3): the one copy every generator here runs, for tests
+int iyk_client_chacha20_block(const uint32_t* state, uint32_t* out)
+{
+    if (!state || !out || state == out) return -1;
+    kx::chacha20_block(state, out);
+    return 0;
+}
+
+// The masks themselves: rows [first_row, first_row + row_count) of kind `kind`, words_per_row u32 words each (N of the private key,
+// 2 N2 of the lvl2 key: a[m] = w[2m] | w[2m+1] << 32) -> out u32 [row_count][words_per_row].  first_row is any 64-bit row index.
+int iyk_client_expand_key_masks(uint32_t kind, const uint8_t* mask_seed, uint64_t first_row, uint64_t row_count, uint64_t words_per_row,
+                                uint32_t* out)
+{
+    if (!mask_seed || !out || (kind != kx::KIND_PRIVKS && kind != kx::KIND_BK2) || words_per_row == 0 ||
+        words_per_row > (uint64_t)kx::BLOCK_WORDS << 32 || row_count > UINT64_MAX - first_row)
+        return -1;
+    const kx::MaskKey key = kx::mask_key_of(mask_seed);
+    for (uint64_t q = 0; q < row_count; ++q) kx::mask_row(key, kind, first_row + q, words_per_row, out + q * words_per_row);
+    return 0;
+}
+
+// iyk_client_privks_key_rows for a seeded key: out_b u32 [row_count][N], the b polynomials of the rows
+int iyk_client_privks_key_rows_seeded(const iyk_params* p, const uint32_t* s1, uint32_t n_in, const uint32_t* s2, uint32_t t, uint32_t basebit,
+                                      const uint8_t* mask_seed, uint64_t first_row, uint64_t row_count, uint64_t seed, int deterministic,
+                                      int nthreads, uint32_t* out_b)
+{
+    if (!p || p->k != 1 || basebit < 1 || basebit > 8 || t == 0 || (uint64_t)basebit * t > 63 || n_in == 0 || !mask_seed || !out_b) return -1;
+    const uint64_t nb = (1u << basebit) - 1, n1 = (uint64_t)n_in + 1, total = (p->k + 1) * n1 * t * nb;
+    if (first_row > total || row_count > total - first_row) return -1;
+    const uint32_t N = p->N;
+    const kx::MaskKey key = kx::mask_key_of(mask_seed);
+    over_rows(row_count, nthreads, [&](uint64_t lo, uint64_t hi) {
+        std::vector<uint32_t> a(N);
+        for (uint64_t q = lo; q < hi; ++q) {
+            const uint64_t R = first_row + q;
+            const uint32_t u = (uint32_t)(R % nb), j = (uint32_t)(R / nb % t), i = (uint32_t)(R / nb / t % n1), c = (uint32_t)(R / nb / t / n1);
+            Rng rng(seed ^ (0xD1342543DE82EF95ull * (R + 1)), deterministic);
+            uint32_t* b = out_b + q * N;
+            kx::mask_row(key, kx::KIND_PRIVKS, R, N, a.data());
+            trlwe_zero_b_of(p, s1, rng, a.data(), b);
+            const uint32_t sh = (j + 1) * basebit;
+            const uint32_t m = sh <= 32 ? (uint32_t)(((uint64_t)(u + 1) << (32 - sh)) & 0xFFFFFFFFu) : 0u;
+            const uint32_t v = i == n_in ? 0u - m : s2[i] ? m : 0u;
+            if (c == 1) b[0] += v;
+            else
+                for (uint32_t x = 0; x < N; ++x)
+                    if (s1[x]) b[x] -= v;
+        }
+    });
+    return 0;
+}
+
+// iyk_client_bk2_rows for a seeded key: out_b u64 [step_count][(k+1) l2][N2], the b polynomials of the rows
+int iyk_client_bk2_rows_seeded(uint32_t n, const uint32_t* s0, uint32_t N2, const uint32_t* s2, uint32_t l2, uint32_t Bgbit2, double alpha2,
+                               const uint8_t* mask_seed, uint64_t first_step, uint64_t step_count, uint64_t seed, int deterministic,
+                               int nthreads, uint64_t* out_b)
+{
+    if (!s0 || !s2 || !out_b || !mask_seed || n == 0 || N2 == 0 || l2 == 0 || Bgbit2 == 0 || (uint64_t)l2 * Bgbit2 > 63) return -1;
+    if (first_step > n || step_count > n - first_step) return -1;
+    const uint64_t rows = 2ull * l2, total = step_count * rows;
+    const kx::MaskKey key = kx::mask_key_of(mask_seed);
+    over_rows(total, nthreads, [&](uint64_t lo, uint64_t hi) {
+        std::vector<uint32_t> w(2 * (size_t)N2);
+        std::vector<uint64_t> a(N2);
+        for (uint64_t q = lo; q < hi; ++q) {
+            const uint64_t R = first_step * rows + q, i = R / rows, r = R % rows;
+            Rng rng(seed ^ (0xA0761D6478BD642Full * (R + 1)), deterministic);
+            uint64_t* b = out_b + q * N2;
+            kx::mask_row(key, kx::KIND_BK2, R, 2 * (uint64_t)N2, w.data());
+            for (uint32_t x = 0; x < N2; ++x) {
+                a[x] = (uint64_t)w[2 * x] | (uint64_t)w[2 * x + 1] << 32;
+                double d = rng.gauss(alpha2);
+                d -= std::rint(d);
+                b[x] = (uint64_t)(int64_t)std::ldexp(d, 63) << 1;
+            }
+            for (uint32_t s = 0; s < N2; ++s) {
+                if (!s2[s]) continue;
+                for (uint32_t x = 0; x < N2 - s; ++x) b[x + s] += a[x];
+                for (uint32_t x = N2 - s; x < N2; ++x) b[x + s - N2] -= a[x];
+            }
+            const uint64_t c = r / l2, j = r % l2;
+            const uint64_t v = s0[i] ? 1ull << (64 - (j + 1) * Bgbit2) : 0ull;
+            if (c == 1) b[0] += v;
+            else
+                for (uint32_t x = 0; x < N2; ++x)
+                    if (s2[x]) b[x] -= v;
+        }
+    });
     return 0;
 }
 

@@ -24,6 +24,7 @@
 #include "cb_rotate.hpp"
 #include "cb_rotate_lat.hpp"
 #include "cb_rotate_fft.hpp"
+#include "key_expand.hpp"
 
 using namespace iyk;
 
@@ -1958,6 +1959,33 @@ int iyk_emul_stream_wait_args(uint64_t st, uint64_t other, int st_replica, int o
     return o.finish(args::stream_wait_args((const void*)(uintptr_t)st, (const void*)(uintptr_t)other, st_replica, other_replica, st_ordinal,
                                            other_ordinal));
 }
+/* args::key_upload_seeded_args; the four pointers as integers (0 = null).  No job list. */
+int iyk_emul_key_upload_seeded_args(uint64_t st, uint64_t key, uint64_t mask_seed, uint64_t host_b, int st_replica, int key_replica,
+                                    int st_ordinal, int key_ordinal, uint64_t key_units, uint64_t first, uint64_t count, IYK_CHECK_OUT)
+{
+    IYK_CHECK_OUT_INIT;
+    return o.finish(args::key_upload_seeded_args((const void*)(uintptr_t)st, (const void*)(uintptr_t)key, (const void*)(uintptr_t)mask_seed,
+                                                 (const void*)(uintptr_t)host_b, st_replica, key_replica, st_ordinal, key_ordinal, key_units,
+                                                 first, count));
+}
+}
+
+/* ---- key_expand.hpp: key_mask_expand_kernel lane by lane, under the launch shape the library would give it on `cus` compute units ----
+ * kind 1: dst = the first of row_count rows of the private key's device layout u32 [2 ring]; kind 2: the first of row_count rows of the
+ * lvl2 key's staged torus-domain window, u64 [2 ring] as u32 words.  src_b: the window's b halves as the client sent them. */
+extern "C" int iyk_emul_key_mask_expand(uint32_t kind, const uint8_t* mask_seed, uint64_t first_row, uint64_t row_count, uint32_t ring, int cus,
+                                        uint32_t* dst, const uint32_t* src_b)
+{
+    if (!mask_seed || !dst || !src_b || ring == 0 || ring % kx::BLOCK_WORDS) return -1;
+    const kx::MaskKey key = kx::mask_key_of(mask_seed);
+    if (kind != kx::KIND_PRIVKS && kind != kx::KIND_BK2) return -1;
+    const kx::ExpandArgs A = kind == kx::KIND_PRIVKS ? kx::privks_expand_args(key, first_row, row_count, ring)
+                                                     : kx::bk2_expand_args(key, first_row, row_count, ring);
+    if (!kx::expand_args_ok(A)) return -1;
+    const uint64_t total = A.row_count * A.blocks_per_row, step = (uint64_t)kx::expand_grid(total, cus) * kx::EXPAND_THREADS;
+    for (uint64_t lane = 0; lane < step; ++lane)   // every lane of the grid, each with the kernel's stride loop
+        for (uint64_t g = lane; g < total; g += step) kx::expand_lane(A, g, dst, src_b);
+    return 0;
 }
 
 /* ---- lane_jobs.hpp: K request packets of one circuit as one batch — iyk_emul_gate_batch_lanes_args, iyk_emul_lane_jobs, iyk_emul_lane_dispatch */

@@ -11,6 +11,7 @@
 
 #include "ntt32.hpp"
 #include "fpntt32.hpp"
+#include "key_expand.hpp"
 
 using namespace iyk;
 
@@ -297,11 +298,32 @@ static void test_fp50()
     std::printf("fp50 worst-case external product ok (max |x|/p inside transforms = %.3f)\n", g_maxabs);
 }
 
+// key_expand.hpp: the block function against RFC 8439 §2.3.2, and a mask block as the state layout of the header states it
+static void test_key_expand()
+{
+    uint32_t key[8], st[16], out[16];
+    for (int i = 0; i < 8; ++i) key[i] = (4u * i) | (4u * i + 1) << 8 | (4u * i + 2) << 16 | (4u * i + 3) << 24;   // 00 01 .. 1f
+    kx::chacha20_state(key, 1, 0x09000000u, 0x4a000000u, 0, st);
+    kx::chacha20_block(st, out);
+    static const uint32_t want[16] = {0xe4e7f110u, 0x15593bd1u, 0x1fdd0f50u, 0xc47120a3u, 0xc7f4d1c7u, 0x0368c033u, 0x9aaa2204u, 0x4e6cd4c3u,
+                                      0x466482d2u, 0x09aa9f07u, 0x05d7c214u, 0xa2028bd9u, 0xd19c12b5u, 0xb94e16deu, 0xe883d0cbu, 0x4e3c50a2u};
+    for (int i = 0; i < 16; ++i) CHECK(out[i] == want[i]);
+    uint8_t seed[32];
+    for (int i = 0; i < 32; ++i) seed[i] = (uint8_t)i;
+    const kx::MaskKey mk = kx::mask_key_of(seed);
+    for (int i = 0; i < 8; ++i) CHECK(mk.w[i] == key[i]);
+    uint32_t blk[16];
+    kx::mask_block(mk, 0, 0x4a00000009000000ull, 1, blk);   // row low / high = the vector's nonce words, kind 0 = its last
+    for (int i = 0; i < 16; ++i) CHECK(blk[i] == want[i]);
+    std::printf("key_expand ok\n");
+}
+
 int main()
 {
     test_field();
     test_ntt();
     test_fp50();
+    test_key_expand();
     std::printf("ALL OK\n");
     return 0;
 }

@@ -51,6 +51,7 @@
 #include "cb_rotate_fft.hpp"
 #include "lane_jobs.hpp"
 #include "cmux_lane_jobs.hpp"
+#include "key_expand.hpp"
 
 using namespace iyk;
 using namespace iyk::dispatch;
@@ -2605,6 +2606,56 @@ int iyk_hip_privks_key_upload(iyk_hip_stream* st, void* key_, uint64_t first_row
     IYK_API_END
 }
 
+namespace {
+
+constexpr uint64_t PRIVKS_SEEDED_CHUNK = 2 * PRIVKS_UPLOAD_CHUNK;   // b halves per staging slot: the same 2 MiB
+
+// the HIP device behind a replica index, -1 for none: what args::key_upload_seeded_args tells GPUs apart by
+int ordinal_of(int gpu) { return gpu >= 0 && gpu < (int)G.devs.size() ? G.devs[gpu].ordinal : -1; }
+
+// key_mask_expand_kernel over one staged chunk of a seeded window on st: dst the chunk's first destination row, src_b its b halves
+int launch_key_expand(iyk_hip_stream* st, const kx::ExpandArgs& A, u32* dst, const u32* src_b)
+{
+    if (!kx::expand_args_ok(A)) return fail(IYK_ERR_STATE, "key expansion: a window out of shape");
+    const uint64_t blocks = A.row_count * A.blocks_per_row;
+    hipLaunchKernelGGL(kx::key_mask_expand_kernel, dim3(kx::expand_grid(blocks, G.devs[st->gpu].cus)), dim3(kx::EXPAND_THREADS), 0, st->s, A, dst,
+                       src_b);
+    HIP_TRY(hipGetLastError());
+    return IYK_OK;
+}
+
+}  // namespace
+
+int iyk_hip_privks_key_upload_seeded(iyk_hip_stream* st, void* key_, const uint8_t* mask_seed, uint64_t first_row, uint64_t row_count,
+                                     const uint32_t* host_b)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    PrivksKey* key = (PrivksKey*)key_;
+    if (const args::Refusal r = args::key_upload_seeded_args(st, key, mask_seed, host_b, st ? st->gpu : -1, key ? key->gpu : -1,
+                                                             st ? ordinal_of(st->gpu) : -1, key ? ordinal_of(key->gpu) : -1, key ? key->rows : 0,
+                                                             first_row, row_count))
+        return refuse(r);
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    const kx::MaskKey mk = kx::mask_key_of(mask_seed);
+    for (uint64_t done = 0; done < row_count; done += PRIVKS_SEEDED_CHUNK) {
+        const uint64_t c = std::min<uint64_t>(PRIVKS_SEEDED_CHUNK, row_count - done);
+        const size_t bytes = (size_t)c * NTT_N * sizeof(u32);
+        size_t soff = 0;
+        if ((rc = acquire_stage(st, bytes, &soff))) return rc;
+        std::memcpy(st->h_stage + soff, host_b + (size_t)done * NTT_N, bytes);   // the caller's b halves are free on return
+        HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+        // the kernel writes the rows' masks and moves their b halves out of the slot, so the slot is free when the kernel is done
+        if ((rc = launch_key_expand(st, kx::privks_expand_args(mk, first_row + done, c, NTT_N), key->d + (size_t)(first_row + done) * 2 * NTT_N,
+                                    (const u32*)(st->d_stage + soff))))
+            return rc;
+        if ((rc = release_stage(st))) return rc;
+    }
+    return IYK_OK;
+    IYK_API_END
+}
+
 int iyk_hip_tlwe2_alloc(int gpu_index, uint32_t n_in, uint64_t slots, uint64_t** out)
 {
     if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
@@ -2729,6 +2780,33 @@ struct Bk2Key {
 };
 constexpr uint64_t BK2_UPLOAD_CHUNK = 8;   // key steps per staging slot (2 MiB of torus words)
 
+// once per key, by its first upload (create only allocates): the transform's tables, on that upload's stream, ahead of its window
+int bk2_send_tables(iyk_hip_stream* st, Bk2Key* key)
+{
+    if (key->tables_sent.exchange(true)) return IYK_OK;
+    const bool fft_form = key->form == BK2_FORM_FFT;
+    const size_t bytes = fft_form ? fft1k::TAB_POINTS * sizeof(fft::cplx) : 2 * CB_N * sizeof(u64);
+    size_t soff = 0;
+    if (int rc = acquire_stage(st, bytes, &soff)) return rc;
+    if (fft_form) fft1k::make_tables((fft::cplx*)(st->h_stage + soff));
+    else cb_make_tables((u64*)(st->h_stage + soff), (u64*)(st->h_stage + soff) + CB_N);
+    HIP_TRY(hipMemcpyAsync(fft_form ? (void*)key->tab() : (void*)key->tw, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
+    return release_stage(st);
+}
+
+// the key's transform of c staged torus-domain steps into steps first .. first + c - 1 of its store
+int bk2_transform(iyk_hip_stream* st, Bk2Key* key, const u64* d_torus, uint64_t first, uint64_t c)
+{
+    if (key->form == BK2_FORM_FFT)   // one workgroup per (polynomial, quarter); the kernel places its spectrum from the step it is given
+        hipLaunchKernelGGL(bk2_fft_kernel, dim3((unsigned)(c * CB_ROWS * 2 * CBF_QUARTERS)), dim3(64), 0, st->s, d_torus,
+                           key->spectra() + (size_t)first * CBF_STEP_POINTS, key->tab());
+    else
+        hipLaunchKernelGGL(bk2_ntt_kernel, dim3((unsigned)(c * CB_ROWS * 2 * 2)), dim3(64), 0, st->s, d_torus,
+                           key->d + (size_t)first * CB_STEP_WORDS, (const u64*)key->tw);
+    HIP_TRY(hipGetLastError());
+    return IYK_OK;
+}
+
 }  // namespace
 
 int iyk_hip_bk2_key_create(int gpu_index, uint32_t n, uint32_t l2, uint32_t Bgbit2, void** out)
@@ -2811,16 +2889,7 @@ int iyk_hip_bk2_key_upload(iyk_hip_stream* st, void* key_, uint64_t first_step, 
     if (first_step > key->n || step_count > key->n - first_step) return fail(IYK_ERR_INVALID, "step range outside the key");
     int rc = set_device(st->gpu);
     if (rc) return rc;
-    const bool fft_form = key->form == BK2_FORM_FFT;
-    if (!key->tables_sent.exchange(true)) {   // once per key, by its first upload (create only allocates)
-        const size_t bytes = fft_form ? fft1k::TAB_POINTS * sizeof(fft::cplx) : 2 * CB_N * sizeof(u64);
-        size_t soff = 0;
-        if ((rc = acquire_stage(st, bytes, &soff))) return rc;
-        if (fft_form) fft1k::make_tables((fft::cplx*)(st->h_stage + soff));
-        else cb_make_tables((u64*)(st->h_stage + soff), (u64*)(st->h_stage + soff) + CB_N);
-        HIP_TRY(hipMemcpyAsync(fft_form ? (void*)key->tab() : (void*)key->tw, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
-        if ((rc = release_stage(st))) return rc;
-    }
+    if ((rc = bk2_send_tables(st, key))) return rc;
     for (uint64_t done = 0; done < step_count; done += BK2_UPLOAD_CHUNK) {
         const uint64_t c = std::min<uint64_t>(BK2_UPLOAD_CHUNK, step_count - done);
         const size_t bytes = (size_t)c * CB_TORUS_STEP_WORDS * sizeof(u64);
@@ -2828,13 +2897,39 @@ int iyk_hip_bk2_key_upload(iyk_hip_stream* st, void* key_, uint64_t first_step, 
         if ((rc = acquire_stage(st, bytes, &soff))) return rc;
         std::memcpy(st->h_stage + soff, host_trgsw + (size_t)done * CB_TORUS_STEP_WORDS, bytes);   // the caller's window is free on return
         HIP_TRY(hipMemcpyAsync(st->d_stage + soff, st->h_stage + soff, bytes, hipMemcpyHostToDevice, st->s));
-        if (fft_form)   // one workgroup per (polynomial, quarter); the kernel places its spectrum from the step it is given
-            hipLaunchKernelGGL(bk2_fft_kernel, dim3((unsigned)(c * CB_ROWS * 2 * CBF_QUARTERS)), dim3(64), 0, st->s, (const u64*)(st->d_stage + soff),
-                               key->spectra() + (size_t)(first_step + done) * CBF_STEP_POINTS, key->tab());
-        else
-            hipLaunchKernelGGL(bk2_ntt_kernel, dim3((unsigned)(c * CB_ROWS * 2 * 2)), dim3(64), 0, st->s, (const u64*)(st->d_stage + soff),
-                               key->d + (size_t)(first_step + done) * CB_STEP_WORDS, (const u64*)key->tw);
-        HIP_TRY(hipGetLastError());
+        if ((rc = bk2_transform(st, key, (const u64*)(st->d_stage + soff), first_step + done, c))) return rc;
+        if ((rc = release_stage(st))) return rc;
+    }
+    return IYK_OK;
+    IYK_API_END
+}
+
+int iyk_hip_bk2_key_upload_seeded(iyk_hip_stream* st, void* key_, const uint8_t* mask_seed, uint64_t first_step, uint64_t step_count,
+                                  const uint64_t* host_b)
+{
+    IYK_API_BEGIN
+    if (!G.init.load()) return fail(IYK_ERR_STATE, "not initialised");
+    Bk2Key* key = (Bk2Key*)key_;
+    if (const args::Refusal r = args::key_upload_seeded_args(st, key, mask_seed, host_b, st ? st->gpu : -1, key ? key->gpu : -1,
+                                                             st ? ordinal_of(st->gpu) : -1, key ? ordinal_of(key->gpu) : -1, key ? key->n : 0,
+                                                             first_step, step_count))
+        return refuse(r);
+    int rc = set_device(st->gpu);
+    if (rc) return rc;
+    if ((rc = bk2_send_tables(st, key))) return rc;
+    const kx::MaskKey mk = kx::mask_key_of(mask_seed);
+    for (uint64_t done = 0; done < step_count; done += BK2_UPLOAD_CHUNK) {
+        const uint64_t c = std::min<uint64_t>(BK2_UPLOAD_CHUNK, step_count - done);
+        // the slot: the torus-domain window as the unseeded call stages it, then the b halves the client sent (half as many bytes)
+        const size_t window = (size_t)c * CB_TORUS_STEP_WORDS * sizeof(u64), half = window / 2;
+        size_t soff = 0;
+        if ((rc = acquire_stage(st, window + half, &soff))) return rc;
+        std::memcpy(st->h_stage + soff + window, host_b + (size_t)done * (CB_TORUS_STEP_WORDS / 2), half);   // free on return
+        HIP_TRY(hipMemcpyAsync(st->d_stage + soff + window, st->h_stage + soff + window, half, hipMemcpyHostToDevice, st->s));
+        if ((rc = launch_key_expand(st, kx::bk2_expand_args(mk, (first_step + done) * CB_ROWS, c * CB_ROWS, CB_N), (u32*)(st->d_stage + soff),
+                                    (const u32*)(st->d_stage + soff + window))))
+            return rc;
+        if ((rc = bk2_transform(st, key, (const u64*)(st->d_stage + soff), first_step + done, c))) return rc;
         if ((rc = release_stage(st))) return rc;
     }
     return IYK_OK;

@@ -46,6 +46,7 @@ EXPORTS = [
     "iyk_hip_cmux_rotate_chain_batch", "iyk_hip_cmux_tree_batch", "iyk_hip_stream_wait_stream",
     "iyk_hip_gate_batch_lanes",
     "iyk_hip_cmux_batch_lanes", "iyk_hip_cmux_chain_batch_lanes", "iyk_hip_cmux_rotate_chain_batch_lanes", "iyk_hip_cmux_tree_batch_lanes",
+    "iyk_hip_privks_key_upload_seeded", "iyk_hip_bk2_key_upload_seeded",
 ]
 
 
@@ -116,6 +117,7 @@ def lib():
         u32 = ctypes.c_uint32
         L.iyk_hip_privks_key_create.argtypes = [ctypes.c_int, u32, u32, u32, ctypes.POINTER(_vp)]
         L.iyk_hip_privks_key_upload.argtypes = [_vp, _vp, u64, u64, _u32p]
+        L.iyk_hip_privks_key_upload_seeded.argtypes = [_vp, _vp, ctypes.c_char_p, u64, u64, _u32p]
         L.iyk_hip_privks_key_free.argtypes = [_vp]
         L.iyk_hip_privks_key_bytes.argtypes = [ctypes.c_int, ctypes.POINTER(u64)]
         L.iyk_hip_tlwe2_alloc.argtypes = [ctypes.c_int, u32, u64, ctypes.POINTER(_vp)]
@@ -127,6 +129,7 @@ def lib():
         L.iyk_hip_bk2_key_create_form.argtypes = [ctypes.c_int, u32, u32, u32, ctypes.c_int, ctypes.POINTER(_vp)]
         L.iyk_hip_bk2_key_form.argtypes = [_vp, ctypes.POINTER(ctypes.c_int)]
         L.iyk_hip_bk2_key_upload.argtypes = [_vp, _vp, u64, u64, _u64p]
+        L.iyk_hip_bk2_key_upload_seeded.argtypes = [_vp, _vp, ctypes.c_char_p, u64, u64, _u64p]
         L.iyk_hip_bk2_key_free.argtypes = [_vp]
         L.iyk_hip_bk2_key_bytes.argtypes = [ctypes.c_int, ctypes.POINTER(u64)]
         L.iyk_hip_cb_rotate_batch.argtypes = [_vp, _vp, _vp, u64, u64, _i32p, _i32p, _u32p, _u64p, _vp, u64, _i32p]
@@ -353,6 +356,14 @@ class Trgsw:
         self.ptr = None
 
 
+def _mask_seed(mask_seed):
+    """the 32 bytes of a key's public mask seed (client.new_mask_seed)"""
+    seed = bytes(mask_seed)
+    if len(seed) != 32:
+        raise ValueError(f"a mask seed is 32 bytes, not {len(seed)}")
+    return seed
+
+
 class PrivKsKey:
     """Device-resident private key-switching key lvl2 -> lvl1 of one GPU: u32 [k+1][n_in+1][t][2^basebit-1][2N] (client.privks_key_rows),
     uploaded in windows of rows."""
@@ -371,6 +382,13 @@ class PrivKsKey:
         host = np.ascontiguousarray(host_rows, dtype=np.uint32).reshape(-1, self.words)
         _check(lib().iyk_hip_privks_key_upload(stream.h, self.h, int(first_row), host.shape[0], host.ctypes.data_as(_u32p)),
                "iyk_hip_privks_key_upload")
+
+    def upload_seeded(self, stream, mask_seed, first_row, b_rows):
+        """Rows first_row .. of a seeded key: the b halves (rows, N) of client.privks_key_rows(..., mask_seed=) and the key's public
+        32-byte mask seed; the a halves are expanded on the GPU.  Copied before return, ordered on the stream."""
+        host = np.ascontiguousarray(b_rows, dtype=np.uint32).reshape(-1, self.words // 2)
+        _check(lib().iyk_hip_privks_key_upload_seeded(stream.h, self.h, _mask_seed(mask_seed), int(first_row), host.shape[0],
+                                                      host.ctypes.data_as(_u32p)), "iyk_hip_privks_key_upload_seeded")
 
     def free(self):
         if self.h:
@@ -414,6 +432,13 @@ class Bk2Key:
         host = np.ascontiguousarray(host_steps, dtype=np.uint64).reshape(-1, self.step_words)
         _check(lib().iyk_hip_bk2_key_upload(stream.h, self.h, int(first_step), host.shape[0], host.ctypes.data_as(_u64p)),
                "iyk_hip_bk2_key_upload")
+
+    def upload_seeded(self, stream, mask_seed, first_step, b_steps):
+        """Steps first_step .. of a seeded key: the b halves (steps, (k+1) l2, N2) of client.bk2_rows(..., mask_seed=) and the key's
+        public 32-byte mask seed; the a halves are expanded on the GPU ahead of the transform.  Copied before return."""
+        host = np.ascontiguousarray(b_steps, dtype=np.uint64).reshape(-1, self.step_words // 2)
+        _check(lib().iyk_hip_bk2_key_upload_seeded(stream.h, self.h, _mask_seed(mask_seed), int(first_step), host.shape[0],
+                                                   host.ctypes.data_as(_u64p)), "iyk_hip_bk2_key_upload_seeded")
 
     def free(self):
         if self.h:
