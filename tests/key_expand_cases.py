@@ -1,4 +1,4 @@
-"""Builders for the seeded evaluation keys (tests/test_key_expand.py on the CPU, tests/test_gpu_key_seeded.py on the GPU): a numpy
+"""Builders for the seeded evaluation keys (tests/test_key_expand.py on the CPU, tests/test_gpu_key_seeded*.py on the GPU): a numpy
 restatement of the mask generator of csrc/key_expand.hpp written from RFC 8439 and the state layout DESIGN.md §6c states — nothing of
 the library is used by it — small real keys of both kinds in seeded and unseeded form, full rows rebuilt from b halves and masks, and
 the ctypes face of the kernel's emulation and of the pure argument check.  No GPU, no handle of the HIP library."""
@@ -75,7 +75,10 @@ def masks_u64(w):
 
 # ---- small real keys, seeded and unseeded ----------------------------------------------------------------------------------------------
 
-PRIVKS_SHAPES = {"small": (3, 2, 2), "wide": (3, 1, 8)}   # (n_in, t, basebit): 48 rows; 2040 rows, 255 per (c, i, j)
+# (n_in, t, basebit): 48 rows; 2040 rows, 255 per (c, i, j); 6120 rows = 12 staging chunks of 512, the smallest shape of this kind whose
+# whole-key upload takes more chunks than the ring has slots (9) with (j + 1) basebit <= 32 for every j
+PRIVKS_SHAPES = {"small": (3, 2, 2), "wide": (3, 1, 8), "ring": (3, 3, 8)}
+PRIVKS_CHUNK, BK2_CHUNK, STAGE_RING = 512, 8, 8           # iyokan_hip.hip: PRIVKS_SEEDED_CHUNK rows, BK2_UPLOAD_CHUNK steps, the ring's slots
 
 
 @functools.lru_cache(maxsize=None)
@@ -134,19 +137,60 @@ def odd_windows(total):
     return [(cut + 1, total - cut - 1), (0, cut), (cut, 1)]
 
 
+def chunk_windows(total, chunk):
+    """Three windows of a key of `total` units whose uploads are staged `chunk` units at a time, in the order they are sent: one that
+    starts a unit short of a chunk edge and ends on the next edge (a whole chunk at an unaligned destination, then a tail of one unit),
+    the rest of the key, the head."""
+    assert total > 2 * chunk
+    w = [(chunk - 1, chunk + 1), (2 * chunk, total - 2 * chunk), (0, chunk - 1)]
+    assert sorted(u for f, c in w for u in range(f, f + c)) == list(range(total))   # they tile [0, total) exactly once
+    return w
+
+
 BK2_N = 3
+_S0_SEED = 22   # the generator seed of the lvl0 secrets below: found by search for the properties _s0 asserts, and [1, 0, 1] at n = 3
 
 
-class _S0:
-    s0 = np.array([1, 0, 1], dtype=np.uint32)   # both bit values among the steps
+@functools.lru_cache(maxsize=None)
+def _s0(n):
+    """The lvl0 secret of the lvl2 test key of n steps, as what client.bk2_rows reads of a KeySet.  Both bit values occur among the first
+    staging chunk's steps and among the last chunk's (a last chunk of one step: it and the step before it differ)."""
+    ks = cb_rotate_cases.SmallKeys(n, _S0_SEED)
+    s0 = [int(v) for v in ks.s0]
+    last = s0[BK2_CHUNK * ((n - 1) // BK2_CHUNK):]
+    assert len(set(s0[:BK2_CHUNK])) == 2 and len(set(last if len(last) > 1 else s0[-2:])) == 2, (n, s0)
+    return ks
 
 
-def bk2_b(mask_seed=SEED_A, **kw):
-    return client.bk2_rows(_S0, lvl2_key(N2), L2, BGBIT2, ALPHA2, seed=33, mask_seed=mask_seed, **kw)
+_S0 = _s0(BK2_N)   # [1, 0, 1]: the key the n = 3 tests have always used
 
 
-def bk2_unseeded(**kw):
-    return client.bk2_rows(_S0, lvl2_key(N2), L2, BGBIT2, ALPHA2, seed=33, **kw)
+def bk2_b(mask_seed=SEED_A, n=BK2_N, **kw):
+    return client.bk2_rows(_s0(n), lvl2_key(N2), L2, BGBIT2, ALPHA2, seed=33, mask_seed=mask_seed, **kw)
+
+
+def bk2_unseeded(n=BK2_N, **kw):
+    return client.bk2_rows(_s0(n), lvl2_key(N2), L2, BGBIT2, ALPHA2, seed=33, **kw)
+
+
+REAL_N = 67   # 9 staging chunks, one more than the ring has slots: an upload in one call takes a slot of its own again
+
+
+@functools.lru_cache(maxsize=None)
+def bk2_real(n=REAL_N, seed=5, mask_seed=SEED_A):
+    """-> (ks, s2, b halves u64 [n][8][N2]): a real seeded key from the secrets cb_rotate_cases.real_case(n, seed) draws"""
+    ks = cb_rotate_cases.SmallKeys(n, seed)
+    s2 = client.keygen_lvl2(N2, seed=seed + 1)
+    return ks, s2, client.bk2_rows(ks, s2, L2, BGBIT2, ALPHA2, seed=seed + 2, mask_seed=mask_seed)
+
+
+@functools.lru_cache(maxsize=None)
+def bk2_real_jobs(n=REAL_N):
+    """-> (ct u32 [2][n + 1]: a 1 and a 0 under bk2_real's lvl0 secret, jobs (in, sign, off, mu), bits): each bit under both signs at the
+    three mu_r of the 128-bit set"""
+    ct = cb_rotate_cases.encrypt_lvl0(bk2_real(n)[0].s0, [1, 0], seed=671)
+    jobs = [(i, sign, 0, cb_rotate_cases.ref.mu_of(r, 6)) for i in (0, 1) for sign in (1, -1) for r in range(3)]
+    return ct, jobs, [1 - j[0] for j in jobs]
 
 
 def bk2_full_steps(b, mask_seed, first_step=0):
@@ -157,10 +201,10 @@ def bk2_full_steps(b, mask_seed, first_step=0):
     return np.ascontiguousarray(np.stack([a.reshape(b.shape), b], axis=2))
 
 
-def bk2_jobs():
+def bk2_jobs(n=BK2_N):
     """(lvl0 TLWEs u32 [4][n + 1], jobs (in, sign, off, mu, out)): four rotations, both signs, outputs in another order than inputs"""
     rng = np.random.default_rng(34)
-    tl = rng.integers(0, 1 << 32, size=(4, BK2_N + 1), dtype=np.uint64).astype(np.uint32)
+    tl = rng.integers(0, 1 << 32, size=(4, n + 1), dtype=np.uint64).astype(np.uint32)
     mus = [1 << (63 - (r + 1) * 6) for r in range(3)] + [1 << 61]
     jobs = [(g, 1 if g & 1 else -1, int(rng.integers(0, 1 << 32)), mus[g], 3 - g) for g in range(4)]
     return tl, jobs
